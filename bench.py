@@ -16,12 +16,18 @@ recording-iterations per second over all ranks; inputs are resident in HBM befor
 per-GPU work is fixed, recordings never talk to each other, RCCL carries only the barrier / max-over-ranks of the
 timings.
 
-Timing: W untimed warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both
-sides and reduced with MAX over the ranks; blocks are repeated until the timed region covers ``--min-seconds``
-(0.5 s by default: one block of the driver's 20 steps is 7 ms, too short to be stable) and the MEDIAN block gives
-``ms_per_step`` and ``value``; the spread is reported beside it.
+Timing: untimed steps of a second batch of the same recordings for ``--settle-seconds`` (an idle GPU starts at lower
+clocks), W untimed warm-up steps of the timed batch, then ONE block of exactly K steps, bracketed by barrier + synchronize on both
+sides and reduced with MAX over the ranks: ``ms_per_step`` = block time / K, ``value`` = recording-iterations per second
+of that block.  A plain run does nothing else: set-up, warm-up, the K steps, ``--dump-outputs`` if given, the line.
 
-Also on the same JSON line:
+``--dump-outputs DIR``: after the timed steps, what the batch hands its caller after the last step, as DIR/<name>.npy
+(float64): ``gamma`` [recordings, frames, S] at a fixed seeded sample of frames (``gamma_frames``) when all of it would
+exceed 64 MB, ``pi`` [recordings, S], ``elbo`` [recordings] (the last iteration's).  The inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
+
+``--full`` adds everything else, each measured in runs of its own (the sub-records repeat blocks of K steps until
+``--min-seconds`` and take the median block), on the same JSON line:
   roofline                  dominant kernel: algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak
   roofline_whole_iteration  the five launches of an iteration together, against the survey's byte count (SURVEY 8d:
                             one kernel per stage) and against the fused design's compulsory bytes
@@ -42,10 +48,11 @@ Also on the same JSON line:
                             third-party calls, pinned to the reference's outputs at this very size by
                             tests/test_oracle_golden.py) on the host cores, bounded sample (rank 0, N=1 only).  Always the
                             port: the same thing is timed on every box, and nothing of the reference travels
+  strong_scaling_form       N > 1: BASELINE configs[3] as stated, 64 recordings over all ranks
 
-Output: the FULL record goes to ``--full-out`` (default gpurun_out/bench_full.json) and to stderr; the LAST line of
-stdout is a compact JSON (< 4 KB, compact_record()) with the contract's keys, ``roofline``, ``cpu_baseline`` and a digest of
-the sub-records -- what the driver parses.
+Output: the FULL record goes to stderr and, with --full, to ``--full-out``; the LAST line of stdout is a compact JSON
+(< 4 KB, compact_record()) with the contract's keys and, with --full, ``roofline``, ``cpu_baseline`` and a digest of the
+sub-records -- what the driver parses.
 """
 from __future__ import annotations
 
@@ -167,16 +174,24 @@ def algo_bytes(kernel, T, R, S, esize, n_rec=1, rho_copies=None):
     return esize * (pr * T * R * (n_rec if rho_copies is None else rho_copies) + ps * T * S * n_rec)
 
 
-def make_batch(ctx, n_rec, T, S, D, precision, seed0, max_iters, streams=None):
-    from vbx_amd import _capi
+def batch_inputs(n_rec, T, S, D, seed0):
+    """(X, Phi, gamma0) of the recordings seed0 ... seed0 + n_rec - 1 of the headline workload"""
     from vbx_amd.synth import make_recording
-    batch = _capi.Batch(ctx, [T] * n_rec, [S] * n_rec, D, precision=precision, max_iters=max_iters)
-    if streams is not None and batch.streams != streams:
-        batch.set_option(_capi.OPT_STREAMS, streams)
+    out = []
     for b in range(n_rec):
         X, Phi, _ = make_recording(T, S, D=D, seed=seed0 + b, kappa=0.05, dtype=np.float32)
         g = np.random.default_rng(10_000 + seed0 + b).gamma(1.0, size=(T, S))
         g /= g.sum(1, keepdims=True)
+        out.append((X, Phi, g))
+    return out
+
+
+def make_batch(ctx, n_rec, T, S, D, precision, seed0, max_iters, streams=None, inputs=None):
+    from vbx_amd import _capi
+    batch = _capi.Batch(ctx, [T] * n_rec, [S] * n_rec, D, precision=precision, max_iters=max_iters)
+    if streams is not None and batch.streams != streams:
+        batch.set_option(_capi.OPT_STREAMS, streams)
+    for b, (X, Phi, g) in enumerate(inputs or batch_inputs(n_rec, T, S, D, seed0)):
         batch.set_recording(b, X, Phi, np.ones(S) / S, g, 0.99, 0.3, 17.0)
     return batch
 
@@ -310,6 +325,26 @@ def call_level(n_rec, T, S, D, precision, iters=40, reps=3):
                     'results into pinned host memory; float32 inputs, float64 gamma out'}
 
 
+DUMP_LIMIT = 60_000_000         # bytes of array data --dump-outputs may write over all ranks (under 64 MB with the headers)
+
+
+def dump_outputs(batch, path, T, S, prefix='', limit=DUMP_LIMIT):
+    """--dump-outputs: gamma, pi and the last ELBO of every recording of ``batch`` (vbx_batch_get_result: what a caller of
+    the batch receives), float64, as ``path/<prefix><name>.npy``.  gamma keeps a fixed seeded sample of its frames when
+    all of them would not fit ``limit``; ``gamma_frames`` holds their indices."""
+    n = batch.n
+    frames = min(T, (limit - n * (S + 1) * 8) // (n * S * 8 + 8))
+    if frames < 1:
+        raise SystemExit(f'--dump-outputs: {n} recordings of S={S} do not fit {limit} bytes')
+    idx = np.arange(T) if frames == T else np.sort(np.random.default_rng(0).choice(T, frames, replace=False))
+    res = [batch.result(b, want_model=False) for b in range(n)]
+    out = {'gamma': np.stack([r['gamma'][idx] for r in res]), 'gamma_frames': idx.astype(np.float64),
+           'pi': np.stack([r['pi'] for r in res]), 'elbo': np.array([r['Li'][-1] for r in res])}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, prefix + name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 COMPACT_LIMIT = 4096            # bytes: the driver parses the LAST stdout line; round 4's 25 KB line came back unparsed
 
 
@@ -405,7 +440,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
-    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=20,
+                    help='untimed steps of the timed batch before its K steps (after --settle-seconds on a second batch)')
     ap.add_argument('--batch', type=int, default=64, help='recordings per GPU')
     ap.add_argument('--T', type=int, default=10000)
     ap.add_argument('--S', type=int, default=30)
@@ -420,7 +456,17 @@ def main():
     ap.add_argument('--total-recordings', type=int, default=None,
                     help='strong scaling: this many recordings over ALL ranks (BASELINE configs[3] as stated: 64 over 8 GPUs = 8 '
                          'per GPU); --batch is then total / gpus and "scaling" says strong')
-    ap.add_argument('--min-seconds', type=float, default=0.5, help='timed region: blocks of K steps until this much time')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline (kernel probe and rooflines, the other GEMM mode, fp64, the '
+                         'BASELINE configurations, batch=1, the call level, the CPU baseline, on N GPUs the strong-scaling form) '
+                         'and write the full record to --full-out')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write gamma (a fixed seeded sample of frames if needed), pi and the last ELBO '
+                         'of every recording as DIR/<name>.npy, float64, at most 64 MB')
+    ap.add_argument('--settle-seconds', type=float, default=0.5,
+                    help='before the warm-up: untimed steps of a second batch of the same recordings for this long, so that '
+                         'the K steps do not run at the lower clocks of an idle GPU (0 = none)')
+    ap.add_argument('--min-seconds', type=float, default=0.5, help='--full sub-records: blocks of K steps until this much time')
     ap.add_argument('--max-blocks', type=int, default=200)
     ap.add_argument('--cpu-iters', type=int, default=20, help='oracle iterations for cpu_baseline (0 = skip)')
     ap.add_argument('--parity-iters', type=int, default=8, help='iterations 1 ... n over which gamma_max_abs_diff_vs_numpy is the maximum')
@@ -572,16 +618,38 @@ def main():
         return make_batch(ctx, n_rec, args.T, args.S, args.D, precision, seed0=rank * n_rec,
                           max_iters=max_iters, streams=streams)
 
-    per_kernel, dom, probe_ms_per_step, probe_blocks = kernel_probe(lambda mi, st: headline(head_prec, mi, st),
-                                                                     args.min_seconds / 2, args.max_blocks)
+    if args.full:
+        per_kernel, dom, probe_ms_per_step, probe_blocks = kernel_probe(lambda mi, st: headline(head_prec, mi, st),
+                                                                         args.min_seconds / 2, args.max_blocks)
 
-    # ---- the timed region: the library's default configuration, no per-kernel events
-    batch = headline(head_prec, budget, args.streams)
+    # ---- the timed region: the library's default configuration, no per-kernel events, one block of exactly K steps.  An
+    # idle GPU runs the first tenths of a second at lower clocks (blocks of 20 steps repeated for 0.5 s: the slowest 0.336 ms
+    # per step, the fastest 0.265, profiles/r02_split_bench_driver_args.json), so a second batch of the same recordings keeps
+    # it busy for --settle-seconds first; the timed batch itself runs W + K steps, and what it computes does not depend on
+    # the settling.  max_iters >= 40: the library picks the stream count of a small batch by it (auto_streams), and both
+    # batches must run the configuration of any step count
+    inputs = batch_inputs(args.batch, args.T, args.S, args.D, rank * args.batch)
+    mi = max(W + K + 16, 40)
+    batch = make_batch(ctx, args.batch, args.T, args.S, args.D, head_prec, rank * args.batch, mi, args.streams, inputs)
     streams = batch.streams
+    settle_steps, t_settle = 0, time.perf_counter()
+    if args.settle_seconds > 0:
+        settle = make_batch(ctx, args.batch, args.T, args.S, args.D, head_prec, rank * args.batch, mi, args.streams, inputs)
+        assert settle.streams == streams
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < args.settle_seconds:
+            settle.run(min(K, 200), -np.inf)              # (the ELBO history stops at max_iters; the iterations go on)
+            settle_steps += min(K, 200)
+    del inputs
+    settle_s = time.perf_counter() - t_settle
     batch.run(W, -np.inf)
-    times = timed_blocks(batch, args.min_seconds, args.max_blocks)
-    res0 = batch.result(0, want_model=False)
+    times = timed_blocks(batch, 0.0, 1)
     gemm_ran = batch.gemm
+    if args.settle_seconds > 0:
+        settle.close()
+    if args.dump_outputs:
+        dump_outputs(batch, args.dump_outputs, args.T, args.S, f'rank{rank}_' if world > 1 else '', DUMP_LIMIT // world)
+    res0 = batch.result(0, want_model=False) if args.full else None
     batch.close()
     med = statistics.median(times)
     if args.precision == 'fp32':
@@ -591,7 +659,7 @@ def main():
     # (strong scaling) -- next to the weak-scaling headline, so that one driver sweep N = 1, 2, 4, 8 yields both curves
     strong = None
     STATED_TOTAL = 64
-    if world > 1 and args.total_recordings is None and STATED_TOTAL % world == 0:
+    if args.full and world > 1 and args.total_recordings is None and STATED_TOTAL % world == 0:
         bs = headline(head_prec, budget, args.streams, n_rec=STATED_TOTAL // world)
         bs.run(W, -np.inf)
         ts_ = timed_blocks(bs, args.min_seconds / 2, args.max_blocks)
@@ -632,7 +700,7 @@ def main():
                 'kernels_avg_us': {k: round(v['avg_us'], 2) for k, v in pk.items()}, 'elbo_last': elbo}
 
     configs = {}
-    if rank == 0 and world == 1 and not args.no_configs:      # (a multi-GPU run measures the sharded batch only)
+    if args.full and rank == 0 and world == 1 and not args.no_configs:      # (a multi-GPU run measures the sharded batch only)
         def single(T, S, precision, lp):
             def make(mi, st):
                 from vbx_amd.synth import make_recording
@@ -699,7 +767,7 @@ def main():
                     rho_copies=1 if mode == 'shared' else None)
 
     other = None
-    if other_prec is not None and not args.no_split:
+    if args.full and other_prec is not None and not args.no_split:
         pko, dko, mso, _ = kernel_probe(lambda mi, st: headline(other_prec, mi, st), args.min_seconds / 4, args.max_blocks)
         bo = headline(other_prec, budget, args.streams)
         bo.run(W, -np.inf)
@@ -709,7 +777,7 @@ def main():
         other = (to, pko, dko, mso)
 
     f64 = None
-    if not args.no_f64 and args.precision == 'fp32':
+    if args.full and not args.no_f64 and args.precision == 'fp32':
         pk64, dk64, ms64, _ = kernel_probe(lambda mi, st: headline('fp64', mi, st), args.min_seconds / 4, args.max_blocks)
         b64 = headline('fp64', budget, args.streams)
         b64.run(W, -np.inf)
@@ -718,7 +786,7 @@ def main():
         f64 = (t64, pk64, dk64, ms64)
 
     single_rec = None
-    if not args.no_single and rank == 0 and world == 1:
+    if args.full and not args.no_single and rank == 0 and world == 1:
         b1 = make_batch(ctx, 1, args.T, args.S, args.D, args.precision, seed0=0, max_iters=W + 4 * K)
         b1.run(W, -np.inf)
         ts = []
@@ -733,16 +801,12 @@ def main():
         b1.close()
 
     call_rec = None
-    if rank == 0 and world == 1 and not args.no_call_level:
+    if args.full and rank == 0 and world == 1 and not args.no_call_level:
         call_rec = call_level(args.batch, args.T, args.S, args.D, head_prec)
 
     if rank == 0:
         total_units = world * args.batch * K
         workload = {'batch': args.batch, 'T': args.T, 'S': args.S, 'D': args.D, 'precision': head_prec}
-        roof, traffic = roofline_of(per_kernel, dom, args.batch, args.T, args.S, args.D, esize, workload)   # (profiled with --streams 1)
-        roof['measured'] = (f'HIP events over {probe_blocks} block(s) of K steps (after W warm-up steps) of the same batch on ONE '
-                            f'stream (VBX_OPT_STREAMS=1, {probe_ms_per_step:.4f} ms per step): a kernel-level figure needs the '
-                            'kernel alone on the GPU')
         out = {
             'metric': 'VB EM iterations/sec (T=10k xvecs, R=128, S=30)',
             'value': total_units / med,
@@ -763,18 +827,25 @@ def main():
                        'recordings_per_gpu': args.batch, 'T': args.T, 'R': args.D, 'S': args.S, 'streams_per_gpu': streams,
                        'parallelism': f'recordings sharded over {world} rank(s), no data-path collective'
                                       + ('' if backend == 'nccl' or world == 1 else f' [TEST HOOK: backend {backend}, every rank on GPU {device} -- not a scaling measurement]')},
-            'timed_region': {'blocks_of_K_steps': len(times), 'seconds': sum(times), 'statistic': 'median block',
-                             'ms_per_step_min': 1e3 * min(times) / K, 'ms_per_step_max': 1e3 * max(times) / K,
-                             'note': 'every block holds exactly K steps between barrier + synchronize; includes the '
-                                     'one gamma write-out (replay launch) per block'},
+            'timed_region': {'blocks_of_K_steps': len(times), 'seconds': sum(times),
+                             'settle_steps': settle_steps, 'settle_seconds': settle_s,
+                             'note': 'one block of exactly K steps between barrier + synchronize, after W untimed warm-up '
+                                     'steps; includes the one gamma write-out (replay launch) of the block.  Before them, '
+                                     'settle_steps untimed steps of a second batch of the same recordings'},
             'device': info['name'],
-            'kernels_avg_us': {k: round(v['avg_us'], 2) for k, v in per_kernel.items()},
-            'kernels_avg_us_note': 'one-stream pass: the HBM-side kernels (ALGO_PASSES) over the K steps, the others over 8 survey iterations; '
-                                   '"post" = the gamma write-out, once per run',
-            'roofline': roof,
-            'gamma_checks': {'row_sum_max_dev': float(np.abs(res0['gamma'].sum(1) - 1).max()),
-                             'elbo_last': float(res0['Li'][-1])},
         }
+        traffic = (None, None, None)
+        if args.full:
+            roof, traffic = roofline_of(per_kernel, dom, args.batch, args.T, args.S, args.D, esize, workload)   # (profiled with --streams 1)
+            roof['measured'] = (f'HIP events over {probe_blocks} block(s) of K steps (after W warm-up steps) of the same batch on ONE '
+                                f'stream (VBX_OPT_STREAMS=1, {probe_ms_per_step:.4f} ms per step): a kernel-level figure needs the '
+                                'kernel alone on the GPU')
+            out['kernels_avg_us'] = {k: round(v['avg_us'], 2) for k, v in per_kernel.items()}
+            out['kernels_avg_us_note'] = ('one-stream pass: the HBM-side kernels (ALGO_PASSES) over the K steps, the others over 8 '
+                                          'survey iterations; "post" = the gamma write-out, once per run')
+            out['roofline'] = roof
+            out['gamma_checks'] = {'row_sum_max_dev': float(np.abs(res0['gamma'].sum(1) - 1).max()),
+                                   'elbo_last': float(res0['Li'][-1])}
         # what one recording keeps resident in HBM: rho, in split mode also its two f16-pair copies
         # (4 bytes per element each, made once per upload by rho_absmax + rho_split: two more passes over rho inside the first
         # run, under VBX_K_PREP); b and the caller's gamma [T][Sp]; per chunk the partial sums and the three operators
@@ -843,12 +914,12 @@ def main():
             out['single_recording'] = single_rec
         if call_rec:
             out['call_level'] = call_rec
-        if world == 1 and args.cpu_iters > 0:
+        if args.full and world == 1 and args.cpu_iters > 0:
             cb = cpu_baseline(args.T, args.S, args.D, args.cpu_iters, head_prec, args.parity_iters, args.cpu_reference)
             out['cpu_baseline'] = cb
             if single_rec:
                 out['single_recording']['speedup_vs_cpu_baseline'] = single_rec['value'] / cb['value']
-        emit(out, args.full_out)
+        emit(out, args.full_out if args.full else None)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -13,6 +13,7 @@ compare the RTTM files byte for byte:
 import io
 import os
 import socket
+import struct
 import sys
 
 import numpy as np
@@ -20,7 +21,6 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(REPO, 'tests', 'golden', 'driver_split3.npz')
-REF = os.environ.get('VBX_REFERENCE', '/root/reference')
 RECS = ('recA', 'recB', 'recC')
 
 
@@ -162,26 +162,97 @@ def test_segments_rttm_and_label_merging(tmp_path):
     assert kf.read_rttm(q)[1] == ('rec', 1.08, 0.84, '2')
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, 'VBx', 'models')), reason='reference checkout not present')
-def test_readers_on_the_reference_files():
-    """The reference's own model files and example archive (authoring container): the HDF5 subset reader against
-    the known layout of transform.h5 (three contiguous float64 datasets), the PLDA and archive readers against the
-    values SURVEY.md App. B quotes."""
+def _h5_file(datasets):
+    """Bytes of an HDF5 file as h5py writes a handful of small float64 arrays (the layout of the reference's
+    transform.h5): superblock version 0, the root group as a symbol table (one B-tree leaf, one symbol node, a local
+    heap of names), one version-1 object header per dataset (dataspace, IEEE float64 datatype, contiguous layout
+    version 3), the data from byte 2048 on.  Written from "HDF5 File Format Specification Version 2.0", sections
+    III.A-D and IV.A, independently of vbx_amd.h5_minimal.  -> (bytes, {name: data offset})"""
+    import struct
+    undef = b'\xff' * 8
+    names = sorted(datasets)
+    name_off, heap = {}, b'\0' * 8
+    for n in names:
+        name_off[n] = len(heap)
+        heap += n.encode() + b'\0' * (8 - len(n) % 8)
+
+    def message(mtype, body):
+        body += b'\0' * (-len(body) % 8)
+        return struct.pack('<HHB3x', mtype, len(body), 0) + body
+
+    def object_header(msgs):
+        block = b''.join(msgs)
+        return struct.pack('<BxHII4x', 1, len(msgs), 1, len(block)) + block
+
+    root_hdr, btree, snod, heap_hdr, heap_data = 96, 136, 184, 312, 344
+    hdr_at = heap_data + len(heap)
+    headers, data_at, data_off = b'', 2048, {}
+    for n in list(datasets):                                  # (creation order; the symbol table is sorted by name)
+        a = np.ascontiguousarray(datasets[n], dtype='<f8')
+        data_off[n] = data_at
+        space = struct.pack('<BBB5x', 1, a.ndim, 0) + b''.join(struct.pack('<Q', d) for d in a.shape)
+        dtype = struct.pack('<B3BI', 0x11, 0x20, 63, 0, 8) + struct.pack('<HHBBBBI', 0, 64, 52, 11, 0, 52, 1023)
+        layout = struct.pack('<BBQQ', 3, 1, data_at, a.nbytes)
+        h = object_header([message(0x0001, space), message(0x0003, dtype), message(0x0008, layout)])
+        datasets[n] = (hdr_at + len(headers), a)
+        headers += h
+        data_at += a.nbytes
+    assert hdr_at + len(headers) <= 2048
+    out = bytearray(data_at)
+    out[0:56] = (b'\x89HDF\r\n\x1a\n' + bytes([0, 0, 0, 0, 0, 8, 8, 0]) + struct.pack('<HHI', 4, 16, 0)
+                 + struct.pack('<Q', 0) + undef + struct.pack('<Q', data_at) + undef)
+    out[56:96] = struct.pack('<QQII', 0, root_hdr, 1, 0) + struct.pack('<QQ', btree, heap_hdr)
+    out[root_hdr:btree] = object_header([message(0x0011, struct.pack('<QQ', btree, heap_hdr))])
+    out[btree:snod] = b'TREE' + struct.pack('<BBH', 0, 0, 1) + undef + undef + struct.pack('<QQQ', 0, snod, name_off[names[-1]])
+    entries = b''.join(struct.pack('<QQII16x', name_off[n], datasets[n][0], 0, 0) for n in names)
+    out[snod:snod + 8 + len(entries)] = b'SNOD' + struct.pack('<BxH', 1, len(names)) + entries
+    out[heap_hdr:heap_data] = b'HEAP' + struct.pack('<B3xQQQ', 0, len(heap), 0xFFFFFFFFFFFFFFFF, heap_data)
+    out[heap_data:hdr_at] = heap
+    out[hdr_at:hdr_at + len(headers)] = headers
+    for n in datasets:
+        out[data_off[n]:data_off[n] + datasets[n][1].nbytes] = datasets[n][1].tobytes()
+    return bytes(out), data_off
+
+
+def _kaldi_vector(v):
+    """Kaldi's binary form of a vector: 'FV ' / 'DV ', the size of the length field, the length, the data."""
+    v = np.ascontiguousarray(v)
+    return (b'FV ' if v.dtype == np.float32 else b'DV ') + b'\x04' + struct.pack('<i', v.size) + v.astype(v.dtype.newbyteorder('<')).tobytes()
+
+
+def test_readers_on_the_reference_files(tmp_path):
+    """The readers on files in the formats the reference ships, rebuilt byte by byte from the reference's own values
+    (driver_split3.npz: transform, PLDA, all 1025 x-vectors of its example archive) by writers that share no code with
+    vbx_amd: the HDF5 subset reader against the layout of transform.h5 (three contiguous float64 datasets at 2048, 4096,
+    5120), the binary Kaldi PLDA model and vector archive readers."""
     from vbx_amd import kaldi_formats as kf
     from vbx_amd.h5_minimal import read_datasets
-    path = f'{REF}/VBx/models/ResNet101_16kHz/transform.h5'
+    g = np.load(GOLD)
+    raw, offsets = _h5_file({'mean1': g['mean1'], 'mean2': g['mean2'], 'lda': g['lda']})
+    assert offsets == {'lda': 5120, 'mean1': 2048, 'mean2': 4096} and len(raw) == 267264
+    path = str(tmp_path / 'transform.h5')
+    open(path, 'wb').write(raw)
     d = read_datasets(path)
-    raw = open(path, 'rb').read()
     for name, (off, shape) in {'mean1': (2048, (256,)), 'mean2': (4096, (128,)), 'lda': (5120, (256, 128))}.items():
         assert np.array_equal(d[name], np.frombuffer(raw, '<f8', int(np.prod(shape)), off).reshape(shape))
+        assert np.array_equal(d[name], g[name])
+    assert np.array_equal(kf.read_xvec_transform(path)[2], g['lda'])
     with pytest.raises(KeyError):
         read_datasets(path, ('nope',))
-    mean, trans, psi = kf.read_plda(f'{REF}/VBx/models/ResNet101_16kHz/plda')
-    assert mean.shape == (128,) and trans.shape == (128, 128) and psi.shape == (128,)
-    items = list(kf.read_vec_flt_ark(f'{REF}/exp/ES2005a.ark'))
-    assert len(items) == 1025 and items[0][0] == 'ES2005a_0000-00000000-00000144' and items[0][1].shape == (256,)
-    g = np.load(GOLD)
-    assert np.array_equal(g['xvecs'], np.array([v for _, v in items])) and np.array_equal(g['plda_psi'], psi)
+    plda = str(tmp_path / 'plda')
+    trans = np.ascontiguousarray(g['plda_trans'], dtype='<f8')
+    open(plda, 'wb').write(b'\0B<Plda> ' + _kaldi_vector(g['plda_mean']) + b'DM \x04' + struct.pack('<i', trans.shape[0])
+                           + b'\x04' + struct.pack('<i', trans.shape[1]) + trans.tobytes() + _kaldi_vector(g['plda_psi'])
+                           + b'</Plda> ')
+    mean, trans_r, psi = kf.read_plda(plda)
+    assert mean.shape == (128,) and trans_r.shape == (128, 128) and psi.shape == (128,)
+    assert np.array_equal(mean, g['plda_mean']) and np.array_equal(trans_r, trans) and np.array_equal(psi, g['plda_psi'])
+    ark = str(tmp_path / 'x.ark')
+    open(ark, 'wb').write(b''.join(k.encode() + b' \0B' + _kaldi_vector(v) for k, v in zip(g['keys'].tolist(), g['xvecs'])))
+    items = list(kf.read_vec_flt_ark(ark))
+    assert len(items) == 1025 and items[0][0] == 'recA_0000-00000000-00000144' and items[0][1].shape == (256,)
+    assert [k for k, _ in items] == g['keys'].tolist()
+    assert np.array_equal(g['xvecs'], np.array([v for _, v in items]))
 
 
 def test_h5_reader_rejects_what_it_does_not_handle(tmp_path):

@@ -147,7 +147,7 @@ def test_rccl_gather_to_root_on_a_multi_gpu_box(tmp_path):
 @pytest.mark.skipif(_gpu_count() < 2, reason='fewer than two GPUs on this box')
 def test_bench_two_gpus_prints_a_compact_line_with_both_scaling_forms():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    res = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2',
+    res = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--full', '--steps', '5', '--warmup', '2',
                           '--min-seconds', '0.1', '--batch', '8', '--full-out', ''], env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith('{')][-1]
@@ -162,7 +162,7 @@ def test_bench_n_rank_code_path_on_one_gpu():
     (backend gloo, both ranks on device 0).  Not a scaling measurement; the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(VBX_AMD_DIST_BACKEND='gloo', VBX_AMD_DEVICE='0')
-    res = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2',
+    res = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--full', '--steps', '5', '--warmup', '2',
                           '--min-seconds', '0.05', '--batch', '6', '--full-out', ''], env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]

@@ -12,8 +12,8 @@ cp $out/config_parity.json $out/${r}_config_parity.json 2>/dev/null
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -4
 ( time bash tools/profiles.sh $r > $out/${r}_profiles.log 2>&1 ) 2>&1 | grep real
 # (stdout of bench.py = the compact line the driver parses; the full record goes to --full-out; stderr repeats it)
-( time python bench.py --full-out $out/${r}_bench_default.json > $out/${r}_bench_default_compact.json 2> /dev/null ) 2>&1 | grep real
-( time python bench.py --steps 20 --warmup 5 --full-out $out/${r}_bench_driver_args.json > $out/${r}_bench_driver_args_compact.json 2> /dev/null ) 2>&1 | grep real
+( time python bench.py --full --full-out $out/${r}_bench_default.json > $out/${r}_bench_default_compact.json 2> /dev/null ) 2>&1 | grep real
+( time python bench.py --full --steps 20 --warmup 5 --full-out $out/${r}_bench_driver_args.json > $out/${r}_bench_driver_args_compact.json 2> /dev/null ) 2>&1 | grep real
 wc -c $out/${r}_bench_driver_args_compact.json
 # what one GPU delivers at the per-GPU batch of BASELINE configs[3] as stated on 1 / 2 / 4 / 8 GPUs, the call
 # level of the headline batch, the launch gaps of a small batch, the one-step error of the fp32 paths

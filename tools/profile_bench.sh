@@ -9,6 +9,7 @@ tag=$1; shift
 # (bench.py takes the batch shape and the precision, not profile_target.py's sweep flag)
 BENCH_ARGS=$(echo "$*" | sed -e 's/--sweep [a-z]*//')
 export VBX_AMD_NO_REBUILD=1
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
@@ -19,7 +20,7 @@ timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $out/write -o write -- 
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY $SQ_EXTRA -d $out/sq -o sq -- $common > $out/sq.log 2>&1
 # (optional second SQ pass, SQ2="counter ...": what the SIMDs issue -- SQ_ACTIVE_INST_VALU / _LDS / _SCA beside the matrix pipes)
 [ -n "$SQ2" ] && timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES $SQ2 -d $out/sq2 -o sq2 -- $common > $out/sq2.log 2>&1
-[ -z "$NO_BENCH" ] && timeout 900 rocprofv3 --kernel-trace --stats -d $out/bench -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --cpu-iters 0 --no-f64 --no-single --no-configs $BENCH_ARGS > $out/bench.log 2>&1
+[ -z "$NO_BENCH" ] && timeout 900 rocprofv3 --kernel-trace --stats -d $out/bench -o bench -- python $repo/bench.py --full --steps 20 --warmup 5 --cpu-iters 0 --no-f64 --no-single --no-configs $BENCH_ARGS > $out/bench.log 2>&1
 cd $GRAFT_REPO_ROOT
 python tools/rocpd_stats.py $out/trace/trace_results.db $out/kernel_stats.txt > /dev/null
 [ -z "$NO_BENCH" ] && python tools/rocpd_stats.py $out/bench/bench_results.db $out/bench_py_kernel_stats.txt > /dev/null
