@@ -352,6 +352,32 @@ int vbx_gather_rows(const void* buf, int64_t len, const int64_t* offsets, int64_
 int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, double* llr);
 int vbx_scores_destroy(vbx_scores* sc);
 
+/* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
+ * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
+ * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then
+ * cmvn_floating_kaldi(., LC, RC, norm_vars=False) cast to float32.  The four linear steps run as ONE f64 operator on the
+ * matrix cores (vbx_fbank.hpp).  The dither is the caller's (numpy's generator: predict.py:169-170). */
+typedef struct vbx_fbank vbx_fbank;
+/* window [winlen], mel [nfft/2 + 1][n_mel] f64 (features.mel_fbank_mx).  Geometries built: winlen / shift / nfft =
+ * 400 / 160 / 512 (16 kHz) and 200 / 80 / 256 (8 kHz), n_mel = 64; others: VBX_ERR_UNSUPPORTED. */
+int vbx_fbank_create(vbx_ctx* ctx, int32_t winlen, int32_t shift, int32_t nfft, int32_t n_mel, const double* window,
+                     const double* mel, double preemph, vbx_fbank** out);
+/* signal [n_samples] f64 (one recording or several laid end to end); seg [n_seg][2] = (first sample, samples) of every
+ * segment to process, clipped to its recording and longer than (winlen - shift) / 2 samples.  The features of all
+ * segments land in one device array of rows [*n_frames][n_mel], segment after segment, (padded - winlen) / shift + 1
+ * rows each.  Returns once the host arrays may be reused. */
+int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_t n_seg, const int64_t* seg, int32_t cmn_lc,
+                  int32_t cmn_rc, int64_t* n_frames);
+/* rows [row0, row0 + nrows) of the last run: which = 0 the CMN features (f32), 1 the log-Mel rows before CMN (f64).
+ * dst_on_device != 0: dst is device memory of the ctx's device (e.g. a torch tensor).  Synchronises before it returns. */
+int vbx_fbank_get(vbx_fbank* fb, int which, int64_t row0, int64_t nrows, void* dst, int dst_on_device);
+/* n windows of len rows of the CMN features starting at rows starts[n], transposed to dst [n][n_mel][len] f32 (the
+ * embedding model's [B, C, T] input, predict.py:68-70).  Synchronises before it returns. */
+int vbx_fbank_windows(vbx_fbank* fb, int32_t n, const int64_t* starts, int32_t len, float* dst, int dst_on_device);
+/* device milliseconds (HIP events) of the last run: ms[0] upload, [1] frame kernel, [2] CMN; ms[3] the last windows call. */
+int vbx_fbank_times(vbx_fbank* fb, float* ms);
+int vbx_fbank_destroy(vbx_fbank* fb);
+
 #ifdef __cplusplus
 }
 #endif

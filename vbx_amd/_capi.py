@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     'vbx_batch_set_recording_resident', 'vbx_batch_get_labels', 'vbx_batch_set_recording_shared',
     'vbx_batch_gemm_in_effect',
     'vbx_batch_stream_of', 'vbx_batch_sync_uploads', 'vbx_batch_get_results', 'vbx_host_alloc', 'vbx_host_free',
+    'vbx_fbank_create', 'vbx_fbank_run', 'vbx_fbank_get', 'vbx_fbank_windows', 'vbx_fbank_times', 'vbx_fbank_destroy',
 ]
 
 
@@ -118,6 +119,12 @@ def load():
     lib.vbx_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     lib.vbx_host_free.argtypes = [vp]
     lib.vbx_batch_set_recording_shared.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, dbl, dbl, dbl]
+    lib.vbx_fbank_create.argtypes = [vp, i32, i32, i32, i32, vp, vp, dbl, C.POINTER(vp)]
+    lib.vbx_fbank_run.argtypes = [vp, i64, vp, i32, vp, i32, i32, C.POINTER(i64)]
+    lib.vbx_fbank_get.argtypes = [vp, C.c_int, i64, i64, vp, C.c_int]
+    lib.vbx_fbank_windows.argtypes = [vp, i32, vp, i32, vp, C.c_int]
+    lib.vbx_fbank_times.argtypes = [vp, vp]
+    lib.vbx_fbank_destroy.argtypes = [vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -313,6 +320,72 @@ class XVectors:
     def close(self):
         if getattr(self, '_h', None):
             self._lib.vbx_xvectors_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FbankDevice:
+    """The filterbank front end of one sample rate on one device (vbx_fbank): the folded f64 frame operator stays
+    resident; every run replaces the features of the previous one."""
+
+    def __init__(self, ctx: Context, winlen, shift, nfft, window, mel, preemph=0.97):
+        self.ctx, self._lib = ctx, ctx._lib
+        window, mel = _f64(window), _f64(mel)
+        assert window.shape == (winlen,) and mel.shape[0] == nfft // 2 + 1
+        h = C.c_void_p()
+        ctx.check(self._lib.vbx_fbank_create(ctx._h, int(winlen), int(shift), int(nfft), int(mel.shape[1]), _ptr(window),
+                                             _ptr(mel), float(preemph), C.byref(h)), 'vbx_fbank_create')
+        self._h, self.n_mel, self.rows = h, int(mel.shape[1]), 0
+
+    def run(self, signal, segs, lc=150, rc=149):
+        """signal f64 [n]; segs int64 [n_seg][2] (first sample, samples).  Returns the number of feature rows."""
+        signal = _f64(signal)
+        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 2)
+        rows = C.c_int64()
+        self.ctx.check(self._lib.vbx_fbank_run(self._h, signal.shape[0], _ptr(signal), segs.shape[0], _ptr(segs), int(lc),
+                                               int(rc), C.byref(rows)), 'vbx_fbank_run')
+        self.rows = rows.value
+        return self.rows
+
+    def get(self, which, row0, nrows, dst_ptr=None):
+        """rows of the CMN features ('fea', f32) or the log-Mel rows ('logmel', f64); into a host array, or into device
+        memory at dst_ptr (returns None then)."""
+        w = 0 if which == 'fea' else 1
+        out = None
+        if dst_ptr is None:
+            out = np.empty((nrows, self.n_mel), dtype=np.float32 if w == 0 else np.float64)
+            dst_ptr = out.ctypes.data
+        self.ctx.check(self._lib.vbx_fbank_get(self._h, w, int(row0), int(nrows), C.c_void_p(dst_ptr), int(out is None)),
+                       'vbx_fbank_get')
+        return out
+
+    def windows(self, starts, length, dst_ptr=None):
+        """[n][n_mel][length] f32 windows of the CMN features from rows starts[n] (host array, or into device memory)."""
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        out = None
+        if dst_ptr is None:
+            out = np.empty((starts.shape[0], self.n_mel, int(length)), dtype=np.float32)
+            dst_ptr = out.ctypes.data
+        self.ctx.check(self._lib.vbx_fbank_windows(self._h, starts.shape[0], _ptr(starts), int(length), C.c_void_p(dst_ptr),
+                                                   int(out is None)), 'vbx_fbank_windows')
+        return out
+
+    def times(self):
+        """device ms of the last run: upload, frame kernel, CMN, and of the last windows call: gather."""
+        ms = np.zeros(4, dtype=np.float32)
+        self.ctx.check(self._lib.vbx_fbank_times(self._h, _ptr(ms)), 'vbx_fbank_times')
+        return dict(zip(('upload', 'frame', 'cmn', 'gather'), ms.astype(float).tolist()))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.vbx_fbank_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,125 @@
+"""python -m vbx_amd.predict: predict.py's x-vector extraction with the front end on the GPU.
+
+The command line is predict.py's.  The features of a file come from the device front end (vbx_amd.fbank: log-Mel
+filterbank, floating CMN, windows cut straight into the model's [B, 64, 144] layout); the embedding model is a
+TorchScript module (``--model-file``) run by PyTorch on the same device, full windows ``--batch-size`` at a time and the
+tail windows grouped by length.  The ark file and the segments file are the ones predict.py writes, in its order.  The
+dither of the next file is drawn on the host while the device works on the current one.
+
+Not supported: ``--backend onnx`` and ``--model/--weights`` (the reference's network definition is not part of this
+package; export the model to TorchScript instead).
+"""
+from __future__ import annotations
+
+import argparse
+import concurrent.futures
+import logging
+import os
+import struct
+import sys
+import time
+
+import numpy as np
+
+from . import fbank
+
+logger = logging.getLogger('vbx_amd.predict')
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument('--gpus', type=str, default='', help='the device to run on (first index of the list); required')
+    p.add_argument('--model', type=str, default=None, help='not supported: use --model-file')
+    p.add_argument('--weights', type=str, default=None, help='not supported: use --model-file')
+    p.add_argument('--model-file', type=str, default=None, help='TorchScript embedding model: [B, ndim, T] -> [B, embed]')
+    p.add_argument('--ndim', type=int, default=64, help='dimensionality of features')
+    p.add_argument('--embed-dim', type=int, default=256, help='dimensionality of the emb')
+    p.add_argument('--seg-len', type=int, default=144, help='segment length')
+    p.add_argument('--seg-jump', type=int, default=24, help='segment jump')
+    p.add_argument('--in-file-list', required=True, type=str, help='input list of files')
+    p.add_argument('--in-lab-dir', required=True, type=str, help='input directory with VAD labels')
+    p.add_argument('--in-wav-dir', required=True, type=str, help='input directory with wavs')
+    p.add_argument('--out-ark-fn', required=True, type=str, help='output embedding file')
+    p.add_argument('--out-seg-fn', required=True, type=str, help='output segments file')
+    p.add_argument('--backend', default='pytorch', choices=['pytorch', 'onnx'], help='only pytorch is supported')
+    p.add_argument('--batch-size', type=int, default=128, help='full windows per model call')
+    p.add_argument('--no-dither', action='store_true', help='skip the dither (the reference always adds it)')
+    args = p.parse_args(argv)
+    if args.backend == 'onnx':
+        p.error('--backend onnx is not supported: export the model to TorchScript and pass --model-file')
+    if args.model is not None or args.model_file is None:
+        p.error('--model/--weights are not supported (the network definition is not part of this package): '
+                'pass a TorchScript module with --model-file')
+    if args.gpus.strip() == '':
+        p.error('--gpus is empty: this extractor runs on a GPU only; pass a device index such as --gpus 0')
+    if args.ndim != fbank.N_MEL:
+        p.error(f'--ndim must be {fbank.N_MEL} (the filterbank has {fbank.N_MEL} channels)')
+    if args.seg_len <= 0 or args.seg_jump <= 0 or args.batch_size <= 0:
+        p.error('--seg-len, --seg-jump and --batch-size must be positive')
+    return args
+
+
+def _ark_entry(key: str, vec: np.ndarray) -> bytes:
+    """kaldi_io.write_vec_flt: '<key> \\0B' + 'FV ' / 'DV ' + '\\4' + int32 dim + the values."""
+    tag = b'FV ' if vec.dtype == np.float32 else b'DV '
+    return (key + ' ').encode('latin1') + b'\0B' + tag + b'\4' + struct.pack('<i', vec.shape[0]) + vec.tobytes()
+
+
+def _load(args, fn):
+    samples, sr = fbank.read_wav(os.path.join(args.in_wav_dir, fn) + '.wav')
+    labs = fbank.read_lab(os.path.join(args.in_lab_dir, fn) + '.lab', sr)
+    sig, segs = fbank.prepare(samples, labs, sr, dither_signal=not args.no_dither)
+    return sr, sig, segs
+
+
+def embed_file(model, fe, fn, sig, segs, sr, args, torch):
+    """(key, segments line, embedding) of every window of one file, in predict.py's order."""
+    rows = fe.run([(sig, segs)])[0]
+    plan = fbank.window_plan(fn, segs, sr, args.seg_len, args.seg_jump)
+    emb = [None] * len(plan)
+    groups = {}
+    for i, w in enumerate(plan):
+        groups.setdefault(w.end - w.start, []).append(i)
+    for length, idx in groups.items():
+        step = args.batch_size if length == args.seg_len else len(idx)
+        for b0 in range(0, len(idx), step):
+            part = idx[b0:b0 + step]
+            x = fe.windows([rows[plan[i].seg] + plan[i].start for i in part], length, out='torch')
+            y = model(x).detach().cpu().numpy()
+            for i, v in zip(part, y):
+                emb[i] = v
+    return [(w.key, w.line, e) for w, e in zip(plan, emb)]
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    logging.basicConfig(level=logging.INFO)
+    import torch
+    device = int(args.gpus.split(',')[0])
+    if not torch.cuda.is_available() or device >= torch.cuda.device_count():
+        raise SystemExit(f'--gpus {args.gpus}: no such GPU visible to PyTorch')
+    tdev = torch.device('cuda', device)
+    model = torch.jit.load(args.model_file, map_location=tdev)
+    model.eval()
+    file_names = [str(f) for f in np.atleast_1d(np.loadtxt(args.in_file_list, dtype=object))]
+    pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+    nxt = pool.submit(_load, args, file_names[0]) if file_names else None
+    with torch.no_grad(), open(args.out_seg_fn, 'w') as seg_file, open(args.out_ark_fn, 'wb') as ark_file:
+        for k, fn in enumerate(file_names):
+            t0 = time.time()
+            sr, sig, segs = nxt.result()
+            nxt = pool.submit(_load, args, file_names[k + 1]) if k + 1 < len(file_names) else None
+            fe = fbank.front_end(sr, device)
+            for key, line, vec in embed_file(model, fe, fn, sig, segs, sr, args, torch):
+                if np.isnan(vec).any():
+                    logger.warning(f'NaN found, not processing: {key}{os.linesep}')
+                    continue
+                seg_file.write(line + os.linesep)
+                ark_file.write(_ark_entry(key, vec))
+            logger.info(f'{fn}: {time.time() - t0:.3f} s')
+    pool.shutdown()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
