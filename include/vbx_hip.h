@@ -73,7 +73,7 @@ extern "C" {
 #define VBX_OPT_THREE_LEVEL_FROM 13 /* chunk count from which VBX_OPT_SCAN_GROUP2 = 0 adds the third level            */
 #define VBX_OPT_SPLIT_TILES 11  /* fused path: tiles re-run as two halves side by side (four 64-frame chains per tile instead of two
                                    128-frame ones; chunk_loglik hands the half-tile operators over).  0 = auto (on), 1 = on,
-                                   2 = off; env VBX_AMD_SPLIT_TILES overrides                                             */
+                                   2 = off                                                                                */
 #define VBX_OPT_STREAMS 10      /* HIP streams of a batch: its recordings are dealt to that many sub-batches, one
                                    iteration of each is launched stream after stream, so the latency-bound launches of
                                    one overlap the bandwidth-bound ones of the others.  0 = auto (3 from 24 recordings and

@@ -49,5 +49,5 @@ for name in pr:
             print('   first bad tile', t, 'speakers', np.nonzero(dd.max(1))[0][:16], 'dims', np.nonzero(dd.max(0))[0][:40], 'values', sh[name][k][t][dd > 0][:6], sh[name][0][t][dd > 0][:6])
 tot = sum(int((np.abs(sh['mpart'][k] - sh['mpart'][0]).reshape(nt, -1).max(1) > 0).sum()) for k in range(n_rec))
 tot_p = sum(int((np.abs(pr['mpart'][k] - sh['mpart'][0]).reshape(nt, -1).max(1) > 0).sum()) for k in range(n_rec))
-print('SUMMARY lib', os.environ.get('VBX_AMD_LIB', 'default'), 'mask', os.environ.get('VBX_AMD_SPLIT_MASK'), 'bad tiles among sharers', tot, 'private tiles differing from shared rec0', tot_p, flush=True)
+print('SUMMARY lib', os.environ.get('VBX_AMD_LIB', 'default'), 'bad tiles among sharers', tot, 'private tiles differing from shared rec0', tot_p, flush=True)
 print('NANS', {n: (int(np.isnan(pr[n]).sum()), int(np.isnan(sh[n]).sum())) for n in pr}, flush=True)

@@ -2,15 +2,11 @@
 
 Three recordings on one shared rho with the same hyper-parameters (T = 60 000: more workgroups than the chip holds at
 once, so that workgroups in every phase share a CU) must agree bit for bit; the tiles whose partial sums differ are counted.
-Run on A/B builds of the library (tools/build_variants.sh):
-    cutbp  -DVBX_CUT_VIA_BPERMUTE    chunk_post's product at the cut with __shfl_xor, as round 3 had it: the compiler then
-                                     vectorises the product into v_pk_fma_f32 ... op_sel:[0,1,0] and the build FAILS
-    allbp  -DVBX_XOR_VIA_BPERMUTE    every add_xor / max_xor through __shfl_xor: fails the same way
-and on the production library, which must not.  (Round 4 also ran builds that computed the reduction both ways in the
-kernel and compared -- ds_bpermute_b32 and v_permlane*_swap agreed in all 50 652 reductions -- and builds with the
-reduction as fixed machine code around the permutes: none of those failed, none held the packed form.)
+The shipped library must show no difference.  (Round 4 ran it on builds that took chunk_post's product at the cut, or
+every add_xor / max_xor, through __shfl_xor as round 3 had it: the compiler then vectorised the product into
+v_pk_fma_f32 ... op_sel:[0,1,0] and those builds failed -- DESIGN section 6, NOTES.md "Variants removed from the tree".)
 
-usage: VBX_AMD_LIB=vbx_amd/csrc/libvbx_hip_<tag>.so python tools/hazard/bpermute_compare.py [T S n_rec precision reps]
+usage: python tools/hazard/bpermute_compare.py [T S n_rec precision reps]   (VBX_AMD_LIB=<path> checks another build)
 """
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -1,7 +1,7 @@
 // cut_sequence_probe.hip -- the instruction stream that failed in chunk_post, outside of chunk_post.
 //
-// The -DVBX_CUT_VIA_BPERMUTE build of the library (the product at the cut of the backward wave with __shfl_xor, as round 3
-// compiled it) gives wrong sums in a few of 1400 workgroups per launch once the chip is full.  Isolated patterns that
+// A build of the library with the product at the cut of the backward wave through __shfl_xor (as round 3 compiled it;
+// removed from the tree since) gives wrong sums in a few of 1400 workgroups per launch once the chip is full.  Isolated patterns that
 // were suspected first -- the permute whose address register is overwritten in the next slot, a packed instruction
 // feeding an LDS instruction in the next slot, an s_waitcnt as the only separator of two dependent packed FMAs
 // (bpermute_probe / pk_forward_probe / pk_waitstate_probe) -- never failed.  This probe runs the WHOLE stream of the failing

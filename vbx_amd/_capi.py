@@ -503,19 +503,6 @@ class Batch:
         if algo:
             self.set_option(OPT_FB_ALGO, choice('VBX_AMD_FB_ALGO', algo, {'auto': FB_AUTO, 'sequential': FB_SEQUENTIAL,
                                                                           'chunked': FB_CHUNKED}))
-        if experiment_env('VBX_AMD_TWO_LEVEL_FROM') is not None:
-            self.set_option(OPT_TWO_LEVEL_FROM, int(experiment_env('VBX_AMD_TWO_LEVEL_FROM')))
-        group = experiment_env('VBX_AMD_SCAN_GROUP')      # chunks per group of the two-level boundary walk
-        if group is not None:
-            self.set_option(OPT_SCAN_GROUP, int(group))
-        group2 = experiment_env('VBX_AMD_SCAN_GROUP2')    # level-2 groups of the three-level walk (0 auto, 1 off)
-        if group2 is not None:
-            self.set_option(OPT_SCAN_GROUP2, int(group2))
-        if experiment_env('VBX_AMD_THREE_LEVEL_FROM') is not None:
-            self.set_option(OPT_THREE_LEVEL_FROM, int(experiment_env('VBX_AMD_THREE_LEVEL_FROM')))
-        split = experiment_env('VBX_AMD_SPLIT_TILES')     # 1 / 2: half-tile re-runs on / off (0: the library's choice)
-        if split is not None:
-            self.set_option(OPT_SPLIT_TILES, int(split))
         # VBX_OPT_GEMM: the precision argument decides where it names a mode ('fp32-split'); VBX_AMD_GEMM = exact | split
         # decides for a plain 'fp32' -- an explicit argument is never overridden by the environment, in either direction
         gemm = os.environ.get('VBX_AMD_GEMM')

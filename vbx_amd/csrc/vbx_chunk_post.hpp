@@ -25,34 +25,12 @@
 // from the b, boundary vectors and priors of each recording's last iteration, which stay in HBM untouched once it
 // has stopped).  Measured on 64 recordings of T = 10 000, S = 30: 174 -> 165 us per launch, 77 MB less written.
 //
-// Tried and dropped (round 2): one workgroup walking a RUN of several tiles with the accumulators kept in registers
-// across them (one partial per run instead of per tile) and b of the next tile prefetched into `r1` during the
-// accumulation.  As a loop the compiler keeps per-lane addresses of the whole body live across it (100-130 spilled
-// registers at the 128-register budget of four workgroups per CU; laundering the lane index per tile and unrolling
-// the loop completely brings that to ~25); measured 182 us (two tiles per run), 226 us (three), 277-333 us (five:
-// one balanced round of persistent workgroups also puts the phases of the whole chip in lock-step) against 165 us.
-//
-// (What worked in the end is the half-tile scheme above: two operators per tile from chunk_loglik, 8 KB per tile.)
-// Also tried and dropped (round 2): the tile cut into four SUB-CHUNKS of 32 frames that re-run side by side in the four
-// 16-lane rows of the two re-run waves (32 dependent steps instead of 128; elimination runs of the re-run cut to 64 /
-// 32 / 4 frames: 134 / 119 / 107 us).  The vectors at the three inner edges need the sub-chunks' S x S transfer
-// operators; built here from the b tile (vbx_operator.hpp, all four waves) and pushed through by three mat-vecs per
-// direction the kernel took 190 us: the operator build is S^2 FMAs per frame of VALU work -- the same 40-45 us it
-// costs chunk_loglik, chip-wide VALU throughput, not latency -- and the edge chain + two more barriers eat what is
-// left of the gain.  Handing the operators over from chunk_loglik instead would add 16 KB per tile to both kernels'
-// traffic (+20 %) for an estimated 135 us.
-//
 // LDS: 2 regions of kTileFrames x SP + ~3 KB: 35 KB at SP = 32 (f32) -> four workgroups per CU.
 // Instrumentation build: -DVBX_PHASE_CLOCKS (per-workgroup phase stamps, tools/phase_timeline.py).
 #pragma once
 #include <type_traits>
 #include "vbx_scan.hpp"
 #include "vbx_split.hpp"
-
-// 0: the four chains of a split tile on four waves (A/B builds)
-#ifndef VBX_POST_PACKED
-#define VBX_POST_PACKED 1
-#endif
 
 namespace vbx {
 
@@ -106,15 +84,12 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
     __shared__ R nsum_w[SPLIT ? 4 : 1][SP];            // SPLIT: sum of gamma per wave and speaker (taken from registers)
 
     // (without a table the tiles are taken from the last one down: chunk_loglik has just written b and the half-tile operators
-    //  front to back, so the ones written last -- still in the memory-side cache -- are read first; VBX_POST_REVERSE=0: A/B)
-#ifndef VBX_POST_REVERSE
-#define VBX_POST_REVERSE 1
-#endif
+    //  front to back, so the ones written last -- still in the memory-side cache -- are read first)
     // (round 6: only when the launch's working set is beyond the L2s -- 80 KB per tile against 8 x 4 MB.  A smaller batch keeps the
     //  tile -> XCD map of chunk_loglik, block b on XCD b % 8, so that b and the half-tile operators are found in the L2 that wrote
     //  them: one recording 46.9 -> 45.8 us per iteration, fp64 69.1 -> 67.1, two recordings 49.5 -> 48.2, eight: no difference)
-    const int tile = (VBX_POST_REVERSE && !REPLAY && !bt.tile_order && bt.ntiles_total > 512) ? bt.ntiles_total - 1 - (int)blockIdx.x
-                                                                                              : tile_of_block(bt, blockIdx.x);
+    const int tile = (!REPLAY && !bt.tile_order && bt.ntiles_total > 512) ? bt.ntiles_total - 1 - (int)blockIdx.x
+                                                                          : tile_of_block(bt, blockIdx.x);
     if (tile < 0 || (!REPLAY && bt.tile_done[tile])) return;
     VBX_CLOCKS_DECL();
     // (the wave index as a scalar: roles, frame ranges and loop bounds of the re-run stay in SGPRs)
@@ -142,7 +117,7 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
         // same instruction stream, LDS rows offset by H frames per lane -- while waves 2 and 3 only compute the vectors at
         // the cut.  Half as many chain waves compete for a SIMD and the re-run issues half the vector instructions.
         const bool chunk0 = (t0 == 0);
-        const bool packed = VBX_POST_PACKED && split && len == kTileFrames && !chunk0;     // (uniform)
+        const bool packed = split && len == kTileFrames && !chunk0;     // (uniform)
         const int hl = packed ? (g4 >> 1) : 0;             // the half this lane's row walks in a packed wave
         const int hoff = hl * H, soh = so + hoff * SP;     // ... as a frame offset / an offset into a lattice region
         const int clo = packed ? 0 : lo, chi = packed ? H : hi, cm = packed ? H / 2 : m;   // chain range and crossing
@@ -398,15 +373,8 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
                     R tot = 0;
 #pragma unroll
                     for (int ii = 0; ii < QS; ++ii) tot += opb[r][ii] * mv_w[1][g4 * QS + ii];
-#ifdef VBX_CUT_VIA_BPERMUTE
-                    // (A/B build, tools/hazard/bpermute_compare.py: with __shfl_xor here the compiler vectorises the product
-                    //  over r into v_pk_fma_f32 ... op_sel:[0,1,0] -- the form of DESIGN section 6 -- and the build fails as round 3's did)
-                    tot += __shfl_xor(tot, 16, 64);
-                    tot += __shfl_xor(tot, 32, 64);
-#else
                     tot = add_xor<16>(tot);
                     tot = add_xor<32>(tot);
-#endif
                     x[r] = tot;
                     tj[r] = (tot > (R)0 && ope[r] > kNoMass / 2) ? ope[r] + exponent_of(tot) : kNever;
                     top = max(top, tj[r]);
@@ -542,11 +510,7 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
         // pass; with the streams of a big batch side by side the earlier request measured 0.2315 / 0.2319 / 0.2340 -> 0.2249 / 0.2258 / 0.2275 ms per step (three
         // A/B pairs in one call; on ONE stream 0.2603 -> 0.2629: the loads of a lone launch queue up behind each other), the C5
         // sweep 1.421 -> 1.408; small batches: see FOLD above
-#ifndef VBX_POST_ALLAHEAD
-#define VBX_POST_ALLAHEAD 1
-#endif
-        constexpr bool kAllAhead = (FOLD || (VBX_POST_ALLAHEAD && SP >= 32)) && SPLIT && !REPLAY;
-        R2 bq_all[kAllAhead && !SPLIT ? 4 : 1][QK];
+        constexpr bool kAllAhead = SPLIT && (FOLD || SP >= 32);
         if constexpr (SPLIT) {
             if (wave * 32 < Dp) {
                 load_kstep(0, wave, 0);
@@ -554,11 +518,6 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
 #pragma unroll
                     for (int kk = 1; kk < 4; ++kk) load_kstep(kk, wave, kk);
                 }
-            }
-        } else if constexpr (kAllAhead) {
-            if (wave * 32 < Dp) {
-#pragma unroll
-                for (int qi = 0; qi < 4; ++qi) load_quarter(bq_all[qi], wave, qi);
             }
         } else {
             if (!REPLAY && wave * 32 < Dp) load_quarter(bq[0], wave, 0);
@@ -758,7 +717,7 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
                 acc[mu][1] = acc_t{0, 0, 0, 0};
                 nsum[mu] = 0;
             }
-            if (slab != wave || kAllAhead) { if (!(kAllAhead && slab == wave)) load_quarter(bq[0], slab, 0); }
+            if (slab != wave) load_quarter(bq[0], slab, 0);
             auto quarter = [&](const R2 (&bfr)[QK], int qi) {
 #pragma unroll
                 for (int u = 0; u < QK; ++u) {
@@ -773,17 +732,12 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
                     }
                 }
             };
-            if (kAllAhead && slab == wave) {                     // the small-batch instances: the slab has been in flight since the start
-#pragma unroll
-                for (int qi = 0; qi < 4; ++qi) quarter(bq_all[qi], qi);
-            } else {
 #pragma unroll 1
-                for (int pair = 0; pair < 2; ++pair) {           // (not unrolled: bounds how many LDS reads are hoisted)
-                    load_quarter(bq[1], slab, 2 * pair + 1);     // next quarter in flight
-                    quarter(bq[0], 2 * pair);
-                    if (pair == 0) load_quarter(bq[0], slab, 2);
-                    quarter(bq[1], 2 * pair + 1);
-                }
+            for (int pair = 0; pair < 2; ++pair) {               // (not unrolled: bounds how many LDS reads are hoisted)
+                load_quarter(bq[1], slab, 2 * pair + 1);         // next quarter in flight
+                quarter(bq[0], 2 * pair);
+                if (pair == 0) load_quarter(bq[0], slab, 2);
+                quarter(bq[1], 2 * pair + 1);
             }
             R* __restrict__ part = bt.mpart + (long long)tile * SP * Dp;
 #pragma unroll

@@ -149,25 +149,15 @@ template <typename R> __device__ __forceinline__ R lone_register(R v) {
     return v;
 }
 
-// (-DVBX_XOR_VIA_BPERMUTE: the round-3 code generation again, for tools/hazard/bpermute_compare.py)
 template <int STAGE, typename T> __device__ __forceinline__ T add_xor(T v) {
-#ifdef VBX_XOR_VIA_BPERMUTE
-    return v + __shfl_xor(v, STAGE, 64);
-#else
     T a, b;
     cross_rows<STAGE>(v, a, b);
     return a + b;
-#endif
 }
 template <int STAGE> __device__ __forceinline__ int max_xor(int v) {
-#ifdef VBX_XOR_VIA_BPERMUTE
-    const int o = __shfl_xor(v, STAGE, 64);
-    return v > o ? v : o;
-#else
     int a, b;
     cross_rows<STAGE>(v, a, b);
     return a > b ? a : b;
-#endif
 }
 
 // value held by one lane, as a wave-uniform scalar (v_readlane_b32 -> SGPR)
@@ -191,21 +181,12 @@ __device__ __forceinline__ int vmax(int a, int b) { return a > b ? a : b; }
 // symmetric pair).
 template <int W, typename R> __device__ __forceinline__ R allreduce_sum(R v) {
     static_assert(W == 16 || W == 32 || W == 64, "group width");
-#ifdef VBX_NO_DPP
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    if (W >= 32) v += __shfl_xor(v, 16, 64);
-    if (W >= 64) v += __shfl_xor(v, 32, 64);
-#else
     v += dpp_mov<0xB1>(v);
     v += dpp_mov<0x4E>(v);
     v += dpp_mov<0x141>(v);
     v += dpp_mov<0x140>(v);
     if (W >= 32) { R a, b; cross_rows<16>(v, a, b); v = a + b; }
     if (W >= 64) { R a, b; cross_rows<32>(v, a, b); v = a + b; }
-#endif
     return v;
 }
 
@@ -227,21 +208,12 @@ template <int W, typename R> __device__ __forceinline__ R allreduce_max(R v) {
 
 template <int W, typename R> __device__ __forceinline__ R allreduce_max_impl(R v) {
     static_assert(W == 16 || W == 32 || W == 64, "group width");
-#ifdef VBX_NO_DPP
-    v = vmax(v, __shfl_xor(v, 1, 64));
-    v = vmax(v, __shfl_xor(v, 2, 64));
-    v = vmax(v, __shfl_xor(v, 4, 64));
-    v = vmax(v, __shfl_xor(v, 8, 64));
-    if (W >= 32) v = vmax(v, __shfl_xor(v, 16, 64));
-    if (W >= 64) v = vmax(v, __shfl_xor(v, 32, 64));
-#else
     v = vmax(v, dpp_mov<0xB1>(v));
     v = vmax(v, dpp_mov<0x4E>(v));
     v = vmax(v, dpp_mov<0x141>(v));
     v = vmax(v, dpp_mov<0x140>(v));
     if (W >= 32) { R a, b; cross_rows<16>(v, a, b); v = vmax(a, b); }
     if (W >= 64) { R a, b; cross_rows<32>(v, a, b); v = vmax(a, b); }
-#endif
     return v;
 }
 

@@ -9,7 +9,6 @@ struct vbx_scores {
     vbx_ctx* ctx = nullptr;
     long long n = 0;
     double* d_s = nullptr;
-    size_t d_s_bytes = 0;
 };
 
 extern "C" {
@@ -17,7 +16,7 @@ extern "C" {
 int vbx_scores_destroy(vbx_scores* sc) {
     if (!sc) return VBX_OK;
     (void)hipSetDevice(sc->ctx->device);
-    scratch_put(sc->ctx, sc->d_s, sc->d_s_bytes);
+    ctx_free(sc->ctx, sc->d_s);
     delete sc;
     return VBX_OK;
 }
@@ -34,10 +33,9 @@ static int cos_similarity_impl(vbx_ctx* ctx, int64_t T, int32_t D, const double*
     vbx_scores* sc = new vbx_scores();
     sc->ctx = ctx;
     sc->n = (long long)T * T;
-    size_t x_bytes = 0, xn_bytes = 0;
-    int rc = on_device ? VBX_OK : scratch_get(ctx, &d_x, (size_t)T * D, &x_bytes);
-    if (rc == VBX_OK) rc = scratch_get(ctx, &d_xn, (size_t)T * Dp, &xn_bytes);
-    if (rc == VBX_OK) rc = scratch_get(ctx, &sc->d_s, (size_t)sc->n, &sc->d_s_bytes);
+    int rc = on_device ? VBX_OK : dmalloc(ctx, &d_x, (size_t)T * D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_xn, (size_t)T * Dp);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &sc->d_s, (size_t)sc->n);
     hipError_t e = hipSuccess;
     if (rc == VBX_OK) {
         if (!on_device) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice, ctx->stream);
@@ -54,8 +52,8 @@ static int cos_similarity_impl(vbx_ctx* ctx, int64_t T, int32_t D, const double*
             rc = VBX_ERR_HIP;
         }
     }
-    if (!on_device) scratch_put(ctx, d_x, x_bytes);
-    scratch_put(ctx, d_xn, xn_bytes);
+    if (!on_device) ctx_free(ctx, d_x);
+    ctx_free(ctx, d_xn);
     if (rc != VBX_OK) {
         vbx_scores_destroy(sc);
         return rc;
@@ -200,7 +198,7 @@ int vbx_scores_upload(vbx_ctx* ctx, int64_t n, const double* s, vbx_scores** out
     vbx_scores* sc = new vbx_scores();
     sc->ctx = ctx;
     sc->n = n;
-    int rc = scratch_get(ctx, &sc->d_s, (size_t)n, &sc->d_s_bytes);
+    int rc = dmalloc(ctx, &sc->d_s, (size_t)n);
     if (rc == VBX_OK) {
         hipError_t e = hipMemcpy(sc->d_s, s, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
@@ -291,12 +289,9 @@ int vbx_scores_linkage_average(vbx_scores* sc, int64_t T, double* Z) {
     //           at T = 1025) and is the reference the rounds are tested against
     // The chain runs in stages of n/4 merges with a compaction of the live rows and columns in between; below kStageMin
     // clusters the rest runs in one stage (there a merge costs its four round trips, not the bytes of a row).
-    static const long long kStageMin = [] { const char* e = experiment_env("VBX_AMD_LINKAGE_STAGE_MIN"); const long long v = e ? atoll(e) : 0; return v >= 64 ? v : 4096LL; }();
-    static const bool staged = [] { const char* e = experiment_env("VBX_AMD_LINKAGE_STAGES"); return !(e && e[0] == '0'); }();
+    constexpr long long kStageMin = 4096, kRoundsFrom = 256, kRoundsStop = 48;
     const char* dev_mode = experiment_env("VBX_AMD_LINKAGE_DEVICE");           // (read per call: tests compare the two in one process)
     const bool rounds_on = !(dev_mode && std::strcmp(dev_mode, "chain") == 0);
-    static const long long kRoundsFrom = [] { const char* e = experiment_env("VBX_AMD_LINKAGE_ROUNDS_FROM"); const long long v = e ? atoll(e) : 0; return v >= 4 ? v : 256LL; }();
-    static const long long kRoundsStop = [] { const char* e = experiment_env("VBX_AMD_LINKAGE_ROUNDS_STOP"); const long long v = e ? atoll(e) : 0; return v >= 2 ? v : 48LL; }();
     int *d_size = nullptr, *d_size2 = nullptr, *d_chain = nullptr, *d_orig = nullptr, *d_orig2 = nullptr, *d_old = nullptr,
         *d_newidx = nullptr, *d_state = nullptr, *d_nn = nullptr, *d_role = nullptr;
     double *d_alt = nullptr, *d_cmp = nullptr, *d_nnd = nullptr;
@@ -376,7 +371,7 @@ int vbx_scores_linkage_average(vbx_scores* sc, int64_t T, double* Z) {
                 }
             }
             if (rc == VBX_OK && e == hipSuccess && done < T - 1) {
-                const bool stages = staged && n_cur >= 2 * kStageMin;
+                const bool stages = n_cur >= 2 * kStageMin;
                 const long long n_alt = stages ? n_cur - n_cur / 4 : 0;
                 if (stages) rc = dmalloc(ctx, &d_alt, (size_t)(n_alt * n_alt));
                 double* alt = d_alt;
@@ -417,13 +412,12 @@ int vbx_scores_get_condensed(vbx_scores* sc, int64_t T, double scale, double* ou
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t m = (size_t)T * (size_t)(T - 1) / 2;
     double* d_c = nullptr;
-    size_t c_bytes = 0;
-    int rc = scratch_get(ctx, &d_c, m, &c_bytes);
+    int rc = dmalloc(ctx, &d_c, m);
     if (rc != VBX_OK) return rc;
     hipLaunchKernelGGL(vbx::condense_kernel, dim3((unsigned)(T - 1)), dim3(256), 0, ctx->stream, sc->d_s, d_c, (long long)T, scale);
     hipError_t e = hipMemcpyAsync(out, d_c, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    scratch_put(ctx, d_c, c_bytes);
+    ctx_free(ctx, d_c);
     if (e != hipSuccess) {
         ctx->err = std::string("vbx_scores_get_condensed: ") + hipGetErrorString(e);
         return VBX_ERR_HIP;
@@ -439,10 +433,9 @@ int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, 
     hipStream_t st = ctx->stream;
     const int nb = (int)std::min<long long>(vbx::kGmmPartials, (sc->n + 255) / 256);
     double *d_par = nullptr, *d_part = nullptr, *d_llr = nullptr;
-    size_t par_bytes = 0, part_bytes = 0, llr_bytes = 0;
-    int rc = scratch_get(ctx, &d_par, 16, &par_bytes);
-    if (rc == VBX_OK) rc = scratch_get(ctx, &d_part, (size_t)nb * 6, &part_bytes);
-    if (rc == VBX_OK && llr) rc = scratch_get(ctx, &d_llr, (size_t)sc->n, &llr_bytes);
+    int rc = dmalloc(ctx, &d_par, 16);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)nb * 6);
+    if (rc == VBX_OK && llr) rc = dmalloc(ctx, &d_llr, (size_t)sc->n);
     double par[16];
     hipError_t e = hipSuccess;
     if (rc == VBX_OK) {
@@ -470,9 +463,9 @@ int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, 
         const double t0 = std::log(w0 * w0 / var) - m0 * m0 / var, t1 = std::log(w1 * w1 / var) - m1 * m1 / var;
         *threshold = -0.5 * (t0 - t1) / (m0 / var - m1 / var);
     }
-    scratch_put(ctx, d_par, par_bytes);
-    scratch_put(ctx, d_part, part_bytes);
-    scratch_put(ctx, d_llr, llr_bytes);
+    ctx_free(ctx, d_par);
+    ctx_free(ctx, d_part);
+    ctx_free(ctx, d_llr);
     return rc;
 }
 

@@ -25,12 +25,6 @@ struct LaunchScope {   // brackets one kernel launch with events when profiling 
     }
 };
 
-// (debugging aid: VBX_AMD_SPLIT_MASK = 1 / 2 keeps the split GEMM to chunk_loglik / chunk_post only)
-static int split_debug_mask() {
-    static const int m = [] { const char* e = experiment_env("VBX_AMD_SPLIT_MASK"); return e ? atoi(e) : 3; }();
-    return m;
-}
-
 #define NT_SWITCH(nt_, BODY)                                   \
     switch (nt_) {                                             \
         case 1: { constexpr int kNT = 1; BODY } break;         \
@@ -106,8 +100,6 @@ template <typename R> void launch_loglik(vbx_batch* b, double eps, bool raw) {
 // the smaller block fetches in a few rounds (one recording of T = 200 000, rounds 2-3: mstep_fin 42 -> 30 us, iter_fin 33 -> 23 us
 // with 1024 threads instead of 256).
 static int small_kernel_threads(const vbx_batch* b, int from_tiles) {
-    static const int forced = [] { const char* e = experiment_env("VBX_AMD_FIN_THREADS"); const int v = e ? atoi(e) : 0; return (v == 256 || v == 512 || v == 1024) ? v : 0; }();
-    if (forced && b->Sp <= 256) return forced;
     int maxtiles = 0;
     for (auto& rd : b->recs) maxtiles = std::max(maxtiles, rd.ntiles);
     // (round 6, one recording, split, us per iteration with 256 / 512 / 1024 threads: T = 12 000 48.7 / 48.0 / 51.3, 20 000 52.9 /
@@ -122,18 +114,11 @@ static int small_kernel_threads(const vbx_batch* b, int from_tiles) {
 // chunk_post over the tiles of the batch; REPLAY: the instance that only writes the responsibilities
 // Does chunk_post walk the last level of the boundary walk itself (FOLD, vbx_chunk_post.hpp)?  Where an iteration is its launches:
 // a grouped walk, the group's operators fit the free LDS region, and the batch does not fill the chip (beyond that the extra
-// mat-vecs per workgroup cost more than the launch they replace).  VBX_AMD_FOLD_WALK=0 / 1 forces it off / on (A/B runs).
-// A batch that does not fill the chip: the small-batch instances of the chunk kernels (FOLD / LAT).  VBX_AMD_FOLD_WALK /
-// VBX_AMD_SMALL_BATCH = 0 / 1 force them off / on (A/B runs, under VBX_AMD_EXPERIMENT=1).
-static bool small_batch_wanted(const vbx_batch* b) {
-    static const int forced = [] { const char* e = experiment_env("VBX_AMD_SMALL_BATCH"); return (e && *e) ? (e[0] == '0' ? 0 : 1) : -1; }();
-    if (forced >= 0) return forced == 1;
-    return b->ntiles_total <= 2048;
-}
+// mat-vecs per workgroup cost more than the launch they replace).
+// A batch that does not fill the chip: the small-batch instances of the chunk kernels (FOLD / LAT).
+static bool small_batch_wanted(const vbx_batch* b) { return b->ntiles_total <= 2048; }
 template <int SP> bool fold_walk_wanted(const vbx_batch* b) {
-    static const int forced = [] { const char* e = experiment_env("VBX_AMD_FOLD_WALK"); return (e && *e) ? (e[0] == '0' ? 0 : 1) : -1; }();
-    if (SP > 32 || b->sgroup <= 1 || b->spt != 1 || b->sgroup - 1 > kTileFrames / SP) return false;
-    if (forced >= 0) return forced == 1;
+    if (SP > 32 || b->sgroup <= 1 || b->sgroup - 1 > kTileFrames / SP) return false;
     return small_batch_wanted(b);
 }
 
@@ -142,7 +127,7 @@ template <typename R, int SP, bool REPLAY> void launch_chunk_post(vbx_batch* b, 
         constexpr bool kCanFold = SP <= 32;                  // (a group has at least four chunks: three operators in r1)
         const bool fold = kCanFold && b->fold_now;
         if constexpr (std::is_same<R, float>::value && !REPLAY) {
-            if (v.rho_b && (split_debug_mask() & 2)) {       // gamma^T rho on the f16 matrix cores (vbx_split.hpp)
+            if (v.rho_b) {                                   // gamma^T rho on the f16 matrix cores (vbx_split.hpp)
                 if constexpr (kCanFold) {
                     if (fold) {
                         hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true, true>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
@@ -174,7 +159,7 @@ template <typename R, int SP> void launch_scan(vbx_batch* b, const BatchView<R>&
             // not fill the chip, feature dimensions that fit the registers
             const bool lat = SP <= 32 && b->Dp <= 128 && small_batch_wanted(b);
             if constexpr (std::is_same<R, float>::value) {
-                if (v.rho_a && (split_debug_mask() & 1)) {   // rho alpha^T on the f16 matrix cores (vbx_split.hpp)
+                if (v.rho_a) {                               // rho alpha^T on the f16 matrix cores (vbx_split.hpp)
                     if constexpr (SP <= 32) {
                         if (lat) {
                             hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
@@ -232,15 +217,10 @@ template <typename R, int SP> void launch_scan_wide(vbx_batch* b, const BatchVie
     hipStream_t st = b->ctx->stream;
     {
         LaunchScope ls(b, VBX_K_FB);
-        bool launched = false;
-        if constexpr (Scan1WideLdsCfg<R, SP>::kFits) {
-            static const bool off = [] { const char* e = experiment_env("VBX_AMD_SCAN1_WIDE_LDS"); return e && e[0] == '0'; }();
-            if (b->d_lppow && !off) {
-                hipLaunchKernelGGL((scan1_wide_lds_kernel<R, SP>), dim3(b->ntiles_total, SP / Scan1WideLdsCfg<R, SP>::COLS), dim3(1024), 0, st, v);
-                launched = true;
-            }
-        }
-        if (!launched) hipLaunchKernelGGL((scan1_wide_kernel<R, SP>), dim3(b->ntiles_total, SP / ScanWideCfg<R, SP>::CB), dim3(256), 0, st, v);
+        if constexpr (Scan1WideLdsCfg<R, SP>::kFits)     // (d_lppow: allocated by choose_fb_algo on this path)
+            hipLaunchKernelGGL((scan1_wide_lds_kernel<R, SP>), dim3(b->ntiles_total, SP / Scan1WideLdsCfg<R, SP>::COLS), dim3(1024), 0, st, v);
+        else
+            hipLaunchKernelGGL((scan1_wide_kernel<R, SP>), dim3(b->ntiles_total, SP / ScanWideCfg<R, SP>::CB), dim3(256), 0, st, v);
     }
     {
         LaunchScope ls(b, VBX_K_FB_AUX);
@@ -428,12 +408,6 @@ template <typename T> int dmalloc(vbx_ctx* ctx, T** p, size_t count) {
 }
 int dmalloc_bytes(vbx_ctx* ctx, void** p, size_t bytes) { return ctx_alloc(ctx, p, bytes); }
 
-template <typename T> int scratch_get(vbx_ctx* ctx, T** p, size_t count, size_t* got_bytes) {
-    *got_bytes = 0;
-    return ctx_alloc(ctx, (void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
-void scratch_put(vbx_ctx* ctx, void* p, size_t) { ctx_free(ctx, p); }
-
 // Decide between the sequential walk and the chunked scan, allocating the scan buffers on first use.
 int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
     int maxtiles = 0;
@@ -456,7 +430,6 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
         if (rc != VBX_OK) return rc;
     }
     b->use_chunked = chunked;
-    const int spt = 1;
     // the forward / backward lattices live in HBM only on the paths that do not keep them in LDS
     const bool fused1 = b->precision == VBX_PREC_FP64 ? fused_available<double>(b) : fused_available<float>(b);
     if (fused1 && chunked && !b->d_oph) {
@@ -479,11 +452,6 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
         if (rc == VBX_OK) rc = dmalloc_bytes(b->ctx, &b->d_bhat, cells * b->rsize);
         if (rc != VBX_OK) return rc;
     }
-    int maxchunks = maxtiles;
-    if (spt == 2) {
-        maxchunks = 0;
-        for (auto& rd : b->recs) maxchunks = std::max(maxchunks, (rd.T + kTileFrames / 2 - 1) / (kTileFrames / 2));
-    }
     // two-level walk over the chunk boundaries once the flat chain gets long
     int group = 1;
     if (chunked && b->Sp <= 64) {            // (the wide scan walks the flat chain)
@@ -494,11 +462,11 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
         // g (compose) + K/g (walk) + g (expand) is shortest near g = sqrt(K/5), not sqrt(K) -- measured on one
         // recording, boundary walk per iteration: T = 200 000 (K = 1563): g = 8/12/16/20/24/32/40 -> 229/191/175/178/
         // 185/216/253 us; T = 50 000 (K = 391): g = 8/12/16/24 -> 35/37/41/51 us.
-        const int g_auto = std::max(4, (int)std::lround(std::sqrt((double)maxchunks / 5.0)));
+        const int g_auto = std::max(4, (int)std::lround(std::sqrt((double)maxtiles / 5.0)));
         if (b->scan_group >= 2) group = b->scan_group;
         // (round 4, 8 / 16 / 24 / 32 / 64 recordings of T = 10 000 on one stream, groups of 4 against the flat chain: walk
         //  25.3 -> 20.5 / 21.6 / 22.5 / 25.4 / 32.5 us, iteration 73.7 -> 69.1, 95.7 -> 90.0, then no gain: up to 16 recordings)
-        else if (b->scan_group == 0 && (maxchunks >= b->two_level_from || (b->n_rec <= 16 && maxchunks >= 32)))
+        else if (b->scan_group == 0 && (maxtiles >= b->two_level_from || (b->n_rec <= 16 && maxtiles >= 32)))
             group = g_auto;
     }
     // The wide scan (64 < Sp <= 256, round 6): a walk step there is 0.95 us (fp32) / 1.6 us (fp64) at Sp = 128 and a product of
@@ -509,14 +477,13 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
     // against 0.127 in groups of 4 -- the two extra launches are paid from about 40 chunks.
     if (chunked && b->Sp > 64 && b->Sp <= 256) {
         if (b->scan_group >= 2) group = b->scan_group;
-        else if (b->scan_group == 0 && maxchunks >= 40) group = std::max(4, (int)std::lround(std::sqrt((double)maxchunks / 3.5)));
+        else if (b->scan_group == 0 && maxtiles >= 40) group = std::max(4, (int)std::lround(std::sqrt((double)maxtiles / 3.5)));
     }
     // Round 6: where chunk_post walks the last level itself (FOLD: groups of at most kTileFrames / Sp + 1 chunks) that level
     // costs no launch, so the automatic group size stops there: one recording of T = 20 000 / 30 000 (g = 6 / 7 before, last
     // level a launch of its own) 57.5 -> 54.9 / 64.0 -> 62.0 us per iteration.
-    static const bool fold_off = [] { const char* e = experiment_env("VBX_AMD_FOLD_WALK"); return e && e[0] == '0'; }();
     const int fold_max = kTileFrames / std::max(b->Sp, 1) + 1;
-    const bool may_fold = group > 1 && fused1 && spt == 1 && b->Sp <= 32 && !fold_off && small_batch_wanted(b) && b->scan_group == 0;
+    const bool may_fold = group > 1 && fused1 && b->Sp <= 32 && small_batch_wanted(b) && b->scan_group == 0;
     if (may_fold) group = std::min(group, fold_max);
     // Third level: with products worth ~4 walk steps the chain 4 (g - 1) + 4 (g2 - 1) + K / (g g2) + g2 + g is shortest
     // near g = g2 = (K / 8)^(1/3) rounded up: K = 1563 (T = 200 000): 7 x 7 -> 94 step equivalents against 173 on two
@@ -525,34 +492,32 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
     int group2 = 1;
     if (group > 1) {
         if (b->scan_group2 >= 2) group2 = b->scan_group2;
-        else if (b->scan_group2 == 0 && b->scan_group == 0 && maxchunks >= b->three_level_from) {
-            group = group2 = std::max(4, (int)std::ceil(std::cbrt((double)maxchunks / 8.0)) + 1);
+        else if (b->scan_group2 == 0 && b->scan_group == 0 && maxtiles >= b->three_level_from) {
+            group = group2 = std::max(4, (int)std::ceil(std::cbrt((double)maxtiles / 8.0)) + 1);
             // (a first level that folds, and the second as long as the chain 4 (g2 - 1) + K / (g g2) + g2 likes it: T = 100 000 /
             //  120 000, (6, 6) -> (5, 6): 102.3 -> 100.7 / 106.6 -> 104.4 us; from 1200 chunks the cube root wins: T = 200 000,
             //  (7, 7) 148.6 against (5, 8) 150.6.  A two-level walk with a folded first level loses from 300 chunks:
             //  T = 50 000 81.8 against 75.5, T = 100 000 125 against 102)
-            if (may_fold && group > fold_max && maxchunks < 1200) {
+            if (may_fold && group > fold_max && maxtiles < 1200) {
                 group = fold_max;
-                group2 = std::max(5, (int)std::lround(std::sqrt((double)maxchunks / (5.0 * group))));
+                group2 = std::max(5, (int)std::lround(std::sqrt((double)maxtiles / (5.0 * group))));
             }
         }
     }
-    if (group != b->sgroup || group2 != b->sgroup2 || spt != b->spt || (group > 1 && !b->d_sop) || (group2 > 1 && !b->d_sop2)) {
+    if (group != b->sgroup || group2 != b->sgroup2 || (group > 1 && !b->d_sop) || (group2 > 1 && !b->d_sop2)) {
         for (void* p : {(void*)b->d_sop, (void*)b->d_sopexp, (void*)b->d_sup_rec, (void*)b->d_sup_idx,
                         (void*)b->d_sop2, (void*)b->d_sopexp2, (void*)b->d_sup2_rec, (void*)b->d_sup2_idx}) ctx_free(b->ctx, p);
         b->d_sop = nullptr; b->d_sopexp = nullptr; b->d_sup_rec = nullptr; b->d_sup_idx = nullptr;
         b->d_sop2 = nullptr; b->d_sopexp2 = nullptr; b->d_sup2_rec = nullptr; b->d_sup2_idx = nullptr;
         b->sgroup = group;
         b->sgroup2 = group2;
-        b->spt = spt;
         b->nsup_total = b->nsup2_total = 0;
         if (group > 1) {
             std::vector<int> sup_rec, sup_idx, sup2_rec, sup2_idx;
             for (int i = 0; i < b->n_rec; ++i) {
                 b->recs[i].sup0 = (int)sup_rec.size();
                 b->recs[i].sup20 = (int)sup2_rec.size();
-                const int kc = spt == 2 ? (b->recs[i].T + kTileFrames / 2 - 1) / (kTileFrames / 2) : b->recs[i].ntiles;
-                const int ns = (kc + group - 1) / group;
+                const int ns = (b->recs[i].ntiles + group - 1) / group;
                 for (int s = 0; s < ns; ++s) {
                     sup_rec.push_back(i);
                     sup_idx.push_back(s);

@@ -185,7 +185,6 @@ struct vbx_batch {
     int scan_group = 0;                           // option: 0 auto, 1 flat, >= 2 chunks per group
     int two_level_from = 160;
     int sgroup = 1, nsup_total = 0;               // in effect
-    int spt = 1;                                  // scan chunks per tile in effect (2: fused kernels, half-tile operators)
     void* d_sop = nullptr;
     int *d_sopexp = nullptr, *d_sup_rec = nullptr, *d_sup_idx = nullptr;
     // third level of the walk (very long recordings): groups of sgroup2 groups
@@ -224,7 +223,7 @@ struct vbx_batch {
         v.op = (R*)d_op; v.opexp = d_opexp; v.fbound = (R*)d_fbound; v.gbound = (R*)d_gbound;
         v.tllpart = use_chunked ? d_tllpart : nullptr; v.sfw = (R*)d_sfw; v.dump = (R*)d_dump;
         v.sop = (R*)d_sop; v.sopexp = d_sopexp; v.sup_rec = d_sup_rec; v.sup_idx = d_sup_idx;
-        v.sgroup = sgroup; v.nsup_total = nsup_total; v.spt = spt;
+        v.sgroup = sgroup; v.nsup_total = nsup_total;
         v.sop2 = (R*)d_sop2; v.sopexp2 = d_sopexp2; v.sup2_rec = d_sup2_rec; v.sup2_idx = d_sup2_idx;
         v.sgroup2 = sgroup2; v.nsup2_total = nsup2_total;
         v.gamma0 = fused_now ? (R*)d_gamma0 : nullptr; v.pi_prev = d_pi_prev;

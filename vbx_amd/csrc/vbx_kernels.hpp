@@ -114,11 +114,6 @@ template <typename R> struct BatchView {
     const int* sup2_rec;   // [nsup2_total] recording of a level-2 group
     const int* sup2_idx;   // [nsup2_total] index of the level-2 group within its recording
     int sgroup2, nsup2_total;
-    // scan chunks per tile: 1 = one transfer operator / boundary pair per tile of kTileFrames frames;
-    // 2 = per half tile (kScanHalf frames), chunk index 2*tile + half -- the fused kernels use it to re-run the
-    // two halves of a tile on separate waves (half the dependent chain).  op / opexp / fbound / gbound always
-    // have room for two chunks per tile.
-    int spt;
     // split GEMMs (vbx_split.hpp; fp32 batches with VBX_OPT_GEMM = split): rho as f16 pairs in MFMA fragment order, the
     // model's alpha likewise (fin_kernel), and their power-of-two scales.  All null when the mode is off.
     const _Float16* rho_a;     // [tiles][kTileFrames x Dp x 2]  A operand of rho alpha^T   (chunk_loglik)
@@ -131,11 +126,6 @@ template <typename R> struct BatchView {
 // the tile a workgroup of a per-chunk kernel works on (-1: none)
 template <typename R> __device__ __forceinline__ int tile_of_block(const BatchView<R>& bt, int block) {
     return bt.tile_order ? bt.tile_order[block] : block;
-}
-
-constexpr int kScanHalf = kTileFrames / 2;
-__device__ __forceinline__ int chunk_count(const RecDesc& rd, int spt) {
-    return spt == 2 ? (rd.T + kScanHalf - 1) / kScanHalf : rd.ntiles;
 }
 
 // =======================================================================================

@@ -187,8 +187,8 @@ __device__ __forceinline__ void scan2_body(const BatchView<R>& bt, int level, R*
     const int rec = level == 3 ? bt.sup_rec[blockIdx.x] : level == 5 ? bt.sup2_rec[blockIdx.x] : blockIdx.x;
     if (bt.state[rec].done) return;
     const RecDesc rd = bt.recs[rec];
-    const int K = chunk_count(rd, bt.spt), G = bt.sgroup;      // chunks of this recording, first one cb0
-    const long long cb0 = (long long)rd.tile0 * bt.spt;
+    const int K = rd.ntiles, G = bt.sgroup;                    // chunks of this recording, first one cb0
+    const long long cb0 = rd.tile0;
     // chain step n uses operator op0 + n*os and writes the boundary b0 + (n+1)*bs; the chain starts from
     // bound[binit] (level 3) or from the initial vector, which it also stores at bound[binit]
     const R* __restrict__ ops = bt.op;
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void scan_compose_kernel(BatchView<R> bt, int 
     if (bt.state[rec].done) return;
     const RecDesc rd = bt.recs[rec];
     const int G = bt.sgroup;
-    const long long cb0 = (long long)rd.tile0 * bt.spt;
+    const long long cb0 = rd.tile0;
     // the operators [a, b) multiplied here, in the array they come from, and where the product goes
     long long a, b;
     const R* __restrict__ in_op = bt.op;
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void scan_compose_kernel(BatchView<R> bt, int 
     R* __restrict__ out_op = bt.sop;
     int* __restrict__ out_exp = bt.sopexp;
     if (level == 2) {
-        const int n1 = (chunk_count(rd, bt.spt) + G - 1) / G;
+        const int n1 = (rd.ntiles + G - 1) / G;
         a = rd.sup0 + (long long)bt.sup2_idx[sup] * bt.sgroup2;
         b = min(a + bt.sgroup2, (long long)rd.sup0 + n1);
         in_op = bt.sop;
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(256) void scan_compose_kernel(BatchView<R> bt, int 
         out_exp = bt.sopexp2;
     } else {
         a = cb0 + (long long)bt.sup_idx[sup] * G;
-        b = min(a + G, cb0 + chunk_count(rd, bt.spt));
+        b = min(a + G, cb0 + rd.ntiles);
     }
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, g = lane >> 4;
     const bool mul = wave < NT;                        // the waves that hold columns of P

@@ -131,13 +131,13 @@ __global__ __launch_bounds__(1024) void scan1_wide_lds_kernel(BatchView<R> bt) {
     }
     __syncthreads();
     const int col = blockIdx.y * Scan1WideLdsCfg<R, SP>::COLS + tid / PH, part = tid % PH;
-    R x[1][NR];
-    int expo[1];
-    operator_columns<R, SP, PH, 1>(btile, 0, len, t0 == 0, col, part, rd.lp, cl, bt.lppow + (long long)rec * (kTileFrames + 1), x, expo);
+    R x[NR];
+    int expo;
+    operator_columns<R, SP, PH>(btile, 0, len, t0 == 0, col, part, rd.lp, cl, bt.lppow + (long long)rec * (kTileFrames + 1), x, expo);
     R* __restrict__ dst = bt.op + ((long long)tile * SP + col) * SP + part * NR;
 #pragma unroll
-    for (int q = 0; q < NR / 4; ++q) *reinterpret_cast<R4*>(dst + 4 * q) = R4{x[0][4 * q], x[0][4 * q + 1], x[0][4 * q + 2], x[0][4 * q + 3]};
-    if (part == 0) bt.opexp[(long long)tile * SP + col] = expo[0];
+    for (int q = 0; q < NR / 4; ++q) *reinterpret_cast<R4*>(dst + 4 * q) = R4{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+    if (part == 0) bt.opexp[(long long)tile * SP + col] = expo;
 }
 
 // Two values (a, b) in every lane -> ONE per lane, summed over the lane pair (l, l ^ STAGE), STAGE = 16 or 32: lanes with

@@ -30,10 +30,7 @@
 namespace vbx {
 
 __device__ __forceinline__ f4 mfma_h(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-// (small terms first; VBX_SPLIT_LOLO=1 adds the lo lo term, 2^-22 of a product at most: A/B builds)
-#ifndef VBX_SPLIT_LOLO
-#define VBX_SPLIT_LOLO 0
-#endif
+// (small terms first; the lo lo term, 2^-22 of a product at most, is left out)
 // rho alpha^T: the B operand (alpha) carries a third term -- alpha multiplies every frame, its representation error is
 // systematic (fin_kernel) -- while the A operand's error is independent from frame to frame and averages out
 __device__ __forceinline__ f4 mfma_split3(h8 ah, h8 al, h8 bh, h8 bl, h8 bl2, f4 c) {
@@ -43,9 +40,6 @@ __device__ __forceinline__ f4 mfma_split3(h8 ah, h8 al, h8 bh, h8 bl, h8 bl2, f4
     return mfma_h(ah, bh, c);
 }
 __device__ __forceinline__ f4 mfma_split(h8 ah, h8 al, h8 bh, h8 bl, f4 c) {
-#if VBX_SPLIT_LOLO
-    c = mfma_h(al, bl, c);
-#endif
     c = mfma_h(ah, bl, c);
     c = mfma_h(al, bh, c);
     return mfma_h(ah, bh, c);
