@@ -378,6 +378,24 @@ int vbx_fbank_windows(vbx_fbank* fb, int32_t n, const int64_t* starts, int32_t l
 int vbx_fbank_times(vbx_fbank* fb, float* ms);
 int vbx_fbank_destroy(vbx_fbank* fb);
 
+/* ---- x-vector network ------------------------------------------------------------------------------------------------
+ * models/resnet.py:ResNet101 (Bottleneck [3, 4, 23, 3], m = 32, 64 input rows) for inference, BatchNorm folded into the
+ * convolutions, on the ctx's stream (the stream of vbx_fbank: windows it gathers into vbx_resnet_input's buffer need no
+ * host round trip).  Convolutions are implicit GEMMs on the f32 matrix instructions (vbx_resnet.hpp); an embedding does
+ * not depend on the batch its window is run in. */
+typedef struct vbx_resnet vbx_resnet;
+/* params: the folded network as f32 (vbx_amd/xvector.py:fold): per convolution in network order its weights
+ * [kh kw Cin][Cout] and bias [Cout], then the embedding [16384][embed_dim] (pooling order) and its bias. */
+int vbx_resnet_create(vbx_ctx* ctx, int32_t embed_dim, const float* params, int64_t n_params, vbx_resnet** out);
+/* a device buffer of n windows [n][64][T] f32 that vbx_fbank_windows may fill; valid until the next vbx_resnet_input. */
+int vbx_resnet_input(vbx_resnet* net, int32_t n, int32_t T, float** d_in);
+/* embeddings [n][embed_dim] f32 of n windows x [n][64][T] (host or device memory).  Workspace grows to the largest
+ * (n, T) seen.  One synchronize, after the copy out. */
+int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_on_device, float* out, int out_on_device);
+/* device milliseconds of the last run: ms[0] stem, [1..4] layer1..layer4, [5] pooling + embedding. */
+int vbx_resnet_times(vbx_resnet* net, float* ms);
+int vbx_resnet_destroy(vbx_resnet* net);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,92 @@
+"""The x-vector network's host side (vbx_amd/xvector.py): the synthetic checkpoint against the fixture recorded from the
+unmodified predict.py + models/resnet.py (tests/golden/make_golden_resnet.py), the checkpoint checks, the BatchNorm fold and
+packing, and the CLI's refusals.  No GPU."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from vbx_amd import xvector
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R = np.load(os.path.join(REPO, 'tests', 'golden', 'resnet_cases.npz'))
+F = np.load(os.path.join(REPO, 'tests', 'golden', 'fbank_cases.npz'))
+SEED, E = int(R['seed']), int(R['embed_dim'])
+
+
+def window(j):
+    """fixture window j as the network input [64][T]"""
+    name = str(F['names'][R['win_rec'][j]])
+    rows = F['rows_' + name]
+    s, a, n = int(R['win_seg'][j]), int(R['win_start'][j]), int(R['win_len'][j])
+    r0 = int(rows[:s].sum())
+    return F['fea_' + name][r0 + a:r0 + a + n].T
+
+
+@pytest.fixture(scope='module')
+def sd():
+    return xvector.synthetic_state_dict(SEED, E)
+
+
+def test_synthetic_state_dict_rebuilds_the_fixture(sd):
+    # the shortest windows: the f64 forward of the rebuilt checkpoint gives the recorded referee embeddings
+    for j in np.argsort(R['win_len'], kind='stable')[:3]:
+        got = xvector.forward_reference(sd, window(j)[None])[0]
+        ref = R['emb_f64'][j]
+        assert np.abs(got - ref).max() <= 1e-12 * np.abs(ref).max()
+        assert np.abs(R['emb_ref'][j] - ref).max() <= 2e-6 * np.abs(ref).max()   # (the reference's own f32 run)
+
+
+def test_layout_and_parameter_count(sd):
+    assert len(xvector.conv_specs()) == 1 + 3 * 33 + 4
+    assert xvector.fold(sd).shape == (xvector.n_params(E),)
+    assert 14.5e6 < xvector.n_params(256) < 15e6
+    perm = xvector.pool_order()
+    assert np.array_equal(np.sort(perm), np.arange(xvector.POOL_DIM))
+    assert perm[1] == 8 and perm[1024] == 1 and perm[8192] == 8192                  # (h 1024 + c) <- c 8 + h
+
+
+def test_checkpoint_checks(sd, tmp_path):
+    import torch
+    extra = dict(sd, **{'bn1.num_batches_tracked': np.array(7), 'something.else': np.zeros(3)})
+    assert set(xvector.check_state_dict(extra)) == set(sd)
+    bad = dict(sd)
+    del bad['layer3.17.bn2.running_var']
+    with pytest.raises(ValueError, match=r'layer3\.17\.bn2\.running_var'):
+        xvector.check_state_dict(bad)
+    bad = dict(sd, **{'layer2.0.shortcut.0.weight': np.zeros((256, 64, 1, 1), np.float32)})
+    with pytest.raises(ValueError, match=r'layer2\.0\.shortcut\.0\.weight has shape \(256, 64, 1, 1\)'):
+        xvector.check_state_dict(bad)
+    with pytest.raises(ValueError, match="module."):
+        xvector.check_state_dict({'module.' + k: v for k, v in sd.items()})
+    with pytest.raises(ValueError, match='embedding.weight'):
+        xvector.check_state_dict(sd, embed_dim=128)
+    path = str(tmp_path / 'ck.pth')
+    torch.save({'state_dict': {k: torch.from_numpy(np.asarray(v)) for k, v in extra.items()}, 'epoch': 3}, path)
+    got = xvector.load_checkpoint(path)
+    assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
+    torch.save({k: torch.from_numpy(v) for k, v in sd.items()}, path)
+    with pytest.raises(ValueError, match='state_dict'):
+        xvector.load_checkpoint(path)
+
+
+def test_fold_and_packing_match_the_unfolded_network(sd):
+    rng = np.random.default_rng(5)
+    x = np.concatenate([window(j)[None] for j in np.flatnonzero(R['win_len'] == 19)[:1]] +
+                       [rng.standard_normal((1, 64, 19))])
+    ref = xvector.forward_reference(sd, x)
+    got = xvector.forward_folded(xvector.fold(sd), E, x)
+    assert np.abs(got - ref).max() <= 1e-10 * np.abs(ref).max()
+
+
+def test_cli_refuses_checkpoint_with_model_file():
+    base = ['--in-file-list', 'l', '--in-lab-dir', 'd', '--in-wav-dir', 'd', '--out-ark-fn', 'a', '--out-seg-fn', 's']
+    for extra, msg in ((['--gpus', '0', '--checkpoint', 'c.pth', '--model-file', 'm'], 'exclude each other'),
+                       (['--gpus', '0', '--model', 'ResNet101', '--weights', 'w', '--checkpoint', 'c.pth'],
+                        '--model/--weights are not supported'),
+                       (['--gpus', '0'], '--checkpoint')):
+        res = subprocess.run([sys.executable, '-m', 'vbx_amd.predict'] + base + extra, cwd=REPO, capture_output=True,
+                             text=True, timeout=120)
+        assert res.returncode != 0 and msg in res.stderr

@@ -1,0 +1,90 @@
+#!/usr/bin/env python
+"""Device time of the x-vector network (vbx_resnet.hpp) on one batch of windows, per stage, against the same folded network
+in f32 through PyTorch on the same GPU (F.conv2d: MIOpen).  Synthetic checkpoint (vbx_amd.xvector.synthetic_state_dict),
+random N(0, 1) windows.
+
+    python tools/bench_xvec.py [--batch 128] [--frames 144] [--reps 10] [--warmup 3] [--no-torch]
+
+Prints a table and one JSON line.  FLOPs are counted from the architecture (xvector.flops, 2 per multiply-add); TF/s is
+that count over the device time of the stage; the f32 matrix peak is 155 TF (MI355X_MICROARCH.md)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch                                     # first: libvbx_hip.so then binds to PyTorch's HIP runtime
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vbx_amd import xvector                      # noqa: E402
+
+PEAK_TF = 155.0
+HOUR_WINDOWS = 15000                             # one hour of speech at the 24-frame jump
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=128)
+    ap.add_argument('--frames', type=int, default=144)
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--no-torch', action='store_true')
+    a = ap.parse_args()
+    B, T = a.batch, a.frames
+    sd = xvector.synthetic_state_dict(a.seed)
+    net = xvector.ResNet101(sd, a.device)
+    x = np.random.default_rng(a.seed).standard_normal((B, 64, T)).astype(np.float32)
+    dev = torch.device('cuda', a.device)
+    xt = torch.from_numpy(x).to(dev)
+    for _ in range(a.warmup):
+        net.embed(xt)
+    stages, wall = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        y = net.embed(xt)                                     # (ends in a device synchronize)
+        wall.append(time.perf_counter() - t0)
+        stages.append(net.times())
+    names = list(stages[0])
+    med = {k: float(np.median([s[k] for s in stages])) for k in names}
+    total = float(np.median([sum(s.values()) for s in stages]))
+    fl = xvector.flops(T)
+    fl['pool_embed'] = 2 * xvector.POOL_DIM * net.embed_dim
+    rows = []
+    print(f'ResNet101, {B} windows of {T} frames, median of {a.reps} runs (device ms from HIP events)')
+    print(f'{"stage":<12}{"ms":>10}{"GFLOP":>10}{"TF/s":>9}{"% peak":>9}')
+    for k in names:
+        g = fl[k] * B / 1e9
+        tf = g / med[k] if med[k] > 0 else float('nan')
+        rows.append({'stage': k, 'ms': med[k], 'gflop': g, 'tflops': tf})
+        print(f'{k:<12}{med[k]:>10.3f}{g:>10.1f}{tf:>9.1f}{100 * tf / PEAK_TF:>8.1f}%')
+    gt = sum(fl.values()) * B / 1e9
+    print(f'{"total":<12}{total:>10.3f}{gt:>10.1f}{gt / total:>9.1f}{100 * gt / total / PEAK_TF:>8.1f}%')
+    print(f'host wall per batch (copy in, run, copy out): {1e3 * float(np.median(wall)):.3f} ms; '
+          f'{HOUR_WINDOWS} windows (one hour): {total * HOUR_WINDOWS / B / 1e3:.3f} s of device time')
+    result = {'batch': B, 'frames': T, 'device_ms': total, 'stages_ms': med, 'tflops': gt / total,
+              'hour_s': total * HOUR_WINDOWS / B / 1e3, 'wall_ms': 1e3 * float(np.median(wall))}
+    if not a.no_torch:
+        tens = xvector.folded_tensors(xvector.fold(sd), net.embed_dim, device=dev, dtype=torch.float32)
+        for _ in range(a.warmup):
+            ref = xvector.run_folded(tens, xt)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        tms = []
+        for _ in range(a.reps):
+            ev[0].record()
+            ref = xvector.run_folded(tens, xt)
+            ev[1].record()
+            torch.cuda.synchronize(dev)
+            tms.append(ev[0].elapsed_time(ev[1]))
+        tm = float(np.median(tms))
+        diff = float((y - ref).abs().max() / ref.abs().max())
+        print(f'PyTorch f32 (F.conv2d, same folded network): {tm:.3f} ms ({gt / tm:.1f} TF/s); '
+              f'HIP / PyTorch time {total / tm:.2f}; max |HIP - PyTorch| / max|e| = {diff:.2e}')
+        result.update(torch_ms=tm, torch_tflops=gt / tm, max_rel_diff_vs_torch=diff)
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     'vbx_batch_gemm_in_effect',
     'vbx_batch_stream_of', 'vbx_batch_sync_uploads', 'vbx_batch_get_results', 'vbx_host_alloc', 'vbx_host_free',
     'vbx_fbank_create', 'vbx_fbank_run', 'vbx_fbank_get', 'vbx_fbank_windows', 'vbx_fbank_times', 'vbx_fbank_destroy',
+    'vbx_resnet_create', 'vbx_resnet_input', 'vbx_resnet_run', 'vbx_resnet_times', 'vbx_resnet_destroy',
 ]
 
 
@@ -125,6 +126,11 @@ def load():
     lib.vbx_fbank_windows.argtypes = [vp, i32, vp, i32, vp, C.c_int]
     lib.vbx_fbank_times.argtypes = [vp, vp]
     lib.vbx_fbank_destroy.argtypes = [vp]
+    lib.vbx_resnet_create.argtypes = [vp, i32, vp, i64, C.POINTER(vp)]
+    lib.vbx_resnet_input.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    lib.vbx_resnet_run.argtypes = [vp, i32, i32, vp, C.c_int, vp, C.c_int]
+    lib.vbx_resnet_times.argtypes = [vp, vp]
+    lib.vbx_resnet_destroy.argtypes = [vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -386,6 +392,62 @@ class FbankDevice:
     def close(self):
         if getattr(self, '_h', None):
             self._lib.vbx_fbank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ResNetDevice:
+    """The x-vector network resident on one device (vbx_resnet): the folded f32 parameters and a workspace that grows to
+    the largest batch seen."""
+
+    TIMES = ('stem', 'layer1', 'layer2', 'layer3', 'layer4', 'pool_embed')
+
+    def __init__(self, ctx: Context, params, embed_dim):
+        self.ctx, self._lib = ctx, ctx._lib
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        h = C.c_void_p()
+        ctx.check(self._lib.vbx_resnet_create(ctx._h, int(embed_dim), _ptr(params), params.size, C.byref(h)),
+                  'vbx_resnet_create')
+        self._h, self.embed_dim = h, int(embed_dim)
+
+    def input_buffer(self, n, T) -> int:
+        """Device address of the network's own input buffer [n][64][T] f32 (vbx_resnet_input)."""
+        p = C.c_void_p()
+        self.ctx.check(self._lib.vbx_resnet_input(self._h, int(n), int(T), C.byref(p)), 'vbx_resnet_input')
+        return p.value
+
+    def run(self, n, T, x=None, x_ptr=None, out_ptr=None):
+        """Embeddings [n][E] f32 of the host array x [n][64][T], or of device memory at x_ptr; into a new host array, or
+        into device memory at out_ptr (returns None then)."""
+        if x_ptr is None:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.shape == (n, 64, T)
+            src, on_dev = _ptr(x), 0
+        else:
+            src, on_dev = C.c_void_p(x_ptr), 1
+        out = None
+        if out_ptr is None:
+            out = np.empty((int(n), self.embed_dim), dtype=np.float32)
+            out_ptr = out.ctypes.data
+        self.ctx.check(self._lib.vbx_resnet_run(self._h, int(n), int(T), src, on_dev, C.c_void_p(out_ptr), int(out is None)),
+                       'vbx_resnet_run')
+        return out
+
+    def times(self):
+        ms = np.zeros(len(self.TIMES), dtype=np.float32)
+        self.ctx.check(self._lib.vbx_resnet_times(self._h, _ptr(ms)), 'vbx_resnet_times')
+        return dict(zip(self.TIMES, ms.astype(float).tolist()))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.vbx_resnet_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -16,6 +16,7 @@
 #include "vbx_ahc.hpp"
 #include "vbx_frontend.hpp"
 #include "vbx_fbank.hpp"
+#include "vbx_resnet.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -39,6 +40,7 @@ using namespace vbx;
 #include "vbx_host_steps.hpp"    // step-level API of the parity tests
 #include "vbx_host_ahc.hpp"      // AHC score stage, x-vector front end, linkage
 #include "vbx_host_fbank.hpp"    // filterbank front end of the x-vector extractor
+#include "vbx_host_resnet.hpp"   // the x-vector network (ResNet101)
 
 #ifdef VBX_PHASE_CLOCKS
 // instrumentation builds only: the per-tile phase stamps of chunk_post_mid_kernel (tile, {wave 0, wave 2}, 8)

@@ -1,0 +1,198 @@
+// vbx_resnet.hpp -- the x-vector network of the recipes (models/resnet.py: ResNet101, Bottleneck blocks [3, 4, 23, 3],
+// m = 32, feat_dim 64) for inference, with every BatchNorm folded into the convolution before it (vbx_amd/xvector.py:
+// fold, in f64 on the host).  Activations are NHWC f32: [B][H][W][C], H = 64 frequency rows, W = the window's frames.
+//
+//   resnet_conv_kernel   implicit-GEMM convolution, M = B Ho Wo output positions x N = Cout, K = kh kw Cin, on
+//                        v_mfma_f32_32x32x2_f32 (an exact k-ordered f32 fma chain per element).  A BM x BN output tile per
+//                        workgroup (BM = 128: four waves of 32 rows x BN; BM = 64, for grids too small to fill the CUs: 2 x 2
+//                        waves of 32 rows x BN / 2); the K loop walks 16 inputs of one tap at a time (Cin is a
+//                        multiple of 16), both operand tiles staged in LDS, the next one prefetched into registers.  Padded
+//                        taps and rows past M read zero.  Epilogue: + folded bias [+ residual] [ReLU].
+//   resnet_stem_kernel   conv 3x3 1 -> 32 (Cin = 1, K = 9) as a direct kernel, + bias, ReLU
+//   resnet_pool_kernel   mean and standard deviation over time of layer4's [B][8][W4][1024] (resnet.py:138-140), in f64
+//
+// The embedding Linear(16384 -> E) is resnet_conv_kernel at H = W = 1.  No atomics and no split of K: every output element
+// is one thread's fixed-order chain, so a window's embedding does not depend on the batch it is run in.  ReLU keeps NaN as
+// F.relu does (a NaN window must reach the embedding: predict.py skips it).
+#pragma once
+#include "vbx_device.hpp"
+
+namespace vbx {
+
+constexpr int RN_MEL = 64;       // input rows (Mel channels)
+constexpr int RN_H4 = 8;         // rows after the three stride-2 stages
+constexpr int RN_C4 = 1024;      // channels out of layer4 (256 planes x 4)
+constexpr int RN_POOL = 2 * RN_H4 * RN_C4;
+constexpr int RN_BK = 16;        // K per LDS stage
+
+using f32x16 = float __attribute__((ext_vector_type(16)));
+
+// relu(v) with NaN kept: (v < 0) is false for NaN.  fmaxf(v, 0) would return 0.
+__device__ __forceinline__ float rn_relu(float v) { return v < 0.0f ? 0.0f : v; }
+
+// y[m][n] = act(sum_k A[m][k] W[k][n] + bias[n] (+ res[m][n])), A[m][(r KS + s) Cin + c] = x[b][ho S - P + r][wo S - P + s][c].
+// w [K][Cout] (row k = tap r KS + s, input channel c), Cout a multiple of BN; grid (ceil(M / BM), Cout / BN).
+template <int KS, int S, int BN, int BM>
+__global__ __launch_bounds__(256) void resnet_conv_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, const float* __restrict__ res,
+                                                          float* __restrict__ y, int H, int W, int Cin, int Ho, int Wo,
+                                                          int Cout, long long M, int relu) {
+    constexpr int P = KS / 2;
+    constexpr int WM = BM / 32, WN = 4 / WM;                   // waves along M and N
+    constexpr int NACC = BN / WN / 32;
+    static_assert(NACC >= 1 && WM * WN == 4, "tile");
+    constexpr int NA = BM / 64;                                // A float4 per thread
+    constexpr int LDA = BM + 4, LDB = BN + 4;
+    constexpr int NB4 = RN_BK * BN / 4;                        // float4 of one B stage
+    constexpr int NBL = (NB4 + 255) / 256;
+    __shared__ float As[RN_BK][LDA];
+    __shared__ float Bs[RN_BK][LDB];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long m0 = (long long)blockIdx.x * BM;
+    const int n0 = blockIdx.y * BN;
+    const int K = KS * KS * Cin;
+    using f4 = Vec<float>::v4;
+
+    // A: BM rows x 16 k, NA float4 per thread: quad kq of rows (tid >> 2) + 64 p
+    const int kq = tid & 3;
+    int hb[NA], wb[NA];
+    long long xb[NA];
+    bool mv[NA];
+#pragma unroll
+    for (int p = 0; p < NA; ++p) {
+        const long long m = m0 + (tid >> 2) + 64 * p;
+        mv[p] = m < M;
+        const long long hw = (long long)Ho * Wo;
+        const long long b = mv[p] ? m / hw : 0;
+        const int rem = mv[p] ? (int)(m - b * hw) : 0, ho = rem / Wo, wo = rem - ho * Wo;
+        hb[p] = ho * S - P;
+        wb[p] = wo * S - P;
+        xb[p] = b * H * W * (long long)Cin;
+    }
+    f4 ra[NA], rb[NBL];
+    auto load = [&](int k0) {
+        const int tap = k0 / Cin, c0 = k0 - tap * Cin, r = tap / KS, s = tap - r * KS;
+#pragma unroll
+        for (int p = 0; p < NA; ++p) {
+            const int hi = hb[p] + r, wi = wb[p] + s;
+            ra[p] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (mv[p] && hi >= 0 && hi < H && wi >= 0 && wi < W)
+                ra[p] = *reinterpret_cast<const f4*>(x + xb[p] + ((long long)hi * W + wi) * Cin + c0 + 4 * kq);
+        }
+#pragma unroll
+        for (int q = 0; q < NBL; ++q) {
+            const int e = tid + 256 * q;
+            if (e < NB4) {
+                const int kk = e / (BN / 4), nq = e - kk * (BN / 4);
+                rb[q] = *reinterpret_cast<const f4*>(w + (long long)(k0 + kk) * Cout + n0 + 4 * nq);
+            }
+        }
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int p = 0; p < NA; ++p)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) As[4 * kq + j][(tid >> 2) + 64 * p] = ra[p][j];
+#pragma unroll
+        for (int q = 0; q < NBL; ++q) {
+            const int e = tid + 256 * q;
+            if (e < NB4) {
+                const int kk = e / (BN / 4), nq = e - kk * (BN / 4);
+                *reinterpret_cast<f4*>(&Bs[kk][4 * nq]) = rb[q];
+            }
+        }
+    };
+
+    f32x16 acc[NACC];
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+    const int i = lane & 31, kh = lane >> 5, row0 = (wave % WM) * 32, col0 = (wave / WM) * (BN / WN);
+    load(0);
+    store();
+    __syncthreads();
+    for (int k0 = 0; k0 < K; k0 += RN_BK) {
+        const bool more = k0 + RN_BK < K;
+        if (more) load(k0 + RN_BK);
+#pragma unroll
+        for (int kk = 0; kk < RN_BK; kk += 2) {
+            const float a = As[kk + kh][row0 + i];
+#pragma unroll
+            for (int j = 0; j < NACC; ++j)
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[kk + kh][col0 + 32 * j + i], acc[j], 0, 0, 0);
+        }
+        __syncthreads();
+        if (more) {
+            store();
+            __syncthreads();
+        }
+    }
+    // D: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int j = 0; j < NACC; ++j) {
+        const int n = n0 + col0 + 32 * j + i;
+        const float bn = bias[n];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long long m = m0 + row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            if (m < M) {
+                const long long o = m * Cout + n;
+                float v = acc[j][r] + bn;
+                if (res) v += res[o];
+                y[o] = relu ? rn_relu(v) : v;
+            }
+        }
+    }
+}
+
+// x [B][64][W] (the front end's window layout, one input channel), w [9][32] (tap r 3 + s), y [B][64][W][32] NHWC
+__global__ __launch_bounds__(256) void resnet_stem_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, float* __restrict__ y, int W,
+                                                          long long total) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx & 31);
+    const long long pos = idx >> 5;
+    const int wo = (int)(pos % W);
+    const long long t = pos / W;
+    const int h = (int)(t % RN_MEL);
+    const float* __restrict__ xb = x + (t / RN_MEL) * RN_MEL * (long long)W;
+    float acc = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int hi = h + r - 1;
+        if (hi < 0 || hi >= RN_MEL) continue;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int wi = wo + s - 1;
+            if (wi >= 0 && wi < W) acc = fmaf(xb[(long long)hi * W + wi], w[(r * 3 + s) * 32 + c], acc);
+        }
+    }
+    y[idx] = rn_relu(acc + bias[c]);
+}
+
+// x [B][8][W4][1024] -> out [B][16384]: [h 1024 + c] = mean over time, [8192 + h 1024 + c] = sqrt(mean(x^2) - mean^2 + 1e-10)
+// (resnet.py:138-140, summed in f64).  The embedding matrix's columns are permuted on the host to this order.
+__global__ __launch_bounds__(256) void resnet_pool_kernel(const float* __restrict__ x, float* __restrict__ out, int W4,
+                                                          long long total) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx & (RN_C4 - 1));
+    const long long bh = idx >> 10;
+    const int h = (int)(bh & (RN_H4 - 1));
+    const long long b = bh >> 3;
+    const float* __restrict__ p = x + bh * W4 * RN_C4 + c;
+    double s = 0.0, s2 = 0.0;
+    for (int t = 0; t < W4; ++t) {
+        const double v = p[(long long)t * RN_C4];
+        s += v;
+        s2 += v * v;
+    }
+    const double mean = s / W4;
+    float* __restrict__ o = out + b * RN_POOL + h * RN_C4 + c;
+    o[0] = (float)mean;
+    o[RN_POOL / 2] = (float)sqrt(s2 / W4 - mean * mean + 1e-10);
+}
+
+}  // namespace vbx

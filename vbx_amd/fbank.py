@@ -9,7 +9,7 @@
                                frame operator, floating-window CMN, windows in the model's [B, 64, T] layout
     features, windows          one-call conveniences over FrontEnd
 
-The network itself is the caller's (vbx_amd.predict runs a TorchScript module on the windows).
+The network after it is vbx_amd.xvector (ResNet101 from a checkpoint, on the same device stream).
 """
 from __future__ import annotations
 

@@ -1,13 +1,14 @@
 """python -m vbx_amd.predict: predict.py's x-vector extraction with the front end on the GPU.
 
 The command line is predict.py's.  The features of a file come from the device front end (vbx_amd.fbank: log-Mel
-filterbank, floating CMN, windows cut straight into the model's [B, 64, 144] layout); the embedding model is a
-TorchScript module (``--model-file``) run by PyTorch on the same device, full windows ``--batch-size`` at a time and the
-tail windows grouped by length.  The ark file and the segments file are the ones predict.py writes, in its order.  The
-dither of the next file is drawn on the host while the device works on the current one.
+filterbank, floating CMN, windows cut straight into the model's [B, 64, 144] layout); the embedding model is either
+ResNet101 from a checkpoint in predict.py's ``--weights`` format (``--checkpoint``, run by vbx_amd.xvector in HIP, the
+windows gathered straight into its input buffer) or a TorchScript module (``--model-file``) run by PyTorch on the same
+device.  Full windows go ``--batch-size`` at a time and the tail windows are grouped by length.  The ark file and the
+segments file are the ones predict.py writes, in its order.  The dither of the next file is drawn on the host while the
+device works on the current one.
 
-Not supported: ``--backend onnx`` and ``--model/--weights`` (the reference's network definition is not part of this
-package; export the model to TorchScript instead).
+Not supported: ``--backend onnx`` and ``--model/--weights`` (pass the ResNet101 weights with ``--checkpoint``).
 """
 from __future__ import annotations
 
@@ -29,8 +30,10 @@ logger = logging.getLogger('vbx_amd.predict')
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--gpus', type=str, default='', help='the device to run on (first index of the list); required')
-    p.add_argument('--model', type=str, default=None, help='not supported: use --model-file')
-    p.add_argument('--weights', type=str, default=None, help='not supported: use --model-file')
+    p.add_argument('--model', type=str, default=None, help='not supported: use --checkpoint or --model-file')
+    p.add_argument('--weights', type=str, default=None, help='not supported: use --checkpoint or --model-file')
+    p.add_argument('--checkpoint', type=str, default=None,
+                   help="ResNet101 weights in predict.py's --weights format (e.g. raw_81.pth), run in HIP")
     p.add_argument('--model-file', type=str, default=None, help='TorchScript embedding model: [B, ndim, T] -> [B, embed]')
     p.add_argument('--ndim', type=int, default=64, help='dimensionality of features')
     p.add_argument('--embed-dim', type=int, default=256, help='dimensionality of the emb')
@@ -47,9 +50,11 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.backend == 'onnx':
         p.error('--backend onnx is not supported: export the model to TorchScript and pass --model-file')
-    if args.model is not None or args.model_file is None:
-        p.error('--model/--weights are not supported (the network definition is not part of this package): '
-                'pass a TorchScript module with --model-file')
+    if args.model is not None or (args.model_file is None and args.checkpoint is None):
+        p.error('--model/--weights are not supported: pass ResNet101 weights with --checkpoint (e.g. --checkpoint '
+                'VBx/models/ResNet101_16kHz/nnet/raw_81.pth) or a TorchScript module with --model-file')
+    if args.model_file is not None and args.checkpoint is not None:
+        p.error('--checkpoint and --model-file exclude each other: pass one embedding model')
     if args.gpus.strip() == '':
         p.error('--gpus is empty: this extractor runs on a GPU only; pass a device index such as --gpus 0')
     if args.ndim != fbank.N_MEL:
@@ -72,8 +77,9 @@ def _load(args, fn):
     return sr, sig, segs
 
 
-def embed_file(model, fe, fn, sig, segs, sr, args, torch):
-    """(key, segments line, embedding) of every window of one file, in predict.py's order."""
+def embed_file(embed, fe, fn, sig, segs, sr, args):
+    """(key, segments line, embedding) of every window of one file, in predict.py's order.  embed(fe, starts, length):
+    the embeddings [n][E] (numpy) of the windows of `length` frames from feature rows `starts`."""
     rows = fe.run([(sig, segs)])[0]
     plan = fbank.window_plan(fn, segs, sr, args.seg_len, args.seg_jump)
     emb = [None] * len(plan)
@@ -84,8 +90,7 @@ def embed_file(model, fe, fn, sig, segs, sr, args, torch):
         step = args.batch_size if length == args.seg_len else len(idx)
         for b0 in range(0, len(idx), step):
             part = idx[b0:b0 + step]
-            x = fe.windows([rows[plan[i].seg] + plan[i].start for i in part], length, out='torch')
-            y = model(x).detach().cpu().numpy()
+            y = embed(fe, [rows[plan[i].seg] + plan[i].start for i in part], length)
             for i, v in zip(part, y):
                 emb[i] = v
     return [(w.key, w.line, e) for w, e in zip(plan, emb)]
@@ -98,9 +103,21 @@ def main(argv=None):
     device = int(args.gpus.split(',')[0])
     if not torch.cuda.is_available() or device >= torch.cuda.device_count():
         raise SystemExit(f'--gpus {args.gpus}: no such GPU visible to PyTorch')
-    tdev = torch.device('cuda', device)
-    model = torch.jit.load(args.model_file, map_location=tdev)
-    model.eval()
+    if args.checkpoint is not None:
+        from . import xvector
+        try:
+            sd = xvector.load_checkpoint(args.checkpoint, embed_dim=args.embed_dim)
+        except (ValueError, OSError) as exc:
+            raise SystemExit(f'--checkpoint {args.checkpoint}: {exc}')
+        net = xvector.ResNet101(sd, device)
+        del sd
+        embed = net.embed_windows
+    else:
+        model = torch.jit.load(args.model_file, map_location=torch.device('cuda', device))
+        model.eval()
+
+        def embed(fe, starts, length):
+            return model(fe.windows(starts, length, out='torch')).detach().cpu().numpy()
     file_names = [str(f) for f in np.atleast_1d(np.loadtxt(args.in_file_list, dtype=object))]
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     nxt = pool.submit(_load, args, file_names[0]) if file_names else None
@@ -110,7 +127,7 @@ def main(argv=None):
             sr, sig, segs = nxt.result()
             nxt = pool.submit(_load, args, file_names[k + 1]) if k + 1 < len(file_names) else None
             fe = fbank.front_end(sr, device)
-            for key, line, vec in embed_file(model, fe, fn, sig, segs, sr, args, torch):
+            for key, line, vec in embed_file(embed, fe, fn, sig, segs, sr, args):
                 if np.isnan(vec).any():
                     logger.warning(f'NaN found, not processing: {key}{os.linesep}')
                     continue

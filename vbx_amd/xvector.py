@@ -1,0 +1,306 @@
+"""The x-vector network of the recipes -- models/resnet.py:ResNet101 with a predict.py checkpoint -- on the GPU.
+
+    load_checkpoint         torch.load(path)['state_dict'] (predict.py's ``--weights`` format), every tensor the network
+                            needs checked by name and shape
+    synthetic_state_dict    a seeded, well-scaled checkpoint (numpy only): tests, golden data, benchmarks
+    fold                    BatchNorm folded into each convolution in f64, packed in the order libvbx_hip.so reads
+    forward_reference       the network in f64 on the CPU from the raw checkpoint (torch.nn.functional): the referee
+    forward_folded          the same from the folded, packed parameters (checks fold; run_folded: on any torch device)
+    ResNet101               the device path (vbx_resnet.hpp): windows [B][64][T] -> embeddings [B][E] f32
+
+The network: conv 3x3 1 -> 32 + BN + ReLU; Bottleneck stages of [3, 4, 23, 3] blocks, planes 32 / 64 / 128 / 256
+(expansion 4), strides 1 / 2 / 2 / 2, a 1x1 conv + BN shortcut in the first block of every stage; mean and standard
+deviation over time of layer4's [B][1024][8][W4]; Linear(16384 -> E).  BN in eval mode, eps 1e-5.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _capi
+
+FEAT_DIM, M_CHANNELS = 64, 32
+BLOCKS, PLANES, STRIDES = (3, 4, 23, 3), (32, 64, 128, 256), (1, 2, 2, 2)
+EXPANSION, BN_EPS = 4, 1e-5
+H4, C4 = FEAT_DIM // 8, PLANES[-1] * EXPANSION        # layer4's rows and channels
+POOL_DIM = 2 * H4 * C4                                # 16384
+BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
+
+
+def conv_specs():
+    """Every convolution in the order the device reads them: (conv key, BN key, kernel size, stride, Cin, Cout)."""
+    out = [('conv1', 'bn1', 3, 1, 1, M_CHANNELS)]
+    cin = M_CHANNELS
+    for L, (n, planes, stride) in enumerate(zip(BLOCKS, PLANES, STRIDES), 1):
+        for i in range(n):
+            p, s = f'layer{L}.{i}.', stride if i == 0 else 1
+            out += [(p + 'conv1', p + 'bn1', 1, 1, cin, planes), (p + 'conv2', p + 'bn2', 3, s, planes, planes),
+                    (p + 'conv3', p + 'bn3', 1, 1, planes, EXPANSION * planes)]
+            if i == 0:                                # stride 2, or 32 != 128 in layer1
+                out.append((p + 'shortcut.0', p + 'shortcut.1', 1, s, cin, EXPANSION * planes))
+            cin = EXPANSION * planes
+    return out
+
+
+def required_shapes(embed_dim: int) -> dict:
+    shapes = {}
+    for conv, bn, k, _, cin, cout in conv_specs():
+        shapes[conv + '.weight'] = (cout, cin, k, k)
+        for key in BN_KEYS:
+            shapes[f'{bn}.{key}'] = (cout,)
+    shapes['embedding.weight'] = (embed_dim, POOL_DIM)
+    shapes['embedding.bias'] = (embed_dim,)
+    return shapes
+
+
+def n_params(embed_dim: int) -> int:
+    """f32 values of the folded network (vbx_resnet_create's n_params)."""
+    return sum(k * k * cin * cout + cout for _, _, k, _, cin, cout in conv_specs()) + POOL_DIM * embed_dim + embed_dim
+
+
+def _numpy(t):
+    if hasattr(t, 'detach'):
+        t = t.detach().cpu().numpy()
+    return np.asarray(t)
+
+
+def check_state_dict(sd, embed_dim: int | None = None) -> dict:
+    """The tensors ResNet101 needs, as numpy arrays, after checking every one by name and shape.  Extra keys (such as
+    ``num_batches_tracked``) are ignored; a missing or misshapen tensor is an error that names it.  (predict.py loads with
+    strict=False and would run a partly random network instead.)"""
+    if not isinstance(sd, dict):
+        raise ValueError(f'a checkpoint state_dict must be a dict, got {type(sd).__name__}')
+    if embed_dim is None:
+        if 'embedding.weight' not in sd:
+            raise ValueError(_missing_message(sd, ['embedding.weight']))
+        embed_dim = int(np.shape(_numpy(sd['embedding.weight']))[0])
+    shapes = required_shapes(int(embed_dim))
+    missing = [k for k in shapes if k not in sd]
+    if missing:
+        raise ValueError(_missing_message(sd, missing))
+    out = {}
+    for k, shape in shapes.items():
+        a = _numpy(sd[k])
+        if tuple(a.shape) != shape:
+            raise ValueError(f'checkpoint tensor {k} has shape {tuple(a.shape)}, ResNet101 (embed_dim {embed_dim}) needs {shape}')
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError(f'checkpoint tensor {k} is {a.dtype}, not floating point')
+        out[k] = a
+    return out
+
+
+def _missing_message(sd, missing):
+    msg = f'checkpoint lacks {len(missing)} tensor(s) ResNet101 needs, first {missing[0]}'
+    if any(str(k).startswith('module.') for k in sd):
+        msg += " (its keys start with 'module.': a DataParallel state_dict; strip the prefix)"
+    return msg
+
+
+def load_checkpoint(path, embed_dim: int | None = None) -> dict:
+    """predict.py's ``--weights`` file: ``torch.load(path)['state_dict']``, checked (check_state_dict)."""
+    import torch
+    ck = torch.load(path, map_location='cpu', weights_only=True)
+    if not isinstance(ck, dict) or 'state_dict' not in ck:
+        raise ValueError(f"{path}: not a checkpoint of predict.py's format (a dict with a 'state_dict')")
+    return check_state_dict(ck['state_dict'], embed_dim)
+
+
+def synthetic_state_dict(seed: int, embed_dim: int = 256) -> dict:
+    """A deterministic f32 checkpoint whose activations stay in range through all 33 blocks: conv weights N(0, 2 / fan_in);
+    BN gamma U(0.2, 0.5) for bn3, U(0.8, 1.2) elsewhere; beta and running mean 0.1 N(0, 1); running variance
+    U(0.5, 1.5); embedding weight N(0, 1 / 16384), bias 0.1 N(0, 1).  numpy's PCG64 only, drawn in conv_specs() order."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for conv, bn, k, _, cin, cout in conv_specs():
+        sd[conv + '.weight'] = rng.normal(0.0, np.sqrt(2.0 / (cin * k * k)), (cout, cin, k, k))
+        lo, hi = (0.2, 0.5) if bn.endswith('bn3') else (0.8, 1.2)
+        sd[bn + '.weight'] = rng.uniform(lo, hi, cout)
+        sd[bn + '.bias'] = 0.1 * rng.standard_normal(cout)
+        sd[bn + '.running_mean'] = 0.1 * rng.standard_normal(cout)
+        sd[bn + '.running_var'] = rng.uniform(0.5, 1.5, cout)
+    sd['embedding.weight'] = rng.normal(0.0, np.sqrt(1.0 / POOL_DIM), (embed_dim, POOL_DIM))
+    sd['embedding.bias'] = 0.1 * rng.standard_normal(embed_dim)
+    return {k: v.astype(np.float32) for k, v in sd.items()}
+
+
+def pool_order() -> np.ndarray:
+    """perm[p] = the reference's pooled index (mean: c 8 + h, std: 8192 + c 8 + h) of the device's pooled index p
+    (mean: h 1024 + c, std: 8192 + h 1024 + c)."""
+    p = np.arange(H4 * C4)
+    ref = (p % C4) * H4 + p // C4
+    return np.concatenate([ref, H4 * C4 + ref])
+
+
+def fold(sd) -> np.ndarray:
+    """The folded network, f64, in the device's order (include/vbx_hip.h: vbx_resnet_create): per convolution
+    W[o] gamma[o] / sqrt(var[o] + eps) laid out [(r kw + s) Cin + c][o], then bias beta - mean gamma / sqrt(var + eps);
+    then the embedding [16384][E] with its rows in pooling order, and its bias."""
+    sd = check_state_dict(sd)
+    parts = []
+    for conv, bn, k, _, cin, cout in conv_specs():
+        w = sd[conv + '.weight'].astype(np.float64)
+        g, b, m, v = (sd[f'{bn}.{key}'].astype(np.float64) for key in BN_KEYS)
+        scale = g / np.sqrt(v + BN_EPS)
+        parts.append((w * scale[:, None, None, None]).transpose(2, 3, 1, 0).reshape(-1))
+        parts.append(b - m * scale)
+    parts.append(sd['embedding.weight'].astype(np.float64)[:, pool_order()].T.reshape(-1))
+    parts.append(sd['embedding.bias'].astype(np.float64))
+    return np.concatenate(parts)
+
+
+def _pool_embed(out, ew, eb, torch):
+    mean = out.mean(dim=-1)
+    std = torch.sqrt((out * out).mean(dim=-1) - mean ** 2 + 1e-10)
+    return torch.cat([mean.flatten(1), std.flatten(1)], 1) @ ew.T + eb
+
+
+def forward_reference(sd, x) -> np.ndarray:
+    """ResNet.forward (models/resnet.py:130-145) with BN in eval mode, in f64 on the CPU: x [B][64][T] -> [B][E]."""
+    import torch
+    import torch.nn.functional as F
+    sd = check_state_dict(sd)
+    t = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)) for k, v in sd.items()}
+
+    def cbn(h, conv, bn, stride, pad):
+        h = F.conv2d(h, t[conv + '.weight'], stride=stride, padding=pad)
+        return F.batch_norm(h, t[bn + '.running_mean'], t[bn + '.running_var'], t[bn + '.weight'], t[bn + '.bias'],
+                            training=False, eps=BN_EPS)
+
+    with torch.no_grad():
+        h = torch.from_numpy(np.asarray(x, dtype=np.float64))[:, None]
+        h = F.relu(cbn(h, 'conv1', 'bn1', 1, 1))
+        for L, (n, stride) in enumerate(zip(BLOCKS, STRIDES), 1):
+            for i in range(n):
+                p, s = f'layer{L}.{i}.', stride if i == 0 else 1
+                o = F.relu(cbn(h, p + 'conv1', p + 'bn1', 1, 0))
+                o = F.relu(cbn(o, p + 'conv2', p + 'bn2', s, 1))
+                o = cbn(o, p + 'conv3', p + 'bn3', 1, 0)
+                h = F.relu(o + (cbn(h, p + 'shortcut.0', p + 'shortcut.1', s, 0) if i == 0 else h))
+        return _pool_embed(h, t['embedding.weight'], t['embedding.bias'], torch).numpy()
+
+
+def folded_tensors(params, embed_dim: int, device='cpu', dtype=None) -> list:
+    """fold()'s packed parameters as torch tensors in conv2d's layout: [(weight [Cout][Cin][k][k], bias)] in
+    conv_specs() order, then (embedding [16384][E], bias)."""
+    import torch
+    dtype = dtype or torch.float64
+    params = torch.from_numpy(np.asarray(params, dtype=np.float64))
+    assert params.numel() == n_params(embed_dim)
+    out, off = [], 0
+    for _, _, k, _, cin, cout in conv_specs():
+        w = params[off:off + k * k * cin * cout].reshape(k, k, cin, cout).permute(3, 2, 0, 1)
+        off += k * k * cin * cout
+        out.append((w, params[off:off + cout]))
+        off += cout
+    out.append((params[off:off + POOL_DIM * embed_dim].reshape(POOL_DIM, embed_dim), params[off + POOL_DIM * embed_dim:]))
+    return [(w.to(device=device, dtype=dtype).contiguous(), b.to(device=device, dtype=dtype)) for w, b in out]
+
+
+def run_folded(tensors, x):
+    """The network on folded_tensors(): x [B][64][T] tensor of their device and dtype -> [B][E]."""
+    import torch
+    import torch.nn.functional as F
+    it = iter(tensors)
+
+    def conv(h, stride, relu, res=None):
+        w, b = next(it)
+        h = F.conv2d(h, w, b, stride=stride, padding=w.shape[-1] // 2)
+        if res is not None:
+            h = h + res
+        return F.relu(h) if relu else h
+
+    with torch.no_grad():
+        h = conv(x[:, None], 1, True)
+        for n, stride in zip(BLOCKS, STRIDES):
+            for i in range(n):
+                s = stride if i == 0 else 1
+                o = conv(conv(h, 1, True), s, True)
+                c3 = next(it)
+                sc = conv(h, s, False) if i == 0 else h
+                h = F.relu(F.conv2d(o, c3[0], c3[1]) + sc)
+        mean = h.mean(dim=-1)                                              # [B][1024][8]
+        std = torch.sqrt((h * h).mean(dim=-1) - mean ** 2 + 1e-10)
+        pooled = torch.cat([mean.transpose(1, 2).flatten(1), std.transpose(1, 2).flatten(1)], 1)   # (h 1024 + c)
+        ew, eb = next(it)
+        return pooled @ ew + eb
+
+
+def forward_folded(params, embed_dim: int, x) -> np.ndarray:
+    """The network from fold()'s packed parameters, in f64 on the CPU (what the device computes, in f64)."""
+    import torch
+    return run_folded(folded_tensors(params, embed_dim), torch.from_numpy(np.asarray(x, dtype=np.float64))).numpy()
+
+
+class ResNet101:
+    """The network on one device.  ``embed(x)``: x [B][64][T] f32 (numpy, or a torch tensor on the device) -> [B][E] f32
+    of the same kind.  Runs on the device context's stream, the front end's (vbx_amd.fbank), so that ``embed_windows``
+    goes from features to embeddings without a host round trip or a torch allocation."""
+
+    def __init__(self, sd, device: int = 0):
+        sd = check_state_dict(sd)
+        self.embed_dim = int(sd['embedding.weight'].shape[0])
+        self.device = int(device)
+        if _capi._lib is None:
+            try:                                      # (PyTorch's HIP runtime first: see fbank.FrontEnd)
+                import torch  # noqa: F401
+            except ImportError:
+                pass
+        self.ctx = _capi.default_context(self.device)
+        self.dev = _capi.ResNetDevice(self.ctx, fold(sd).astype(np.float32), self.embed_dim)
+
+    @classmethod
+    def from_checkpoint(cls, src, device: int = 0, embed_dim: int | None = None) -> 'ResNet101':
+        """src: a checkpoint path (predict.py's ``--weights``) or a state_dict."""
+        sd = load_checkpoint(src, embed_dim) if isinstance(src, (str, bytes)) or hasattr(src, '__fspath__') else \
+            check_state_dict(src, embed_dim)
+        return cls(sd, device)
+
+    def embed(self, x):
+        if hasattr(x, 'data_ptr'):
+            import torch
+            if x.dim() != 3 or x.shape[1] != FEAT_DIM or x.dtype != torch.float32 or not x.is_cuda:
+                raise ValueError(f'embed: expected a float32 [B][{FEAT_DIM}][T] tensor on the GPU')
+            x = x.contiguous()
+            B, _, T = x.shape
+            out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=x.device)
+            torch.cuda.current_stream(x.device).synchronize()      # x written, out's block free, on torch's stream
+            if B:
+                self.dev.run(B, T, x_ptr=x.data_ptr(), out_ptr=out.data_ptr())
+            return out
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 3 or x.shape[1] != FEAT_DIM:
+            raise ValueError(f'embed: expected [B][{FEAT_DIM}][T], got {x.shape}')
+        if x.shape[0] == 0:
+            return np.empty((0, self.embed_dim), dtype=np.float32)
+        return self.dev.run(x.shape[0], x.shape[2], x)
+
+    def embed_windows(self, fe, starts, length: int) -> np.ndarray:
+        """Embeddings of the windows ``fe.windows(starts, length)`` of a front end on the same device: gathered straight
+        into the network's input buffer."""
+        starts = np.asarray(starts, dtype=np.int64)
+        ptr = self.dev.input_buffer(len(starts), length)
+        fe.dev.windows(starts, length, dst_ptr=ptr)
+        return self.dev.run(len(starts), length, x_ptr=ptr)
+
+    def times(self) -> dict:
+        """Device ms of the last run: stem, layer1 .. layer4, pool_embed."""
+        return self.dev.times()
+
+
+def flops(T: int) -> dict:
+    """Multiply-add FLOPs (2 per MAC) of one window of T frames, per stage."""
+    out, H, W = {'stem': 2 * 9 * M_CHANNELS * FEAT_DIM * T}, FEAT_DIM, T
+    specs = conv_specs()[1:]
+    k = 0
+    for L, (n, stride) in enumerate(zip(BLOCKS, STRIDES), 1):
+        f = 0
+        for i in range(n):
+            c1, c2, c3 = specs[k:k + 3]
+            s = c2[3]
+            Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+            f += 2 * H * W * c1[4] * c1[5] + 2 * Ho * Wo * 9 * c2[4] * c2[5] + 2 * Ho * Wo * c3[4] * c3[5]
+            if i == 0:
+                f += 2 * Ho * Wo * specs[k + 3][4] * specs[k + 3][5]
+            k += 4 if i == 0 else 3
+            H, W = Ho, Wo
+        out[f'layer{L}'] = f
+    return out
