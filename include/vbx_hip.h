@@ -396,6 +396,32 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
 int vbx_resnet_times(vbx_resnet* net, float* ms);
 int vbx_resnet_destroy(vbx_resnet* net);
 
+/* ---- step-level entry points of the network (used by the kernel tests) ----------------------------------------------
+ * One kernel of vbx_resnet.hpp per call, on the ctx's stream.  Every array is a host pointer to f32; the call allocates
+ * device buffers, copies in, launches, copies out, synchronizes and frees: for tests, not for speed.
+ * Outputs are IN/OUT with a guard band: the array holds pad + (payload) + pad floats, all of it is uploaded, the kernel is
+ * given the address of element pad, and all of it comes back.  A caller that fills it with a sentinel beforehand sees
+ * stores outside the payload and payload elements the kernel never wrote.
+ *
+ * The BN x BM output tile the network's dispatcher uses for a convolution of M = n Ho Wo output positions and Cout
+ * channels (Cout a multiple of 32).  Host code: needs no device. */
+int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm);
+/* One convolution as the network launches it: ks x ks (1 or 3, padding ks / 2), stride 1 or 2, then + bias, + res (NULL:
+ * none), ReLU if relu != 0 (NaN kept).  Ho = (H - 1) / stride + 1, Wo likewise, M = n Ho Wo.
+ *   x [n][H][W][Cin], w [ks ks Cin][Cout] (row (r ks + s) Cin + c), bias [Cout], res [M][Cout]  ->  y [pad + M Cout + pad]
+ * bn = bm = 0: the dispatcher's tile; otherwise one of BN x BM = 128 x 64, 128 x 128, 64 x 64, 64 x 128, 32 x 128 is forced.
+ * VBX_ERR_INVALID, with nothing launched: ks or stride not built, Cin not a multiple of 16, Cout not a multiple of the
+ * tile's BN (of 32 when the tile is not forced), a tile that is not one of the five, a size <= 0, x / w / bias / y NULL. */
+int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                    const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn, int32_t bm,
+                    float* y, int64_t pad);
+/* The stem: conv 3 x 3 of one input channel to 32, + bias, ReLU.  x [n][64][T], w [9][32] (row r 3 + s), bias [32]
+ * ->  y [pad + n 64 T 32 + pad], the payload [n][64][T][32]. */
+int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const float* w, const float* bias, float* y, int64_t pad);
+/* Statistics pooling: x [n][8][W4][1024]  ->  out [pad + n 16384 + pad], the payload [n][16384]: [h 1024 + c] the mean
+ * over the W4 frames, [8192 + h 1024 + c] sqrt(mean(x^2) - mean^2 + 1e-10), summed in f64. */
+int vbx_resnet_pool(vbx_ctx* ctx, int32_t n, int32_t W4, const float* x, float* out, int64_t pad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ import sys
 import numpy as np
 import pytest
 
+import resnet_shapes as rs
 from vbx_amd import fbank, xvector
 from vbx_amd import kaldi_formats as kf
 
@@ -85,6 +86,26 @@ def test_nan_stays_in_its_window(net, full):
     assert np.isnan(got[2]).all()
     assert np.isfinite(got[[0, 1, 3]]).all()
     assert np.array_equal(got[[0, 1, 3]], net.embed(full[[0, 1, 3]]))
+
+
+@pytest.mark.parametrize('n,T', rs.NETWORK_RUNS)
+def test_production_shapes(net, full, n, T):
+    """Batches as predict forms them (the last, short batch of a file; tail windows grouped by length): together with the
+    other runs of this file they reach every convolution instantiation and edge path the network can (resnet_shapes,
+    tests/test_xvector_host.py).  Every window is bit-equal to its own run alone and within 1e-5 max|e| of the f64 referee."""
+    rng = np.random.default_rng(1000 * n + T)
+    x = full[rng.integers(0, len(full), n)][:, :, :T] + 0.1 * rng.standard_normal((n, 64, T))
+    x = x.astype(np.float32)
+    got = net.embed(x)
+    assert got.shape == (n, E) and got.dtype == np.float32 and np.isfinite(got).all()
+    sd = xvector.synthetic_state_dict(SEED, E)
+    for i in range(n):
+        assert np.array_equal(got[i], net.embed(x[i:i + 1])[0]), i
+    for i0 in range(0, n, 8):
+        ref = xvector.forward_reference(sd, x[i0:i0 + 8])
+        for i, e in enumerate(ref, i0):
+            err, scale = np.abs(got[i] - e).max(), np.abs(e).max()
+            assert err <= 1e-5 * scale, (i, err / scale)
 
 
 DEVICE_INPUTS = '''

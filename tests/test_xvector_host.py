@@ -81,6 +81,45 @@ def test_fold_and_packing_match_the_unfolded_network(sd):
     assert np.abs(got - ref).max() <= 1e-10 * np.abs(ref).max()
 
 
+def test_network_runs_reach_every_reachable_convolution_class():
+    """The (n, T) the GPU tests run the network at reach every class (ks, stride, BN, BM, last M-tile partial) of
+    resnet_conv_kernel that predict can ask for: n <= 128 and 192 / 256 / 384 / 512 windows of 10 ... 144 frames.  The tile
+    is the library's own choice (vbx_resnet_conv_tile), so a change of the dispatcher's thresholds fails here until
+    resnet_shapes.NETWORK_RUNS is extended."""
+    import resnet_shapes as rs
+    convs = {T: [(ks, s, cout, rs.rn_out(h, s) * rs.rn_out(w, s)) for ks, s, _, cout, h, w in rs.network_convs(T)]
+             for T in range(10, 145)}
+
+    def classes(n, T):
+        out = set()
+        for ks, s, cout, hw in convs[T]:
+            bn, bm = rs.conv_tile(n * hw, cout)
+            out.add((ks, s, bn, bm, n * hw % bm != 0))
+        return out
+
+    assert classes(3, 26) == rs.conv_classes(3, 26)
+    domain = set()
+    for T in convs:
+        for n in list(range(1, 129)) + [192, 256, 384, 512]:
+            domain |= classes(n, T)
+    tested = set()
+    for n, T in rs.NETWORK_RUNS + rs.OTHER_RUNS + rs.fixture_runs(R['win_rec'], R['win_len']):
+        tested |= classes(n, T)
+    assert tested == domain, sorted(domain ^ tested)
+    assert all((bn, bm) in rs.TILES for _, _, bn, bm, _ in domain)
+
+
+def test_forced_tile_table_holds_every_instantiation():
+    import resnet_shapes as rs
+    cases = rs.FORCED_CASES
+    assert {c[:4] for c in cases} == {ks_s + t for ks_s in rs.KS_STRIDE for t in rs.TILES} and len({c[:4] for c in cases}) == 20
+    for ks, s in rs.KS_STRIDE:
+        for bn, bm in rs.TILES:
+            ms = [n * rs.rn_out(h, s) * rs.rn_out(w, s) for k, st, b1, b2, n, h, w in cases if (k, st, b1, b2) == (ks, s, bn, bm)]
+            assert {m % bm for m in ms} >= {0, 1, 31, 32, 33, 63, bm - 1}, (ks, s, bn, bm)
+            assert any(m < bm for m in ms)
+
+
 def test_cli_refuses_checkpoint_with_model_file():
     base = ['--in-file-list', 'l', '--in-lab-dir', 'd', '--in-wav-dir', 'd', '--out-ark-fn', 'a', '--out-seg-fn', 's']
     for extra, msg in ((['--gpus', '0', '--checkpoint', 'c.pth', '--model-file', 'm'], 'exclude each other'),

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     'vbx_batch_stream_of', 'vbx_batch_sync_uploads', 'vbx_batch_get_results', 'vbx_host_alloc', 'vbx_host_free',
     'vbx_fbank_create', 'vbx_fbank_run', 'vbx_fbank_get', 'vbx_fbank_windows', 'vbx_fbank_times', 'vbx_fbank_destroy',
     'vbx_resnet_create', 'vbx_resnet_input', 'vbx_resnet_run', 'vbx_resnet_times', 'vbx_resnet_destroy',
+    'vbx_resnet_conv_tile', 'vbx_resnet_conv', 'vbx_resnet_stem', 'vbx_resnet_pool',
 ]
 
 
@@ -131,6 +132,10 @@ def load():
     lib.vbx_resnet_run.argtypes = [vp, i32, i32, vp, C.c_int, vp, C.c_int]
     lib.vbx_resnet_times.argtypes = [vp, vp]
     lib.vbx_resnet_destroy.argtypes = [vp]
+    lib.vbx_resnet_conv_tile.argtypes = [i64, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.vbx_resnet_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_int, i32, i32, vp, i64]
+    lib.vbx_resnet_stem.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64]
+    lib.vbx_resnet_pool.argtypes = [vp, i32, i32, vp, vp, i64]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -457,6 +462,79 @@ class ResNetDevice:
             self.close()
         except Exception:
             pass
+
+
+# ---- step-level entry points of the network (kernel tests) ------------------------------------
+RN_SENTINEL = 0x7FC5A5A5     # a NaN no kernel produces, compared as uint32: a kernel may legitimately write NaN
+RN_PAD = 4096                # floats of guard band either side of an output
+
+
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _guarded(count, pad):
+    return np.full(int(count) + 2 * int(pad), RN_SENTINEL, dtype=np.uint32).view(np.float32)
+
+
+def _unguard(buf, count, pad):
+    """-> (payload, guard-band words that changed, payload words still holding the sentinel)"""
+    bits = buf.view(np.uint32)
+    guard = int(np.count_nonzero(bits[:pad] != RN_SENTINEL) + np.count_nonzero(bits[pad + count:] != RN_SENTINEL))
+    unwritten = int(np.count_nonzero(bits[pad:pad + count] == RN_SENTINEL))
+    return buf[pad:pad + count].copy(), guard, unwritten
+
+
+def resnet_conv_tile(M, Cout):
+    """(BN, BM) the network's dispatcher picks for M output positions x Cout channels (host code, no device)."""
+    bn, bm = C.c_int32(), C.c_int32()
+    rc = load().vbx_resnet_conv_tile(int(M), int(Cout), C.byref(bn), C.byref(bm))
+    if rc != 0:
+        raise VbxError(f'vbx_resnet_conv_tile(M={M}, Cout={Cout}) failed ({rc})')
+    return bn.value, bm.value
+
+
+def resnet_conv(ctx: 'Context', x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
+    """One convolution of the network (vbx_resnet_conv): x [n][H][W][Cin], w [ks ks Cin][Cout], bias [Cout], res
+    [n][Ho][Wo][Cout] or None; tile None (the dispatcher's) or (BN, BM).  -> (y [n][Ho][Wo][Cout], guard-band words the
+    kernel changed, output words it left unwritten)."""
+    x, w, bias, res = _f32(x), _f32(w), _f32(bias), _f32(res)
+    n, H, W, Cin = x.shape
+    Cout = w.shape[1]
+    s = max(int(stride), 1)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    count = n * Ho * Wo * Cout
+    assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (res is None or res.size == count)
+    bn, bm = tile or (0, 0)
+    buf = _guarded(count, pad)
+    ctx.check(ctx._lib.vbx_resnet_conv(ctx._h, int(ks), int(stride), n, H, W, Cin, Cout, _ptr(x), _ptr(w), _ptr(bias), _ptr(res),
+                                       int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad)), 'vbx_resnet_conv')
+    y, guard, unwritten = _unguard(buf, count, pad)
+    return y.reshape(n, Ho, Wo, Cout), guard, unwritten
+
+
+def resnet_stem(ctx: 'Context', x, w, bias, pad=RN_PAD):
+    """The stem (vbx_resnet_stem): x [n][64][T], w [9][32], bias [32] -> (y [n][64][T][32], guard, unwritten)."""
+    x, w, bias = _f32(x), _f32(w), _f32(bias)
+    n, mel, T = x.shape
+    assert mel == 64 and w.shape == (9, 32) and bias.shape == (32,)
+    count = n * 64 * T * 32
+    buf = _guarded(count, pad)
+    ctx.check(ctx._lib.vbx_resnet_stem(ctx._h, n, T, _ptr(x), _ptr(w), _ptr(bias), _ptr(buf), int(pad)), 'vbx_resnet_stem')
+    y, guard, unwritten = _unguard(buf, count, pad)
+    return y.reshape(n, 64, T, 32), guard, unwritten
+
+
+def resnet_pool(ctx: 'Context', x, pad=RN_PAD):
+    """Statistics pooling (vbx_resnet_pool): x [n][8][W4][1024] -> (out [n][16384], guard, unwritten)."""
+    x = _f32(x)
+    n, h, W4, c = x.shape
+    assert h == 8 and c == 1024
+    count = n * 16384
+    buf = _guarded(count, pad)
+    ctx.check(ctx._lib.vbx_resnet_pool(ctx._h, n, W4, _ptr(x), _ptr(buf), int(pad)), 'vbx_resnet_pool')
+    out, guard, unwritten = _unguard(buf, count, pad)
+    return out.reshape(n, 16384), guard, unwritten
 
 
 class Scores:

@@ -62,20 +62,64 @@ static void rn_launch_ks(hipStream_t st, int BN, int BM, const float* x, const f
         hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 32, 128>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
 }
 
-// one convolution of n images H x W x Cin -> Ho x Wo x Cout (Cout a multiple of 32, Cin of 16)
-static void rn_conv(hipStream_t st, int ks, int stride, const float* x, const float* w, const float* b, const float* res, float* y,
-                    int n, int H, int W, int Cin, int Cout, int relu) {
-    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
-    const long long M = (long long)n * Ho * Wo;
+// the BN x BM output tile of a convolution of M output positions x Cout channels (Cout a multiple of 32)
+static void rn_tile(long long M, int Cout, int* bn, int* bm) {
     // (a few rows -- the embedding -- take narrow tiles: more workgroups over its long K)
-    const int BN = M < 4096 ? 32 : Cout % 128 == 0 ? 128 : Cout % 64 == 0 ? 64 : 32;
+    *bn = M < 4096 ? 32 : Cout % 128 == 0 ? 128 : Cout % 64 == 0 ? 64 : 32;
     // 64-row tiles where 128-row ones leave fewer than four workgroups per CU (layer3 and layer4 at 128 windows)
-    const int BM = BN >= 64 && (M + 127) / 128 * (Cout / BN) < 1024 ? 64 : 128;
+    *bm = *bn >= 64 && (M + 127) / 128 * (Cout / *bn) < 1024 ? 64 : 128;
+}
+
+static void rn_launch(hipStream_t st, int ks, int stride, int BN, int BM, const float* x, const float* w, const float* b,
+                      const float* res, float* y, int H, int W, int Cin, int Ho, int Wo, int Cout, long long M, int relu) {
     if (ks == 1 && stride == 1) rn_launch_ks<1, 1>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
     else if (ks == 1) rn_launch_ks<1, 2>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
     else if (stride == 1) rn_launch_ks<3, 1>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
     else rn_launch_ks<3, 2>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
 }
+
+// one convolution of n images H x W x Cin -> Ho x Wo x Cout (Cout a multiple of 32, Cin of 16)
+static void rn_conv(hipStream_t st, int ks, int stride, const float* x, const float* w, const float* b, const float* res, float* y,
+                    int n, int H, int W, int Cin, int Cout, int relu) {
+    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
+    const long long M = (long long)n * Ho * Wo;
+    int BN, BM;
+    rn_tile(M, Cout, &BN, &BM);
+    rn_launch(st, ks, stride, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
+}
+
+// ---- step-level entry points: one kernel of the network on host arrays (the kernel tests) ----
+
+// device copies of host f32 arrays for one step-level call; everything goes back to the ctx's blocks when it ends
+struct RnStep {
+    vbx_ctx* ctx;
+    std::vector<float*> blocks;
+    explicit RnStep(vbx_ctx* c) : ctx(c) {}
+    ~RnStep() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (float* p : blocks) ctx_free(ctx, p);
+    }
+    int up(const float* host, size_t count, float** dev) {
+        *dev = nullptr;
+        if (!host) return VBX_OK;
+        const int rc = dmalloc(ctx, dev, count);
+        if (rc != VBX_OK) return rc;
+        blocks.push_back(*dev);
+        HIPCHK(ctx, hipMemcpyAsync(*dev, host, sizeof(float) * count, hipMemcpyHostToDevice, ctx->stream));
+        return VBX_OK;
+    }
+    // the kernel has been launched: wait for it and bring the whole in/out buffer back
+    int down(const char* what, float* host, const float* dev, size_t count) {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, sizeof(float) * count, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            ctx->err = std::string(what) + " failed: " + hipGetErrorString(e);
+            return VBX_ERR_HIP;
+        }
+        return VBX_OK;
+    }
+};
 
 extern "C" {
 
@@ -233,6 +277,85 @@ int vbx_resnet_times(vbx_resnet* net, float* ms) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     for (int i = 0; i < 6; ++i) HIPCHK(ctx, hipEventElapsedTime(&ms[i], net->ev[i], net->ev[i + 1]));
     return VBX_OK;
+}
+
+int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm) {
+    if (!bn || !bm || M <= 0 || Cout <= 0 || Cout % 32 != 0) return VBX_ERR_INVALID;
+    int BN, BM;
+    rn_tile(M, Cout, &BN, &BM);
+    *bn = BN;
+    *bm = BM;
+    return VBX_OK;
+}
+
+int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                    const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn, int32_t bm,
+                    float* y, int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!x || !w || !bias || !y) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: x, w, bias and y must not be NULL");
+    if (n <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || pad < 0)
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: n = %d, H = %d, W = %d, Cin = %d, Cout = %d must be positive, pad = %lld not negative",
+             n, H, W, Cin, Cout, (long long)pad);
+    if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2))
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: kernel size %d stride %d: built for 1 or 3 at stride 1 or 2", ks, stride);
+    if (Cin % RN_BK != 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: Cin = %d is not a multiple of %d", Cin, RN_BK);
+    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
+    const long long M = (long long)n * Ho * Wo;
+    int BN = bn, BM = bm;
+    if (bn == 0 && bm == 0) {
+        if (Cout % 32 != 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: Cout = %d is not a multiple of 32", Cout);
+        rn_tile(M, Cout, &BN, &BM);
+    } else {
+        const bool built = (bn == 128 && bm == 64) || (bn == 128 && bm == 128) || (bn == 64 && bm == 64) || (bn == 64 && bm == 128) ||
+                           (bn == 32 && bm == 128);
+        if (!built) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: no %d x %d tile (BN x BM: 128 x 64, 128 x 128, 64 x 64, 64 x 128, 32 x 128)", bn, bm);
+        if (Cout % bn != 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: Cout = %d is not a multiple of the tile's BN = %d", Cout, bn);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnStep s(ctx);
+    const size_t ny = (size_t)M * Cout + 2 * (size_t)pad;
+    float *dx, *dw, *db, *dr, *dy;
+    int rc = s.up(x, (size_t)n * H * W * Cin, &dx);
+    if (rc == VBX_OK) rc = s.up(w, (size_t)ks * ks * Cin * Cout, &dw);
+    if (rc == VBX_OK) rc = s.up(bias, (size_t)Cout, &db);
+    if (rc == VBX_OK) rc = s.up(res, (size_t)M * Cout, &dr);
+    if (rc == VBX_OK) rc = s.up(y, ny, &dy);
+    if (rc != VBX_OK) return rc;
+    rn_launch(ctx->stream, ks, stride, BN, BM, dx, dw, db, dr, dy + pad, H, W, Cin, Ho, Wo, Cout, M, relu ? 1 : 0);
+    return s.down("vbx_resnet_conv", y, dy, ny);
+}
+
+int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const float* w, const float* bias, float* y, int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!x || !w || !bias || !y || n <= 0 || T <= 0 || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_stem: bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnStep s(ctx);
+    const long long total = (long long)n * RN_MEL * T * 32;
+    const size_t ny = (size_t)total + 2 * (size_t)pad;
+    float *dx, *dw, *db, *dy;
+    int rc = s.up(x, (size_t)n * RN_MEL * T, &dx);
+    if (rc == VBX_OK) rc = s.up(w, 9 * 32, &dw);
+    if (rc == VBX_OK) rc = s.up(bias, 32, &db);
+    if (rc == VBX_OK) rc = s.up(y, ny, &dy);
+    if (rc != VBX_OK) return rc;
+    hipLaunchKernelGGL(resnet_stem_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dw, db, dy + pad, T,
+                       total);
+    return s.down("vbx_resnet_stem", y, dy, ny);
+}
+
+int vbx_resnet_pool(vbx_ctx* ctx, int32_t n, int32_t W4, const float* x, float* out, int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!x || !out || n <= 0 || W4 <= 0 || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_pool: bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnStep s(ctx);
+    const long long total = (long long)n * RN_H4 * RN_C4;
+    const size_t ny = (size_t)n * RN_POOL + 2 * (size_t)pad;
+    float *dx, *dy;
+    int rc = s.up(x, (size_t)total * W4, &dx);
+    if (rc == VBX_OK) rc = s.up(out, ny, &dy);
+    if (rc != VBX_OK) return rc;
+    hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dy + pad, W4, total);
+    return s.down("vbx_resnet_pool", out, dy, ny);
 }
 
 }  // extern "C"
