@@ -381,8 +381,9 @@ int vbx_fbank_destroy(vbx_fbank* fb);
 /* ---- x-vector network ------------------------------------------------------------------------------------------------
  * models/resnet.py:ResNet101 (Bottleneck [3, 4, 23, 3], m = 32, 64 input rows) for inference, BatchNorm folded into the
  * convolutions, on the ctx's stream (the stream of vbx_fbank: windows it gathers into vbx_resnet_input's buffer need no
- * host round trip).  Convolutions are implicit GEMMs on the f32 matrix instructions (vbx_resnet.hpp); an embedding does
- * not depend on the batch its window is run in. */
+ * host round trip).  Convolutions are implicit GEMMs on the f32 matrix instructions (vbx_resnet.hpp) or, opt-in, on the
+ * f16 matrix instructions with error-compensated operands (vbx_resnet_set_gemm); an embedding does not depend on the batch
+ * its window is run in. */
 typedef struct vbx_resnet vbx_resnet;
 /* params: the folded network as f32 (vbx_amd/xvector.py:fold): per convolution in network order its weights
  * [kh kw Cin][Cout] and bias [Cout], then the embedding [16384][embed_dim] (pooling order) and its bias. */
@@ -395,6 +396,14 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
 /* device milliseconds of the last run: ms[0] stem, [1..4] layer1..layer4, [5] pooling + embedding. */
 int vbx_resnet_times(vbx_resnet* net, float* ms);
 int vbx_resnet_destroy(vbx_resnet* net);
+/* How the convolutions of layer1 .. layer4 multiply in the runs that follow: VBX_GEMM_EXACT (default: the f32 matrix
+ * instructions, bits as before) or VBX_GEMM_SPLIT (vbx_resnet_split.hpp: v_mfma_f32_32x32x16_f16 on error-compensated f16
+ * operand pairs, weights split per output channel at create time, activations per window as they are staged; f32-level
+ * accuracy, not the exact mode's bits).  The stem, the pooling and the embedding stay exact in both.  An embedding does not
+ * depend on the batch in either mode.  A library built without the ISA audit refuses VBX_GEMM_SPLIT: VBX_ERR_UNSUPPORTED. */
+int vbx_resnet_set_gemm(vbx_resnet* net, int gemm);
+/* VBX_GEMM_EXACT or VBX_GEMM_SPLIT: how the last vbx_resnet_run multiplied (VBX_GEMM_EXACT before the first). */
+int vbx_resnet_gemm_in_effect(vbx_resnet* net);
 
 /* ---- step-level entry points of the network (used by the kernel tests) ----------------------------------------------
  * One kernel of vbx_resnet.hpp per call, on the ctx's stream.  Every array is a host pointer to f32; the call allocates
@@ -415,6 +424,17 @@ int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm);
 int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                     const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn, int32_t bm,
                     float* y, int64_t pad);
+/* vbx_resnet_conv in either mode.  gemm = VBX_GEMM_SPLIT: the weights are split as vbx_resnet_create splits them, max |x| of
+ * every image is measured on the device, and the split kernel of the (dispatcher's or forced) tile runs; the same guard
+ * band contract and the same refusals.  amax_y (NULL: not wanted) [n] receives what the kernel records for its consumer:
+ * max |y| over the finite outputs of every image (split mode only). */
+int vbx_resnet_conv_gemm(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin,
+                         int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn,
+                         int32_t bm, float* y, int64_t pad, float* amax_y);
+/* The split mode's weights (host code, needs no device): w [K][Cout] f32, K a multiple of 16, Cout of 32  ->  e [Cout], the
+ * exponent of every output channel's power-of-two scale, and frag [K / 16][Cout / 32][hi | lo][64 lanes][8] f16 bits, the
+ * fragment order of the B operand of v_mfma_f32_32x32x16_f16: lane l holds B[k = 8 (l >> 5) + j][column l & 31]. */
+int vbx_resnet_split_weights(int32_t K, int32_t Cout, const float* w, uint16_t* frag, int32_t* e);
 /* The stem: conv 3 x 3 of one input channel to 32, + bias, ReLU.  x [n][64][T], w [9][32] (row r 3 + s), bias [32]
  * ->  y [pad + n 64 T 32 + pad], the payload [n][64][T][32]. */
 int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const float* w, const float* bias, float* y, int64_t pad);

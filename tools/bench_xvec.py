@@ -3,10 +3,13 @@
 in f32 through PyTorch on the same GPU (F.conv2d: MIOpen).  Synthetic checkpoint (vbx_amd.xvector.synthetic_state_dict),
 random N(0, 1) windows.
 
-    python tools/bench_xvec.py [--batch 128] [--frames 144] [--reps 10] [--warmup 3] [--no-torch]
+    python tools/bench_xvec.py [--batch 128] [--frames 144] [--reps 10] [--warmup 3] [--no-torch] [--gemm exact|split|both]
+
+--gemm both measures the two modes of the network in one process on the same inputs and prints both tables.
 
 Prints a table and one JSON line.  FLOPs are counted from the architecture (xvector.flops, 2 per multiply-add); TF/s is
-that count over the device time of the stage; the f32 matrix peak is 155 TF (MI355X_MICROARCH.md)."""
+that count over the device time of the stage (once per multiply-add in the split mode too, not once per f16 matrix
+instruction); the f32 matrix peak is 155 TF (MI355X_MICROARCH.md)."""
 import argparse
 import json
 import os
@@ -23,6 +26,40 @@ PEAK_TF = 155.0
 HOUR_WINDOWS = 15000                             # one hour of speech at the 24-frame jump
 
 
+def measure(net, xt, a, gemm):
+    """One mode's table; -> (its result dict, the embeddings of the last run)."""
+    B, T = a.batch, a.frames
+    for _ in range(a.warmup):
+        net.embed(xt)
+    stages, wall = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        y = net.embed(xt)                                     # (ends in a device synchronize)
+        wall.append(time.perf_counter() - t0)
+        stages.append(net.times())
+    assert net.gemm_in_effect() == gemm
+    names = list(stages[0])
+    med = {k: float(np.median([s[k] for s in stages])) for k in names}
+    totals = [sum(s.values()) for s in stages]
+    total = float(np.median(totals))
+    fl = xvector.flops(T)
+    fl['pool_embed'] = 2 * xvector.POOL_DIM * net.embed_dim
+    print(f'ResNet101 ({gemm}), {B} windows of {T} frames, median of {a.reps} runs (device ms from HIP events)')
+    print(f'{"stage":<12}{"ms":>10}{"GFLOP":>10}{"TF/s":>9}{"% peak":>9}')
+    for k in names:
+        g = fl[k] * B / 1e9
+        tf = g / med[k] if med[k] > 0 else float('nan')
+        print(f'{k:<12}{med[k]:>10.3f}{g:>10.1f}{tf:>9.1f}{100 * tf / PEAK_TF:>8.1f}%')
+    gt = sum(fl.values()) * B / 1e9
+    print(f'{"total":<12}{total:>10.3f}{gt:>10.1f}{gt / total:>9.1f}{100 * gt / total / PEAK_TF:>8.1f}%')
+    print(f'total over the {a.reps} runs: min {min(totals):.3f}, max {max(totals):.3f} ms')
+    print(f'host wall per batch (copy in, run, copy out): {1e3 * float(np.median(wall)):.3f} ms; '
+          f'{HOUR_WINDOWS} windows (one hour): {total * HOUR_WINDOWS / B / 1e3:.3f} s of device time')
+    return {'gemm': gemm, 'batch': B, 'frames': T, 'device_ms': total, 'device_ms_min': float(min(totals)),
+            'device_ms_max': float(max(totals)), 'stages_ms': med, 'tflops': gt / total, 'gflop': gt,
+            'hour_s': total * HOUR_WINDOWS / B / 1e3, 'wall_ms': 1e3 * float(np.median(wall))}, y
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=128)
@@ -32,42 +69,34 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--no-torch', action='store_true')
+    ap.add_argument('--gemm', default='exact', choices=['exact', 'split', 'both'])
     a = ap.parse_args()
     B, T = a.batch, a.frames
     sd = xvector.synthetic_state_dict(a.seed)
-    net = xvector.ResNet101(sd, a.device)
     x = np.random.default_rng(a.seed).standard_normal((B, 64, T)).astype(np.float32)
     dev = torch.device('cuda', a.device)
     xt = torch.from_numpy(x).to(dev)
-    for _ in range(a.warmup):
-        net.embed(xt)
-    stages, wall = [], []
-    for _ in range(a.reps):
-        t0 = time.perf_counter()
-        y = net.embed(xt)                                     # (ends in a device synchronize)
-        wall.append(time.perf_counter() - t0)
-        stages.append(net.times())
-    names = list(stages[0])
-    med = {k: float(np.median([s[k] for s in stages])) for k in names}
-    total = float(np.median([sum(s.values()) for s in stages]))
-    fl = xvector.flops(T)
-    fl['pool_embed'] = 2 * xvector.POOL_DIM * net.embed_dim
-    rows = []
-    print(f'ResNet101, {B} windows of {T} frames, median of {a.reps} runs (device ms from HIP events)')
-    print(f'{"stage":<12}{"ms":>10}{"GFLOP":>10}{"TF/s":>9}{"% peak":>9}')
-    for k in names:
-        g = fl[k] * B / 1e9
-        tf = g / med[k] if med[k] > 0 else float('nan')
-        rows.append({'stage': k, 'ms': med[k], 'gflop': g, 'tflops': tf})
-        print(f'{k:<12}{med[k]:>10.3f}{g:>10.1f}{tf:>9.1f}{100 * tf / PEAK_TF:>8.1f}%')
-    gt = sum(fl.values()) * B / 1e9
-    print(f'{"total":<12}{total:>10.3f}{gt:>10.1f}{gt / total:>9.1f}{100 * gt / total / PEAK_TF:>8.1f}%')
-    print(f'host wall per batch (copy in, run, copy out): {1e3 * float(np.median(wall)):.3f} ms; '
-          f'{HOUR_WINDOWS} windows (one hour): {total * HOUR_WINDOWS / B / 1e3:.3f} s of device time')
-    result = {'batch': B, 'frames': T, 'device_ms': total, 'stages_ms': med, 'tflops': gt / total,
-              'hour_s': total * HOUR_WINDOWS / B / 1e3, 'wall_ms': 1e3 * float(np.median(wall))}
+    modes = ['exact', 'split'] if a.gemm == 'both' else [a.gemm]
+    results, ys = [], []
+    for gemm in modes:
+        net = xvector.ResNet101(sd, a.device, gemm=gemm)
+        r, y = measure(net, xt, a, gemm)
+        results.append(r)
+        ys.append(y)
+        del net
+    if len(results) == 2:
+        ex, sp = results
+        diff = float((ys[1] - ys[0]).abs().max() / ys[0].abs().max())
+        print(f'split / exact device time {sp["device_ms"] / ex["device_ms"]:.3f} ({ex["device_ms"]:.3f} -> {sp["device_ms"]:.3f} ms; '
+              f'the exact mode\'s own runs span {ex["device_ms_min"]:.3f} .. {ex["device_ms_max"]:.3f} ms); '
+              f'max |split - exact| / max|e| = {diff:.2e}')
+    result = dict(results[0])
+    if len(results) == 2:
+        result['split'] = results[1]
+        result['max_rel_diff_split_vs_exact'] = diff
+    y, total, gt, embed_dim = ys[0], results[0]['device_ms'], results[0]['gflop'], int(ys[0].shape[1])
     if not a.no_torch:
-        tens = xvector.folded_tensors(xvector.fold(sd), net.embed_dim, device=dev, dtype=torch.float32)
+        tens = xvector.folded_tensors(xvector.fold(sd), embed_dim, device=dev, dtype=torch.float32)
         for _ in range(a.warmup):
             ref = xvector.run_folded(tens, xt)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -81,7 +110,7 @@ def main():
         tm = float(np.median(tms))
         diff = float((y - ref).abs().max() / ref.abs().max())
         print(f'PyTorch f32 (F.conv2d, same folded network): {tm:.3f} ms ({gt / tm:.1f} TF/s); '
-              f'HIP / PyTorch time {total / tm:.2f}; max |HIP - PyTorch| / max|e| = {diff:.2e}')
+              f'HIP ({modes[0]}) / PyTorch time {total / tm:.2f}; max |HIP - PyTorch| / max|e| = {diff:.2e}')
         result.update(torch_ms=tm, torch_tflops=gt / tm, max_rel_diff_vs_torch=diff)
     print(json.dumps(result))
 

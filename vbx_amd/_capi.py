@@ -17,6 +17,7 @@ OPT_FB_ALGO, OPT_CHECK_EVERY, OPT_PROFILE, OPT_CHUNK_FRAMES, OPT_FUSE, OPT_SCAN_
 OPT_TWO_LEVEL_FROM, OPT_STREAMS, OPT_SPLIT_TILES, OPT_SCAN_GROUP2, OPT_THREE_LEVEL_FROM = 8, 10, 11, 12, 13
 OPT_GEMM = 14                # how the fp32 path multiplies: GEMM_EXACT (f32 MFMA) | GEMM_SPLIT (f16 operand pairs, vbx_split.hpp)
 GEMM_EXACT, GEMM_SPLIT = 0, 1
+GEMM_NAMES = {'exact': GEMM_EXACT, 'split': GEMM_SPLIT}
 OPT_ASYNC_UPLOAD = 15        # setters only enqueue; one synchronize when the next run begins (Batch.set_async_upload)
 K_NAMES = ['prep', 'mstep_acc', 'mstep_fin', 'loglik', 'fb', 'fb_aux', 'post', 'iter_fin', 'chunk_loglik',
            'chunk_post']
@@ -38,6 +39,7 @@ ABI_SYMBOLS = [
     'vbx_fbank_create', 'vbx_fbank_run', 'vbx_fbank_get', 'vbx_fbank_windows', 'vbx_fbank_times', 'vbx_fbank_destroy',
     'vbx_resnet_create', 'vbx_resnet_input', 'vbx_resnet_run', 'vbx_resnet_times', 'vbx_resnet_destroy',
     'vbx_resnet_conv_tile', 'vbx_resnet_conv', 'vbx_resnet_stem', 'vbx_resnet_pool',
+    'vbx_resnet_set_gemm', 'vbx_resnet_gemm_in_effect', 'vbx_resnet_conv_gemm', 'vbx_resnet_split_weights',
 ]
 
 
@@ -136,6 +138,10 @@ def load():
     lib.vbx_resnet_conv.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_int, i32, i32, vp, i64]
     lib.vbx_resnet_stem.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64]
     lib.vbx_resnet_pool.argtypes = [vp, i32, i32, vp, vp, i64]
+    lib.vbx_resnet_set_gemm.argtypes = [vp, C.c_int]
+    lib.vbx_resnet_gemm_in_effect.argtypes = [vp]
+    lib.vbx_resnet_conv_gemm.argtypes = [vp, C.c_int, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_int, i32, i32, vp, i64, vp]
+    lib.vbx_resnet_split_weights.argtypes = [i32, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -414,13 +420,25 @@ class ResNetDevice:
 
     TIMES = ('stem', 'layer1', 'layer2', 'layer3', 'layer4', 'pool_embed')
 
-    def __init__(self, ctx: Context, params, embed_dim):
+    def __init__(self, ctx: Context, params, embed_dim, gemm='exact'):
         self.ctx, self._lib = ctx, ctx._lib
+        if gemm not in GEMM_NAMES:
+            raise ValueError(f"gemm must be 'exact' or 'split', got {gemm!r}")
         params = np.ascontiguousarray(params, dtype=np.float32)
         h = C.c_void_p()
         ctx.check(self._lib.vbx_resnet_create(ctx._h, int(embed_dim), _ptr(params), params.size, C.byref(h)),
                   'vbx_resnet_create')
         self._h, self.embed_dim = h, int(embed_dim)
+        if gemm != 'exact':
+            self.set_gemm(gemm)
+
+    def set_gemm(self, gemm):
+        """'exact' or 'split' for the runs that follow (vbx_resnet_set_gemm)."""
+        self.ctx.check(self._lib.vbx_resnet_set_gemm(self._h, GEMM_NAMES[gemm]), 'vbx_resnet_set_gemm')
+
+    def gemm_in_effect(self) -> str:
+        """How the last run multiplied: 'exact' or 'split'."""
+        return 'split' if int(self._lib.vbx_resnet_gemm_in_effect(self._h)) == GEMM_SPLIT else 'exact'
 
     def input_buffer(self, n, T) -> int:
         """Device address of the network's own input buffer [n][64][T] f32 (vbx_resnet_input)."""
@@ -511,6 +529,39 @@ def resnet_conv(ctx: 'Context', x, w, bias, ks, stride, res=None, relu=False, ti
                                        int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad)), 'vbx_resnet_conv')
     y, guard, unwritten = _unguard(buf, count, pad)
     return y.reshape(n, Ho, Wo, Cout), guard, unwritten
+
+
+def resnet_conv_gemm(ctx: 'Context', gemm, x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
+    """resnet_conv in either mode (vbx_resnet_conv_gemm; gemm 'exact' or 'split').  -> (y, guard, unwritten, amax_y [n]: max |y|
+    over the finite outputs of every image as the split kernel records it for its consumer; zeros in the exact mode)."""
+    x, w, bias, res = _f32(x), _f32(w), _f32(bias), _f32(res)
+    n, H, W, Cin = x.shape
+    Cout = w.shape[1]
+    s = max(int(stride), 1)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    count = n * Ho * Wo * Cout
+    assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (res is None or res.size == count)
+    bn, bm = tile or (0, 0)
+    buf = _guarded(count, pad)
+    amax = np.zeros(max(n, 1), dtype=np.float32)
+    ctx.check(ctx._lib.vbx_resnet_conv_gemm(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), n, H, W, Cin, Cout, _ptr(x), _ptr(w),
+                                            _ptr(bias), _ptr(res), int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad),
+                                            _ptr(amax)), 'vbx_resnet_conv_gemm')
+    y, guard, unwritten = _unguard(buf, count, pad)
+    return y.reshape(n, Ho, Wo, Cout), guard, unwritten, amax[:n]
+
+
+def resnet_split_weights(w):
+    """The library's own split of a weight matrix w [K][Cout] (vbx_resnet_split_weights, host code): -> (frag uint16
+    [K / 16][Cout / 32][2][64][8], e int32 [Cout])."""
+    w = _f32(w)
+    K, Cout = w.shape
+    frag = np.zeros((max(K // 16, 1), max(Cout // 32, 1), 2, 64, 8), dtype=np.uint16)
+    e = np.zeros(Cout, dtype=np.int32)
+    rc = load().vbx_resnet_split_weights(K, Cout, _ptr(w), _ptr(frag), _ptr(e))
+    if rc != 0:
+        raise VbxError(f'vbx_resnet_split_weights(K={K}, Cout={Cout}) failed ({rc})')
+    return frag, e
 
 
 def resnet_stem(ctx: 'Context', x, w, bias, pad=RN_PAD):

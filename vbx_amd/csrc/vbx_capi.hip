@@ -17,6 +17,7 @@
 #include "vbx_frontend.hpp"
 #include "vbx_fbank.hpp"
 #include "vbx_resnet.hpp"
+#include "vbx_resnet_split.hpp"
 
 #include <algorithm>
 #include <chrono>

@@ -8,6 +8,7 @@
 struct RnConv {
     int ks, stride, cin, cout;
     size_t w, b;                                               // offsets into the parameter blob
+    size_t wf = 0, we = 0;                                     // split mode: offsets (h8 units, ints) of the fragments and exponents
 };
 
 struct vbx_resnet {
@@ -18,7 +19,16 @@ struct vbx_resnet {
     float *d_in = nullptr, *d_x[2] = {}, *d_t1 = nullptr, *d_t2 = nullptr, *d_sc = nullptr, *d_pool = nullptr, *d_out = nullptr;
     size_t cap_in = 0, cap_x[2] = {}, cap_t1 = 0, cap_t2 = 0, cap_sc = 0, cap_pool = 0, cap_out = 0;
     hipEvent_t ev[7] = {};                                     // stem | layer1 | layer2 | layer3 | layer4 | pool + embedding
+    // split mode (vbx_resnet_split.hpp): the weights a second time as f16 pairs in fragment order, their per-channel
+    // exponents, and one max |y| slot per window for every tensor a split convolution reads
+    int gemm = VBX_GEMM_EXACT, gemm_last = VBX_GEMM_EXACT;
+    vbx::h8* d_wf = nullptr;
+    int* d_we = nullptr;
+    unsigned* d_amax = nullptr;
+    size_t cap_amax = 0;
 };
+
+constexpr int RN_AMAX_SLOTS = 1 + 3 * (3 + 4 + 23 + 3);        // the stem's output, then conv1, conv2 and the output of every block
 
 static const int RN_BLOCKS[4] = {3, 4, 23, 3}, RN_PLANES[4] = {32, 64, 128, 256}, RN_STRIDE[4] = {1, 2, 2, 2};
 
@@ -60,6 +70,68 @@ static void rn_launch_ks(hipStream_t st, int BN, int BM, const float* x, const f
         hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 64, 128>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
     else
         hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 32, 128>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
+}
+
+template <int KS, int S>
+static void rn_launch_split_ks(hipStream_t st, int BN, int BM, const float* x, const unsigned* ax, const vbx::h8* wf, const int* we,
+                               const float* b, const float* res, float* y, unsigned* ay, int H, int W, int Cin, int Ho, int Wo,
+                               int Cout, long long M, int relu) {
+    const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(Cout / BN)), blk(256);
+    if (BN == 128 && BM == 64)
+        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 128, 64>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else if (BN == 128)
+        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 128, 128>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else if (BN == 64 && BM == 64)
+        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 64, 64>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else if (BN == 64)
+        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 64, 128>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else
+        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 32, 128>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+}
+
+// the split mode's launch of one tile (the same five BN x BM as the exact kernel)
+static void rn_launch_split(hipStream_t st, int ks, int stride, int BN, int BM, const float* x, const unsigned* ax, const vbx::h8* wf,
+                            const int* we, const float* b, const float* res, float* y, unsigned* ay, int H, int W, int Cin, int Ho,
+                            int Wo, int Cout, long long M, int relu) {
+    if (ks == 1 && stride == 1) rn_launch_split_ks<1, 1>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else if (ks == 1) rn_launch_split_ks<1, 2>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else if (stride == 1) rn_launch_split_ks<3, 1>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+    else rn_launch_split_ks<3, 2>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+}
+
+// max |x| per window of n windows of per_window floats (a multiple of 4) into amax[n], zeroed beforehand
+static void rn_amax(hipStream_t st, const float* x, int n, long long per_window, unsigned* amax) {
+    const int bpw = (int)std::min<long long>(64, (per_window / 4 + 255) / 256);
+    hipLaunchKernelGGL(resnet_amax_kernel, dim3((unsigned)n * bpw), dim3(256), 0, st, x, per_window, bpw, amax);
+}
+
+// w [K][Cout] f32 (K a multiple of 16, Cout of 32) -> frag [K / 16][Cout / 32][hi | lo][64][8] f16 bits, e [Cout]: the B
+// operand of vbx_resnet_split.hpp, one power-of-two scale per output channel (vbx_amd/xvector.py: pack_split_weights is the
+// same in numpy)
+static void rn_split_weights(const float* w, int K, int Cout, uint16_t* frag, int32_t* e) {
+    for (int n = 0; n < Cout; ++n) {
+        float amax = 0.0f;
+        for (int k = 0; k < K; ++k) {
+            const float a = std::fabs(w[(size_t)k * Cout + n]);
+            if (a > amax) amax = a;                            // (a NaN does not count)
+        }
+        int ex = 0;
+        if (amax > 0.0f && amax < INFINITY) {
+            (void)std::frexp(amax, &ex);
+            ex = std::max(-100, std::min(100, vbx::kSplitTop - ex));
+        }
+        e[n] = ex;
+    }
+    const int CBT = Cout / 32;
+    for (int k = 0; k < K; ++k)
+        for (int n = 0; n < Cout; ++n) {
+            const float v = std::ldexp(w[(size_t)k * Cout + n], e[n]);
+            const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
+            const size_t lane = 32 * ((k & 15) >> 3) + (n & 31);
+            const size_t o = (((size_t)(k >> 4) * CBT + (n >> 5)) * 2 * 64 + lane) * 8 + (k & 7);
+            std::memcpy(&frag[o], &hi, 2);
+            std::memcpy(&frag[o + 64 * 8], &lo, 2);
+        }
 }
 
 // the BN x BM output tile of a convolution of M output positions x Cout channels (Cout a multiple of 32)
@@ -108,6 +180,15 @@ struct RnStep {
         HIPCHK(ctx, hipMemcpyAsync(*dev, host, sizeof(float) * count, hipMemcpyHostToDevice, ctx->stream));
         return VBX_OK;
     }
+    int up_bytes(const void* host, size_t bytes, void** dev) {
+        *dev = nullptr;
+        const int rc = dmalloc_bytes(ctx, dev, std::max<size_t>(bytes, 4));
+        if (rc != VBX_OK) return rc;
+        blocks.push_back((float*)*dev);
+        if (host) HIPCHK(ctx, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        else HIPCHK(ctx, hipMemsetAsync(*dev, 0, bytes, ctx->stream));
+        return VBX_OK;
+    }
     // the kernel has been launched: wait for it and bring the whole in/out buffer back
     int down(const char* what, float* host, const float* dev, size_t count) {
         hipError_t e = hipGetLastError();
@@ -129,7 +210,8 @@ int vbx_resnet_destroy(vbx_resnet* net) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (void* p : {(void*)net->d_par, (void*)net->d_emb_w, (void*)net->d_emb_b, (void*)net->d_in, (void*)net->d_x[0],
-                    (void*)net->d_x[1], (void*)net->d_t1, (void*)net->d_t2, (void*)net->d_sc, (void*)net->d_pool, (void*)net->d_out})
+                    (void*)net->d_x[1], (void*)net->d_t1, (void*)net->d_t2, (void*)net->d_sc, (void*)net->d_pool, (void*)net->d_out,
+                    (void*)net->d_wf, (void*)net->d_we, (void*)net->d_amax})
         ctx_free(ctx, p);
     for (auto& e : net->ev)
         if (e) (void)hipEventDestroy(e);
@@ -158,14 +240,33 @@ int vbx_resnet_create(vbx_ctx* ctx, int32_t embed_dim, const float* params, int6
     for (size_t k = 0; k < (size_t)RN_POOL; ++k)
         std::memcpy(&ew[k * Ep], params + nconv + k * E, sizeof(float) * E);
     std::memcpy(eb.data(), params + nconv + (size_t)RN_POOL * E, sizeof(float) * E);
+    // the split mode's copy of every convolution but the stem
+    size_t nwf = 0, nwe = 0;
+    for (size_t k = 1; k < net->convs.size(); ++k) {
+        RnConv& c = net->convs[k];
+        c.wf = nwf;
+        c.we = nwe;
+        nwf += (size_t)c.ks * c.ks * c.cin * c.cout / 4;       // two halfs per weight, eight per unit
+        nwe += c.cout;
+    }
+    std::vector<uint16_t> wf(nwf * 8);
+    std::vector<int32_t> we(nwe);
+    for (size_t k = 1; k < net->convs.size(); ++k) {
+        const RnConv& c = net->convs[k];
+        rn_split_weights(params + c.w, c.ks * c.ks * c.cin, c.cout, &wf[c.wf * 8], &we[c.we]);
+    }
     hipError_t e = hipSetDevice(ctx->device);
     int rc = e == hipSuccess ? dmalloc(ctx, &net->d_par, nconv) : VBX_ERR_HIP;
+    if (rc == VBX_OK) rc = dmalloc(ctx, &net->d_wf, nwf);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &net->d_we, nwe);
     if (rc == VBX_OK) rc = dmalloc(ctx, &net->d_emb_w, ew.size());
     if (rc == VBX_OK) rc = dmalloc(ctx, &net->d_emb_b, eb.size());
     if (rc == VBX_OK) {
         e = hipMemcpy(net->d_par, params, sizeof(float) * nconv, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(net->d_emb_w, ew.data(), sizeof(float) * ew.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(net->d_emb_b, eb.data(), sizeof(float) * eb.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(net->d_wf, wf.data(), sizeof(uint16_t) * wf.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(net->d_we, we.data(), sizeof(int32_t) * we.size(), hipMemcpyHostToDevice);
         for (auto& ev : net->ev)
             if (e == hipSuccess) e = hipEventCreate(&ev);
     }
@@ -222,7 +323,26 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
     if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_pool, &net->cap_pool, (size_t)n * RN_POOL);
     if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_out, &net->cap_out, (size_t)n * net->Ep);
     if (rc == VBX_OK && !x_on_device) rc = fb_reserve(ctx, &net->d_in, &net->cap_in, (size_t)n * RN_MEL * T);
+    const bool split = net->gemm == VBX_GEMM_SPLIT;
+    if (rc == VBX_OK && split) rc = fb_reserve(ctx, &net->d_amax, &net->cap_amax, (size_t)RN_AMAX_SLOTS * n);
     if (rc != VBX_OK) return rc;
+    net->gemm_last = net->gemm;
+    if (split) HIPCHK(ctx, hipMemsetAsync(net->d_amax, 0, sizeof(unsigned) * RN_AMAX_SLOTS * (size_t)n, st));
+    // one convolution in the run's mode; ax / ay: the max |.| slots of its input and (or null) of its output
+    auto conv = [&](const RnConv& c, const float* xs, const unsigned* ax, const float* res, float* ys, unsigned* ay, int H, int W,
+                    int relu) {
+        if (split) {
+            const int Ho = rn_out(H, c.stride), Wo = rn_out(W, c.stride);
+            const long long M = (long long)n * Ho * Wo;
+            int BN, BM;
+            rn_tile(M, c.cout, &BN, &BM);
+            rn_launch_split(st, c.ks, c.stride, BN, BM, xs, ax, net->d_wf + c.wf, net->d_we + c.we, net->d_par + c.b, res, ys, ay, H,
+                            W, c.cin, Ho, Wo, c.cout, M, relu);
+        } else {
+            rn_conv(st, c.ks, c.stride, xs, net->d_par + c.w, net->d_par + c.b, res, ys, n, H, W, c.cin, c.cout, relu);
+        }
+    };
+    auto slot = [&](int s) { return split ? net->d_amax + (size_t)s * n : nullptr; };
     const float* xin = x;
     if (!x_on_device) {
         HIPCHK(ctx, hipMemcpyAsync(net->d_in, x, sizeof(float) * (size_t)n * RN_MEL * T, hipMemcpyHostToDevice, st));
@@ -234,28 +354,30 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
     const long long tot0 = (long long)n * RN_MEL * T * 32;
     hipLaunchKernelGGL(resnet_stem_kernel, dim3((unsigned)((tot0 + 255) / 256)), dim3(256), 0, st, xin, P + c0.w, P + c0.b,
                        net->d_x[0], T, tot0);
+    if (split) rn_amax(st, net->d_x[0], n, (long long)RN_MEL * T * 32, slot(0));     // (the stem itself stays as it is)
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(net->ev[1], st));
-    int cur = 0, H = RN_MEL, W = T, k = 1;
+    int cur = 0, H = RN_MEL, W = T, k = 1, blk = 0;
     for (int L = 0; L < 4; ++L) {
         for (int i = 0; i < RN_BLOCKS[L]; ++i) {
             const RnConv &a = net->convs[k], &b = net->convs[k + 1], &c = net->convs[k + 2];
             const float* xs = net->d_x[cur];
             float* ys = net->d_x[cur ^ 1];
-            rn_conv(st, a.ks, a.stride, xs, P + a.w, P + a.b, nullptr, net->d_t1, n, H, W, a.cin, a.cout, 1);
-            rn_conv(st, b.ks, b.stride, net->d_t1, P + b.w, P + b.b, nullptr, net->d_t2, n, H, W, b.cin, b.cout, 1);
+            const int s0 = 3 * blk;                            // slots: s0 the block's input, then conv1, conv2, the output
+            conv(a, xs, slot(s0), nullptr, net->d_t1, slot(s0 + 1), H, W, 1);
+            conv(b, net->d_t1, slot(s0 + 1), nullptr, net->d_t2, slot(s0 + 2), H, W, 1);
             const float* res = xs;
             if (i == 0) {
-                const RnConv& sc = net->convs[k + 3];
-                rn_conv(st, sc.ks, sc.stride, xs, P + sc.w, P + sc.b, nullptr, net->d_sc, n, H, W, sc.cin, sc.cout, 0);
+                conv(net->convs[k + 3], xs, slot(s0), nullptr, net->d_sc, nullptr, H, W, 0);
                 res = net->d_sc;
             }
             H = rn_out(H, b.stride);
             W = rn_out(W, b.stride);
-            rn_conv(st, c.ks, c.stride, net->d_t2, P + c.w, P + c.b, res, ys, n, H, W, c.cin, c.cout, 1);
+            conv(c, net->d_t2, slot(s0 + 2), res, ys, slot(s0 + 3), H, W, 1);
             HIPCHK(ctx, hipGetLastError());
             k += i == 0 ? 4 : 3;
             cur ^= 1;
+            ++blk;
         }
         HIPCHK(ctx, hipEventRecord(net->ev[2 + L], st));
     }
@@ -279,6 +401,26 @@ int vbx_resnet_times(vbx_resnet* net, float* ms) {
     return VBX_OK;
 }
 
+int vbx_resnet_set_gemm(vbx_resnet* net, int gemm) {
+    if (!net) return VBX_ERR_INVALID;
+    if (gemm != VBX_GEMM_EXACT && gemm != VBX_GEMM_SPLIT)
+        FAIL(net->ctx, VBX_ERR_INVALID, "vbx_resnet_set_gemm takes VBX_GEMM_EXACT or VBX_GEMM_SPLIT");
+#ifdef VBX_ISA_UNAUDITED
+    if (gemm == VBX_GEMM_SPLIT)
+        FAIL(net->ctx, VBX_ERR_UNSUPPORTED, "VBX_GEMM_SPLIT: this library was built without the ISA audit (vbx_amd/build.py); rebuild with llvm-objdump available");
+#endif
+    net->gemm = gemm;
+    return VBX_OK;
+}
+
+int vbx_resnet_gemm_in_effect(vbx_resnet* net) { return net ? net->gemm_last : VBX_ERR_INVALID; }
+
+int vbx_resnet_split_weights(int32_t K, int32_t Cout, const float* w, uint16_t* frag, int32_t* e) {
+    if (!w || !frag || !e || K <= 0 || Cout <= 0 || K % 16 != 0 || Cout % 32 != 0) return VBX_ERR_INVALID;
+    rn_split_weights(w, K, Cout, frag, e);
+    return VBX_OK;
+}
+
 int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm) {
     if (!bn || !bm || M <= 0 || Cout <= 0 || Cout % 32 != 0) return VBX_ERR_INVALID;
     int BN, BM;
@@ -288,41 +430,79 @@ int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm) {
     return VBX_OK;
 }
 
-int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
-                    const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn, int32_t bm,
-                    float* y, int64_t pad) {
+// vbx_resnet_conv and vbx_resnet_conv_gemm: one convolution on host arrays in either mode
+static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W,
+                        int32_t Cin, int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu,
+                        int32_t bn, int32_t bm, float* y, int64_t pad, float* amax_y) {
     if (!ctx) return VBX_ERR_INVALID;
-    if (!x || !w || !bias || !y) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: x, w, bias and y must not be NULL");
+    if (gemm != VBX_GEMM_EXACT && gemm != VBX_GEMM_SPLIT) FAIL(ctx, VBX_ERR_INVALID, "%s: gemm must be VBX_GEMM_EXACT or VBX_GEMM_SPLIT", name);
+#ifdef VBX_ISA_UNAUDITED
+    if (gemm == VBX_GEMM_SPLIT)
+        FAIL(ctx, VBX_ERR_UNSUPPORTED, "%s: VBX_GEMM_SPLIT: this library was built without the ISA audit (vbx_amd/build.py)", name);
+#endif
+    if (!x || !w || !bias || !y) FAIL(ctx, VBX_ERR_INVALID, "%s: x, w, bias and y must not be NULL", name);
     if (n <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || pad < 0)
-        FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: n = %d, H = %d, W = %d, Cin = %d, Cout = %d must be positive, pad = %lld not negative",
+        FAIL(ctx, VBX_ERR_INVALID, "%s: n = %d, H = %d, W = %d, Cin = %d, Cout = %d must be positive, pad = %lld not negative", name,
              n, H, W, Cin, Cout, (long long)pad);
     if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2))
-        FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: kernel size %d stride %d: built for 1 or 3 at stride 1 or 2", ks, stride);
-    if (Cin % RN_BK != 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: Cin = %d is not a multiple of %d", Cin, RN_BK);
+        FAIL(ctx, VBX_ERR_INVALID, "%s: kernel size %d stride %d: built for 1 or 3 at stride 1 or 2", name, ks, stride);
+    if (Cin % RN_BK != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cin = %d is not a multiple of %d", name, Cin, RN_BK);
     const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
     const long long M = (long long)n * Ho * Wo;
     int BN = bn, BM = bm;
     if (bn == 0 && bm == 0) {
-        if (Cout % 32 != 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: Cout = %d is not a multiple of 32", Cout);
+        if (Cout % 32 != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of 32", name, Cout);
         rn_tile(M, Cout, &BN, &BM);
     } else {
         const bool built = (bn == 128 && bm == 64) || (bn == 128 && bm == 128) || (bn == 64 && bm == 64) || (bn == 64 && bm == 128) ||
                            (bn == 32 && bm == 128);
-        if (!built) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: no %d x %d tile (BN x BM: 128 x 64, 128 x 128, 64 x 64, 64 x 128, 32 x 128)", bn, bm);
-        if (Cout % bn != 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_conv: Cout = %d is not a multiple of the tile's BN = %d", Cout, bn);
+        if (!built) FAIL(ctx, VBX_ERR_INVALID, "%s: no %d x %d tile (BN x BM: 128 x 64, 128 x 128, 64 x 64, 64 x 128, 32 x 128)", name, bn, bm);
+        if (Cout % bn != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of the tile's BN = %d", name, Cout, bn);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RnStep s(ctx);
     const size_t ny = (size_t)M * Cout + 2 * (size_t)pad;
-    float *dx, *dw, *db, *dr, *dy;
+    float *dx, *dw = nullptr, *db, *dr, *dy;
     int rc = s.up(x, (size_t)n * H * W * Cin, &dx);
-    if (rc == VBX_OK) rc = s.up(w, (size_t)ks * ks * Cin * Cout, &dw);
     if (rc == VBX_OK) rc = s.up(bias, (size_t)Cout, &db);
     if (rc == VBX_OK) rc = s.up(res, (size_t)M * Cout, &dr);
     if (rc == VBX_OK) rc = s.up(y, ny, &dy);
     if (rc != VBX_OK) return rc;
-    rn_launch(ctx->stream, ks, stride, BN, BM, dx, dw, db, dr, dy + pad, H, W, Cin, Ho, Wo, Cout, M, relu ? 1 : 0);
-    return s.down("vbx_resnet_conv", y, dy, ny);
+    if (gemm == VBX_GEMM_EXACT) {
+        rc = s.up(w, (size_t)ks * ks * Cin * Cout, &dw);
+        if (rc != VBX_OK) return rc;
+        rn_launch(ctx->stream, ks, stride, BN, BM, dx, dw, db, dr, dy + pad, H, W, Cin, Ho, Wo, Cout, M, relu ? 1 : 0);
+        return s.down(name, y, dy, ny);
+    }
+    const int K = ks * ks * Cin;
+    std::vector<uint16_t> wf((size_t)K * Cout * 2);
+    std::vector<int32_t> we(Cout);
+    rn_split_weights(w, K, Cout, wf.data(), we.data());
+    void *dwf, *dwe, *dax, *day;
+    rc = s.up_bytes(wf.data(), sizeof(uint16_t) * wf.size(), &dwf);
+    if (rc == VBX_OK) rc = s.up_bytes(we.data(), sizeof(int32_t) * we.size(), &dwe);
+    if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &dax);
+    if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &day);
+    if (rc != VBX_OK) return rc;
+    rn_amax(ctx->stream, dx, n, (long long)H * W * Cin, (unsigned*)dax);
+    rn_launch_split(ctx->stream, ks, stride, BN, BM, dx, (const unsigned*)dax, (const vbx::h8*)dwf, (const int*)dwe, db, dr, dy + pad,
+                    (unsigned*)day, H, W, Cin, Ho, Wo, Cout, M, relu ? 1 : 0);
+    if (amax_y) HIPCHK(ctx, hipMemcpyAsync(amax_y, day, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    return s.down(name, y, dy, ny);                            // (wf and we outlive the copies: down() synchronizes)
+}
+
+int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                    const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn, int32_t bm,
+                    float* y, int64_t pad) {
+    return rn_conv_step("vbx_resnet_conv", ctx, VBX_GEMM_EXACT, ks, stride, n, H, W, Cin, Cout, x, w, bias, res, relu, bn, bm, y, pad,
+                        nullptr);
+}
+
+int vbx_resnet_conv_gemm(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin,
+                         int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn,
+                         int32_t bm, float* y, int64_t pad, float* amax_y) {
+    return rn_conv_step("vbx_resnet_conv_gemm", ctx, gemm, ks, stride, n, H, W, Cin, Cout, x, w, bias, res, relu, bn, bm, y, pad,
+                        amax_y);
 }
 
 int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const float* w, const float* bias, float* y, int64_t pad) {

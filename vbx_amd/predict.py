@@ -34,6 +34,9 @@ def parse_args(argv=None):
     p.add_argument('--weights', type=str, default=None, help='not supported: use --checkpoint or --model-file')
     p.add_argument('--checkpoint', type=str, default=None,
                    help="ResNet101 weights in predict.py's --weights format (e.g. raw_81.pth), run in HIP")
+    p.add_argument('--gemm', default='exact', choices=['exact', 'split'],
+                   help='how the --checkpoint network multiplies: exact f32 matrix instructions (default), or f16 matrix '
+                        'instructions on error-compensated operand pairs (f32-level accuracy, faster)')
     p.add_argument('--model-file', type=str, default=None, help='TorchScript embedding model: [B, ndim, T] -> [B, embed]')
     p.add_argument('--ndim', type=int, default=64, help='dimensionality of features')
     p.add_argument('--embed-dim', type=int, default=256, help='dimensionality of the emb')
@@ -55,6 +58,8 @@ def parse_args(argv=None):
                 'VBx/models/ResNet101_16kHz/nnet/raw_81.pth) or a TorchScript module with --model-file')
     if args.model_file is not None and args.checkpoint is not None:
         p.error('--checkpoint and --model-file exclude each other: pass one embedding model')
+    if args.gemm != 'exact' and args.checkpoint is None:
+        p.error('--gemm applies to the --checkpoint network only')
     if args.gpus.strip() == '':
         p.error('--gpus is empty: this extractor runs on a GPU only; pass a device index such as --gpus 0')
     if args.ndim != fbank.N_MEL:
@@ -109,7 +114,7 @@ def main(argv=None):
             sd = xvector.load_checkpoint(args.checkpoint, embed_dim=args.embed_dim)
         except (ValueError, OSError) as exc:
             raise SystemExit(f'--checkpoint {args.checkpoint}: {exc}')
-        net = xvector.ResNet101(sd, device)
+        net = xvector.ResNet101(sd, device, gemm=args.gemm)
         del sd
         embed = net.embed_windows
     else:

@@ -6,7 +6,11 @@
     fold                    BatchNorm folded into each convolution in f64, packed in the order libvbx_hip.so reads
     forward_reference       the network in f64 on the CPU from the raw checkpoint (torch.nn.functional): the referee
     forward_folded          the same from the folded, packed parameters (checks fold; run_folded: on any torch device)
-    ResNet101               the device path (vbx_resnet.hpp): windows [B][64][T] -> embeddings [B][E] f32
+    ResNet101               the device path (vbx_resnet.hpp): windows [B][64][T] -> embeddings [B][E] f32; gemm='split'
+                            runs layer1 .. layer4 on the f16 matrix cores with error-compensated operands
+    split_terms             the representation of the split mode (x 2^e = hi + lo in f16), its one definition
+    pack_split_weights      the split weights in the device's fragment order (unpack_split_weights: back)
+    forward_split_emulated  the split mode's arithmetic on the CPU (torch, f32 accumulation)
 
 The network: conv 3x3 1 -> 32 + BN + ReLU; Bottleneck stages of [3, 4, 23, 3] blocks, planes 32 / 64 / 128 / 256
 (expansion 4), strides 1 / 2 / 2 / 2, a 1x1 conv + BN shortcut in the first block of every stage; mean and standard
@@ -230,12 +234,116 @@ def forward_folded(params, embed_dim: int, x) -> np.ndarray:
     return run_folded(folded_tensors(params, embed_dim), torch.from_numpy(np.asarray(x, dtype=np.float64))).numpy()
 
 
+SPLIT_TOP = 14                                         # a scaling group's largest magnitude sits in [2^13, 2^14)
+
+
+def split_exponent(amax) -> np.ndarray:
+    """e with amax 2^e in [2^13, 2^14) (clamped to +-100); 0 where amax is zero or not finite."""
+    amax = np.asarray(amax, dtype=np.float32)
+    ok = np.isfinite(amax) & (amax > 0)
+    _, ex = np.frexp(np.where(ok, amax, np.float32(1.0)))
+    return np.where(ok, np.clip(SPLIT_TOP - ex, -100, 100), 0).astype(np.int32)
+
+
+def split_terms(x, amax):
+    """The split mode's representation of f32 values x under the scale of their group's largest magnitude amax (an array
+    that broadcasts against x): -> (hi, lo, e) with x 2^e = hi + lo up to 2^-23 |x|, hi = f16(x 2^e), lo = f16(x 2^e - hi)
+    (both float16, round to nearest even), e = split_exponent(amax).  What the device computes, operation for operation."""
+    x = np.asarray(x, dtype=np.float32)
+    e = split_exponent(amax)
+    with np.errstate(over='ignore', invalid='ignore'):
+        v = np.ldexp(x, e).astype(np.float32)
+        hi = v.astype(np.float16)
+        lo = (v - hi.astype(np.float32)).astype(np.float16)
+    return hi, lo, e
+
+
+def _finite_amax(a, axis):
+    a = np.abs(np.asarray(a, dtype=np.float32))
+    return np.where(np.isfinite(a), a, np.float32(0)).max(axis=axis)
+
+
+def pack_split_weights(w):
+    """w [K][Cout] f32 (K a multiple of 16, Cout of 32) -> (frag float16 [K / 16][Cout / 32][hi | lo][64][8], e int32 [Cout]):
+    one scale per output channel, in the fragment order of the B operand of v_mfma_f32_32x32x16_f16 -- lane l holds
+    B[k = 8 (l >> 5) + j][column l & 31] in element j.  What vbx_resnet_create stores (vbx_resnet_split_weights)."""
+    w = np.asarray(w, dtype=np.float32)
+    K, Cout = w.shape
+    assert K % 16 == 0 and Cout % 32 == 0
+    aw = np.abs(w)
+    amax = np.fmax.reduce(aw, axis=0) if K else np.zeros(Cout, np.float32)          # (a NaN does not count)
+    hi, lo, e = split_terms(w, amax[None, :])
+    t = np.stack([hi, lo])                                                           # [term][k][n]
+    # k = 16 kstep + 8 h + j, n = 32 cb + r  ->  [kstep][cb][term][lane = 32 h + r][j]
+    frag = t.reshape(2, K // 16, 2, 8, Cout // 32, 32).transpose(1, 4, 0, 2, 5, 3).reshape(K // 16, Cout // 32, 2, 64, 8)
+    return np.ascontiguousarray(frag), e.reshape(-1)
+
+
+def unpack_split_weights(frag, e):
+    """pack_split_weights backwards: -> (hi, lo) float16 [K][Cout]."""
+    ksteps, cbs = frag.shape[:2]
+    t = frag.reshape(ksteps, cbs, 2, 2, 32, 8).transpose(2, 0, 3, 5, 1, 4).reshape(2, ksteps * 16, cbs * 32)
+    assert t.shape[2] == len(e)
+    return t[0], t[1]
+
+
+def forward_split_emulated(params, embed_dim: int, x) -> np.ndarray:
+    """The split mode on the CPU (torch): the stem, the pooling (f64 sums) and the embedding as the exact mode has them in
+    f32; every other convolution as lo hi + hi lo + hi hi of split_terms' operands -- activations scaled per window (the
+    largest finite magnitude), weights per output channel -- accumulated in f32, then 2^-(e_window + e_channel), + bias,
+    + res, ReLU.  torch sums in another order than the device, so this shows the mode's accuracy, not its bits."""
+    import torch
+    import torch.nn.functional as F
+    tens = folded_tensors(np.asarray(params, dtype=np.float32), embed_dim, dtype=torch.float32)
+    it = iter(tens)
+
+    def conv(h, stride, relu, res=None):
+        w, b = next(it)
+        cout, cin, k, _ = w.shape
+        wk = w.permute(2, 3, 1, 0).reshape(k * k * cin, cout).numpy()
+        whi, wlo, we = split_terms(wk, np.fmax.reduce(np.abs(wk), axis=0)[None, :])
+        hn = h.numpy()
+        ahi, alo, ae = split_terms(hn, _finite_amax(hn.reshape(len(hn), -1), 1)[:, None, None, None])
+        back = lambda a: torch.from_numpy(a.astype(np.float32).reshape(k, k, cin, cout)).permute(3, 2, 0, 1).contiguous()
+        t = lambda a: torch.from_numpy(a.astype(np.float32))
+        kw = dict(stride=stride, padding=k // 2)
+        acc = F.conv2d(t(alo), back(whi), **kw) + F.conv2d(t(ahi), back(wlo), **kw) + F.conv2d(t(ahi), back(whi), **kw)
+        scale = np.ldexp(np.float32(1), -(ae.reshape(-1, 1, 1, 1) + we.reshape(1, -1, 1, 1))).astype(np.float32)
+        y = acc * torch.from_numpy(scale) + b.reshape(1, -1, 1, 1)
+        if res is not None:
+            y = y + res
+        return F.relu(y) if relu else y
+
+    with torch.no_grad():
+        w, b = next(it)
+        h = F.relu(F.conv2d(torch.from_numpy(np.asarray(x, dtype=np.float32))[:, None], w, b, padding=1))
+        for n, stride in zip(BLOCKS, STRIDES):
+            for i in range(n):
+                s = stride if i == 0 else 1
+                o = conv(conv(h, 1, True), s, True)
+                # (conv3 comes before the shortcut in the parameter order)
+                c3 = next(it)
+                sc = conv(h, s, False) if i == 0 else h
+                it, rest = iter([c3]), it
+                h = conv(o, 1, True, res=sc)
+                it = rest
+        hd = h.double()
+        mean = hd.mean(dim=-1)
+        std = torch.sqrt((hd * hd).mean(dim=-1) - mean ** 2 + 1e-10)
+        pooled = torch.cat([mean.transpose(1, 2).flatten(1), std.transpose(1, 2).flatten(1)], 1).float()
+        ew, eb = next(it)
+        return (pooled @ ew + eb).numpy()
+
+
 class ResNet101:
     """The network on one device.  ``embed(x)``: x [B][64][T] f32 (numpy, or a torch tensor on the device) -> [B][E] f32
-    of the same kind.  Runs on the device context's stream, the front end's (vbx_amd.fbank), so that ``embed_windows``
+    of the same kind.  gemm: 'exact' (default: the f32 matrix instructions) or 'split' (f16 matrix instructions on
+    error-compensated operand pairs: f32-level accuracy, faster, other bits).  Runs on the device context's stream, the front end's (vbx_amd.fbank), so that ``embed_windows``
     goes from features to embeddings without a host round trip or a torch allocation."""
 
-    def __init__(self, sd, device: int = 0):
+    def __init__(self, sd, device: int = 0, gemm: str = 'exact'):
+        if gemm not in ('exact', 'split'):
+            raise ValueError(f"gemm must be 'exact' or 'split', got {gemm!r}")
         sd = check_state_dict(sd)
         self.embed_dim = int(sd['embedding.weight'].shape[0])
         self.device = int(device)
@@ -245,14 +353,18 @@ class ResNet101:
             except ImportError:
                 pass
         self.ctx = _capi.default_context(self.device)
-        self.dev = _capi.ResNetDevice(self.ctx, fold(sd).astype(np.float32), self.embed_dim)
+        self.dev = _capi.ResNetDevice(self.ctx, fold(sd).astype(np.float32), self.embed_dim, gemm=gemm)
+
+    def gemm_in_effect(self) -> str:
+        """'exact' or 'split': how the convolutions of the last embed() multiplied."""
+        return self.dev.gemm_in_effect()
 
     @classmethod
-    def from_checkpoint(cls, src, device: int = 0, embed_dim: int | None = None) -> 'ResNet101':
+    def from_checkpoint(cls, src, device: int = 0, embed_dim: int | None = None, gemm: str = 'exact') -> 'ResNet101':
         """src: a checkpoint path (predict.py's ``--weights``) or a state_dict."""
         sd = load_checkpoint(src, embed_dim) if isinstance(src, (str, bytes)) or hasattr(src, '__fspath__') else \
             check_state_dict(src, embed_dim)
-        return cls(sd, device)
+        return cls(sd, device, gemm)
 
     def embed(self, x):
         if hasattr(x, 'data_ptr'):
