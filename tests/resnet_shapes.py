@@ -71,20 +71,8 @@ def fixture_runs(win_rec, win_len, seg_len=144):
 def network_convs(T, embed_dim=256):
     """(ks, stride, Cin, Cout, H, W) of every convolution of one run at T frames, in network order (the stem, a kernel of
     its own, left out), and the embedding as the 1 x 1 convolution it runs as."""
-    out, H, W = [], xvector.FEAT_DIM, T
-    specs = xvector.conv_specs()[1:]
-    k = 0
-    while k < len(specs):
-        first = k + 3 < len(specs) and specs[k + 3][0].endswith('shortcut.0')
-        s = specs[k + 1][3]
-        Ho, Wo = rn_out(H, s), rn_out(W, s)
-        for j, (h, w) in enumerate(((H, W), (H, W), (Ho, Wo), (H, W))[:4 if first else 3]):
-            _, _, ks, stride, cin, cout = specs[k + j]
-            out.append((ks, stride, cin, cout, h, w))
-        k += 4 if first else 3
-        H, W = Ho, Wo
-    out.append((1, 1, xvector.POOL_DIM, (embed_dim + 31) // 32 * 32, 1, 1))
-    return out
+    out = [(ks, stride, cin, cout, H, W) for (_, _, ks, stride, cin, cout), H, W in xvector.walk(T)]
+    return out + [(1, 1, xvector.POOL_DIM, (embed_dim + 31) // 32 * 32, 1, 1)]
 
 
 _tile_cache = {}
@@ -106,3 +94,18 @@ def conv_classes(n, T):
         bn, bm = conv_tile(M, cout)
         out.add((ks, stride, bn, bm, M % bm != 0))
     return out
+
+
+def layer_cases(embedding=False):
+    """(ks, stride, Cin, Cout, H, W, n): every distinct convolution of the network at the W that T = 141 and 144 give at
+    its depth, at the smallest n of the domain for every tile the dispatcher can pick for it; and (embedding) the embedding."""
+    out = []
+    domain = list(range(1, 129)) + [192, 256, 384, 512]
+    for layer in sorted({c for T in (141, 144) for c in network_convs(T)[:-1]}):
+        ks, stride, cin, cout, H, W = layer
+        hw = rn_out(H, stride) * rn_out(W, stride)
+        first = {}
+        for n in domain:
+            first.setdefault(conv_tile(n * hw, cout), n)
+        out += [layer + (n,) for n in first.values()]
+    return out + [(1, 1, xvector.POOL_DIM, 256, 1, 1, n) for n in (1, 3, 37) if embedding]

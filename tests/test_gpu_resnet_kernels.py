@@ -133,23 +133,8 @@ def test_geometry_edges(ctx, ks, stride, tile):
             assert (y.min() >= 0) == relu
 
 
-def _layer_cases():
-    """(ks, stride, Cin, Cout, H, W, n): every distinct convolution of the network at the W that T = 141 and 144 give at
-    its depth, at the smallest n of the domain for every tile the dispatcher can pick for it; and the embedding."""
-    out = []
-    domain = list(range(1, 129)) + [192, 256, 384, 512]
-    for layer in sorted({c for T in (141, 144) for c in rs.network_convs(T)[:-1]}):
-        ks, stride, cin, cout, H, W = layer
-        hw = rs.rn_out(H, stride) * rs.rn_out(W, stride)
-        first = {}
-        for n in domain:
-            first.setdefault(rs.conv_tile(n * hw, cout), n)
-        out += [layer + (n,) for n in first.values()]
-    return out + [(1, 1, xvector.POOL_DIM, 256, 1, 1, n) for n in (1, 3, 37)]
-
-
 def test_the_networks_own_layers(ctx):
-    for ks, stride, cin, cout, H, W, n in _layer_cases():
+    for ks, stride, cin, cout, H, W, n in rs.layer_cases(embedding=True):
         rng = np.random.default_rng(cin + cout + W + n)
         x, w, bias, res = make(rng, ks, n, H, W, cin, cout, stride, with_res=ks == 1)
         w *= np.float32(1.0 / np.sqrt(ks * ks * cin))

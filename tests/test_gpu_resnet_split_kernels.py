@@ -137,23 +137,8 @@ def test_small_k_sees_every_term(ctx, cin, tile):
     assert (2 * 2.0 ** -23 + 2.0 ** -22 + gamma(3 * cin + 2)) * (1 + 2.0 ** -9) < 2.0 ** -12 / 16
 
 
-def _layer_cases():
-    """(ks, stride, Cin, Cout, H, W, n): every distinct convolution of the network at the W that T = 141 and 144 give at
-    its depth, at the smallest n of the domain for every tile the dispatcher can pick for it."""
-    out = []
-    domain = list(range(1, 129)) + [192, 256, 384, 512]
-    for layer in sorted({c for T in (141, 144) for c in rs.network_convs(T)[:-1]}):
-        ks, stride, cin, cout, H, W = layer
-        hw = rs.rn_out(H, stride) * rs.rn_out(W, stride)
-        first = {}
-        for n in domain:
-            first.setdefault(rs.conv_tile(n * hw, cout), n)
-        out += [layer + (n,) for n in first.values()]
-    return out
-
-
 def test_the_networks_own_layers(ctx):
-    for ks, stride, cin, cout, H, W, n in _layer_cases():
+    for ks, stride, cin, cout, H, W, n in rs.layer_cases():
         rng = np.random.default_rng(cin + cout + W + n)
         x, w, bias, res = make(rng, ks, n, H, W, cin, cout, stride, with_res=ks == 1)
         w *= np.float32(1.0 / np.sqrt(ks * ks * cin))

@@ -109,6 +109,27 @@ def test_network_runs_reach_every_reachable_convolution_class():
     assert all((bn, bm) in rs.TILES for _, _, bn, bm, _ in domain)
 
 
+def test_the_network_walk_is_what_it_was():
+    """xvector.walk / flops and resnet_shapes.network_convs against literals recorded from the hand-written loops they replace."""
+    import hashlib
+    import resnet_shapes as rs
+    digest = {10: 'e8a7602b07607708', 141: '34b5bc635944d6ca', 144: 'e75d2e1992ba3593'}
+    for T, want in digest.items():
+        convs = rs.network_convs(T)
+        assert len(convs) == 104
+        assert hashlib.sha256(repr(convs).encode()).hexdigest()[:16] == want, T
+    convs = rs.network_convs(144)
+    assert convs[0] == (1, 1, 32, 32, 64, 144) and convs[3] == (1, 1, 32, 128, 64, 144)
+    assert convs[4] == (1, 1, 128, 32, 64, 144) and convs[10] == (1, 1, 128, 64, 64, 144)
+    assert convs[-2] == (1, 1, 256, 1024, 8, 18) and convs[-1] == (1, 1, 16384, 256, 1, 1)
+    assert rs.network_convs(10)[-2] == (1, 1, 256, 1024, 8, 2)
+    assert xvector.flops(144) == {'stem': 5308416, 'layer1': 981467136, 'layer2': 1509949440, 'layer3': 7606370304,
+                                  'layer4': 1189085184}
+    assert xvector.flops(19) == {'stem': 700416, 'layer1': 129499136, 'layer2': 208666624, 'layer3': 1056440320,
+                                 'layer4': 193986560}
+    assert len(list(xvector.blocks())) == 33 and [spec for spec, _, _ in xvector.walk(144)] == xvector.conv_specs()[1:]
+
+
 def test_forced_tile_table_holds_every_instantiation():
     import resnet_shapes as rs
     cases = rs.FORCED_CASES

@@ -512,10 +512,9 @@ def resnet_conv_tile(M, Cout):
     return bn.value, bm.value
 
 
-def resnet_conv(ctx: 'Context', x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
-    """One convolution of the network (vbx_resnet_conv): x [n][H][W][Cin], w [ks ks Cin][Cout], bias [Cout], res
-    [n][Ho][Wo][Cout] or None; tile None (the dispatcher's) or (BN, BM).  -> (y [n][Ho][Wo][Cout], guard-band words the
-    kernel changed, output words it left unwritten)."""
+def _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad):
+    """The shape bookkeeping of one convolution step: call(n, H, W, Cin, Cout, x, w, bias, res, relu, bn, bm, buf, pad) runs
+    the C entry on the guarded output buffer.  -> (y [n][Ho][Wo][Cout], guard, unwritten)."""
     x, w, bias, res = _f32(x), _f32(w), _f32(bias), _f32(res)
     n, H, W, Cin = x.shape
     Cout = w.shape[1]
@@ -525,30 +524,29 @@ def resnet_conv(ctx: 'Context', x, w, bias, ks, stride, res=None, relu=False, ti
     assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (res is None or res.size == count)
     bn, bm = tile or (0, 0)
     buf = _guarded(count, pad)
-    ctx.check(ctx._lib.vbx_resnet_conv(ctx._h, int(ks), int(stride), n, H, W, Cin, Cout, _ptr(x), _ptr(w), _ptr(bias), _ptr(res),
-                                       int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad)), 'vbx_resnet_conv')
+    call(n, H, W, Cin, Cout, _ptr(x), _ptr(w), _ptr(bias), _ptr(res), int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad))
     y, guard, unwritten = _unguard(buf, count, pad)
     return y.reshape(n, Ho, Wo, Cout), guard, unwritten
+
+
+def resnet_conv(ctx: 'Context', x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
+    """One convolution of the network (vbx_resnet_conv): x [n][H][W][Cin], w [ks ks Cin][Cout], bias [Cout], res
+    [n][Ho][Wo][Cout] or None; tile None (the dispatcher's) or (BN, BM).  -> (y [n][Ho][Wo][Cout], guard-band words the
+    kernel changed, output words it left unwritten)."""
+    def call(*a):
+        ctx.check(ctx._lib.vbx_resnet_conv(ctx._h, int(ks), int(stride), *a), 'vbx_resnet_conv')
+    return _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad)
 
 
 def resnet_conv_gemm(ctx: 'Context', gemm, x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
     """resnet_conv in either mode (vbx_resnet_conv_gemm; gemm 'exact' or 'split').  -> (y, guard, unwritten, amax_y [n]: max |y|
     over the finite outputs of every image as the split kernel records it for its consumer; zeros in the exact mode)."""
-    x, w, bias, res = _f32(x), _f32(w), _f32(bias), _f32(res)
-    n, H, W, Cin = x.shape
-    Cout = w.shape[1]
-    s = max(int(stride), 1)
-    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-    count = n * Ho * Wo * Cout
-    assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (res is None or res.size == count)
-    bn, bm = tile or (0, 0)
-    buf = _guarded(count, pad)
+    n = len(x)
     amax = np.zeros(max(n, 1), dtype=np.float32)
-    ctx.check(ctx._lib.vbx_resnet_conv_gemm(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), n, H, W, Cin, Cout, _ptr(x), _ptr(w),
-                                            _ptr(bias), _ptr(res), int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad),
-                                            _ptr(amax)), 'vbx_resnet_conv_gemm')
-    y, guard, unwritten = _unguard(buf, count, pad)
-    return y.reshape(n, Ho, Wo, Cout), guard, unwritten, amax[:n]
+
+    def call(*a):
+        ctx.check(ctx._lib.vbx_resnet_conv_gemm(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), *a, _ptr(amax)), 'vbx_resnet_conv_gemm')
+    return _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad) + (amax[:n],)
 
 
 def resnet_split_weights(w):

@@ -11,13 +11,25 @@ struct RnConv {
     size_t wf = 0, we = 0;                                     // split mode: offsets (h8 units, ints) of the fragments and exponents
 };
 
+// one convolution of the launch sequence of a run (rn_plan)
+enum RnBuf { RN_X0, RN_X1, RN_T1, RN_T2, RN_SC, RN_NBUF };     // the block outputs (ping-pong), conv1 / conv2 outputs, the shortcut
+struct RnPlanStep {
+    int conv;                                                  // index into vbx_resnet::convs
+    int in, out, res;                                          // RnBuf; res: RN_NBUF for none
+    int H, W, relu;                                            // the input's size
+    int ain, aout;                                             // split mode: the max |.| slots of its input and (or -1) its output
+    int stage;                                                 // 0 .. 3: layer1 .. layer4 (the events)
+};
+
 struct vbx_resnet {
     vbx_ctx* ctx = nullptr;
     int E = 0, Ep = 0;                                         // embedding width, padded to 32 columns on the device
     std::vector<RnConv> convs;                                 // [0] the stem, then 3 or 4 per block
+    std::vector<RnPlanStep> plan;                              // the launch sequence at plan_T frames
+    int plan_T = 0;
     float *d_par = nullptr, *d_emb_w = nullptr, *d_emb_b = nullptr;
-    float *d_in = nullptr, *d_x[2] = {}, *d_t1 = nullptr, *d_t2 = nullptr, *d_sc = nullptr, *d_pool = nullptr, *d_out = nullptr;
-    size_t cap_in = 0, cap_x[2] = {}, cap_t1 = 0, cap_t2 = 0, cap_sc = 0, cap_pool = 0, cap_out = 0;
+    float *d_in = nullptr, *d_buf[RN_NBUF] = {}, *d_pool = nullptr, *d_out = nullptr;
+    size_t cap_in = 0, cap_buf[RN_NBUF] = {}, cap_pool = 0, cap_out = 0;
     hipEvent_t ev[7] = {};                                     // stem | layer1 | layer2 | layer3 | layer4 | pool + embedding
     // split mode (vbx_resnet_split.hpp): the weights a second time as f16 pairs in fragment order, their per-channel
     // exponents, and one max |y| slot per window for every tensor a split convolution reads
@@ -28,11 +40,22 @@ struct vbx_resnet {
     size_t cap_amax = 0;
 };
 
-constexpr int RN_AMAX_SLOTS = 1 + 3 * (3 + 4 + 23 + 3);        // the stem's output, then conv1, conv2 and the output of every block
-
-static const int RN_BLOCKS[4] = {3, 4, 23, 3}, RN_PLANES[4] = {32, 64, 128, 256}, RN_STRIDE[4] = {1, 2, 2, 2};
+constexpr int RN_BLOCKS[4] = {3, 4, 23, 3}, RN_PLANES[4] = {32, 64, 128, 256}, RN_STRIDE[4] = {1, 2, 2, 2};
+constexpr int RN_NBLOCKS = RN_BLOCKS[0] + RN_BLOCKS[1] + RN_BLOCKS[2] + RN_BLOCKS[3];
+constexpr int RN_AMAX_SLOTS = 1 + 3 * RN_NBLOCKS;              // the stem's output, then conv1, conv2 and the output of every block
 
 static inline int rn_out(int n, int stride) { return (n - 1) / stride + 1; }
+
+// the Bottleneck blocks in network order: f(stage, Cin, planes, stride, first of its stage).  The stride sits on conv2; the
+// first block of a stage has the shortcut convolution.
+template <class F> static void rn_for_blocks(F f) {
+    int cin = 32;
+    for (int L = 0; L < 4; ++L)
+        for (int i = 0; i < RN_BLOCKS[L]; ++i) {
+            f(L, cin, RN_PLANES[L], i == 0 ? RN_STRIDE[L] : 1, i == 0);
+            cin = 4 * RN_PLANES[L];
+        }
+}
 
 // the network's convolutions in blob order; returns the number of f32 parameters before the embedding
 static size_t rn_layout(std::vector<RnConv>& convs) {
@@ -43,60 +66,77 @@ static size_t rn_layout(std::vector<RnConv>& convs) {
         convs.push_back(c);
     };
     add(3, 1, 1, 32);
-    int cin = 32;
-    for (int L = 0; L < 4; ++L)
-        for (int i = 0; i < RN_BLOCKS[L]; ++i) {
-            const int planes = RN_PLANES[L], s = i == 0 ? RN_STRIDE[L] : 1;
-            add(1, 1, cin, planes);
-            add(3, s, planes, planes);
-            add(1, 1, planes, 4 * planes);
-            if (i == 0) add(1, s, cin, 4 * planes);
-            cin = 4 * planes;
-        }
+    rn_for_blocks([&](int, int cin, int planes, int s, bool first) {
+        add(1, 1, cin, planes);
+        add(3, s, planes, planes);
+        add(1, 1, planes, 4 * planes);
+        if (first) add(1, s, cin, 4 * planes);
+    });
     return off;
 }
 
-template <int KS, int S>
-static void rn_launch_ks(hipStream_t st, int BN, int BM, const float* x, const float* w, const float* b, const float* res,
-                         float* y, int H, int W, int Cin, int Ho, int Wo, int Cout, long long M, int relu) {
-    const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(Cout / BN)), blk(256);
-    if (BN == 128 && BM == 64)
-        hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 128, 64>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (BN == 128)
-        hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 128, 128>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (BN == 64 && BM == 64)
-        hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 64, 64>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (BN == 64)
-        hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 64, 128>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else
-        hipLaunchKernelGGL((resnet_conv_kernel<KS, S, 32, 128>), grid, blk, 0, st, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
+// the convolutions of layer1 .. layer4 at T frames in launch order: per block conv1, conv2, the shortcut (from the block's
+// input), conv3 + residual.  Slots: 3 blk the block's input, then conv1, conv2, the output.
+static std::vector<RnPlanStep> rn_plan(int T) {
+    std::vector<RnPlanStep> plan;
+    int H = RN_MEL, W = T, k = 1, x = RN_X0, s0 = 0;
+    rn_for_blocks([&](int L, int, int, int s, bool first) {
+        const int y = x == RN_X0 ? RN_X1 : RN_X0;
+        plan.push_back({k, x, RN_T1, RN_NBUF, H, W, 1, s0, s0 + 1, L});
+        plan.push_back({k + 1, RN_T1, RN_T2, RN_NBUF, H, W, 1, s0 + 1, s0 + 2, L});
+        if (first) plan.push_back({k + 3, x, RN_SC, RN_NBUF, H, W, 0, s0, -1, L});
+        H = rn_out(H, s);
+        W = rn_out(W, s);
+        plan.push_back({k + 2, RN_T2, y, first ? RN_SC : x, H, W, 1, s0 + 2, s0 + 3, L});
+        k += first ? 4 : 3;
+        x = y;
+        s0 += 3;
+    });
+    return plan;
 }
 
-template <int KS, int S>
-static void rn_launch_split_ks(hipStream_t st, int BN, int BM, const float* x, const unsigned* ax, const vbx::h8* wf, const int* we,
-                               const float* b, const float* res, float* y, unsigned* ay, int H, int W, int Cin, int Ho, int Wo,
-                               int Cout, long long M, int relu) {
-    const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(Cout / BN)), blk(256);
-    if (BN == 128 && BM == 64)
-        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 128, 64>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (BN == 128)
-        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 128, 128>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (BN == 64 && BM == 64)
-        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 64, 64>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (BN == 64)
-        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 64, 128>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else
-        hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, 32, 128>), grid, blk, 0, st, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+// one call of a convolution kernel: n images H x W x Cin -> Ho x Wo x Cout (Cout a multiple of 32, Cin of 16).  Plain values.
+struct RnCall {
+    int ks, stride, H, W, Cin, Ho, Wo, Cout, relu;
+    long long M;
+    const float *x = nullptr, *w = nullptr, *b = nullptr, *res = nullptr;      // w: the exact mode's weights
+    float* y = nullptr;
+    const unsigned* ax = nullptr;                              // split mode: the max |.| slots of x and (or null) of y,
+    unsigned* ay = nullptr;
+    const vbx::h8* wf = nullptr;                               // the weights' fragments and exponents
+    const int* we = nullptr;
+};
+
+static RnCall rn_call(int ks, int stride, int n, int H, int W, int Cin, int Cout, int relu) {
+    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
+    return RnCall{ks, stride, H, W, Cin, Ho, Wo, Cout, relu, (long long)n * Ho * Wo};
 }
 
-// the split mode's launch of one tile (the same five BN x BM as the exact kernel)
-static void rn_launch_split(hipStream_t st, int ks, int stride, int BN, int BM, const float* x, const unsigned* ax, const vbx::h8* wf,
-                            const int* we, const float* b, const float* res, float* y, unsigned* ay, int H, int W, int Cin, int Ho,
-                            int Wo, int Cout, long long M, int relu) {
-    if (ks == 1 && stride == 1) rn_launch_split_ks<1, 1>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (ks == 1) rn_launch_split_ks<1, 2>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (stride == 1) rn_launch_split_ks<3, 1>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else rn_launch_split_ks<3, 2>(st, BN, BM, x, ax, wf, we, b, res, y, ay, H, W, Cin, Ho, Wo, Cout, M, relu);
+// the instantiations of both convolution kernels: every (KS, S) at every BN x BM tile
+constexpr int RN_KS_STRIDE[4][2] = {{1, 1}, {1, 2}, {3, 1}, {3, 2}};
+constexpr int RN_TILES[5][2] = {{128, 64}, {128, 128}, {64, 64}, {64, 128}, {32, 128}};
+
+static bool rn_tile_built(int bn, int bm) {
+    for (const auto& t : RN_TILES)
+        if (t[0] == bn && t[1] == bm) return true;
+    return false;
+}
+
+// launches c with the BN x BM tile in the exact or the split mode; false (nothing launched) where no such kernel is built
+template <int I = 0> static bool rn_launch(hipStream_t st, const RnCall& c, int BN, int BM, int mode) {
+    if constexpr (I < 20) {
+        constexpr int KS = RN_KS_STRIDE[I / 5][0], S = RN_KS_STRIDE[I / 5][1], bn = RN_TILES[I % 5][0], bm = RN_TILES[I % 5][1];
+        if (c.ks != KS || c.stride != S || BN != bn || BM != bm) return rn_launch<I + 1>(st, c, BN, BM, mode);
+        const dim3 grid((unsigned)((c.M + bm - 1) / bm), (unsigned)(c.Cout / bn)), blk(256);
+        if (mode == VBX_GEMM_SPLIT)
+            hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, bn, bm>), grid, blk, 0, st, c.x, c.ax, c.wf, c.we, c.b, c.res, c.y, c.ay,
+                               c.H, c.W, c.Cin, c.Ho, c.Wo, c.Cout, c.M, c.relu);
+        else
+            hipLaunchKernelGGL((resnet_conv_kernel<KS, S, bn, bm>), grid, blk, 0, st, c.x, c.w, c.b, c.res, c.y, c.H, c.W, c.Cin, c.Ho,
+                               c.Wo, c.Cout, c.M, c.relu);
+        return true;
+    }
+    return false;
 }
 
 // max |x| per window of n windows of per_window floats (a multiple of 4) into amax[n], zeroed beforehand
@@ -142,22 +182,21 @@ static void rn_tile(long long M, int Cout, int* bn, int* bm) {
     *bm = *bn >= 64 && (M + 127) / 128 * (Cout / *bn) < 1024 ? 64 : 128;
 }
 
-static void rn_launch(hipStream_t st, int ks, int stride, int BN, int BM, const float* x, const float* w, const float* b,
-                      const float* res, float* y, int H, int W, int Cin, int Ho, int Wo, int Cout, long long M, int relu) {
-    if (ks == 1 && stride == 1) rn_launch_ks<1, 1>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (ks == 1) rn_launch_ks<1, 2>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else if (stride == 1) rn_launch_ks<3, 1>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
-    else rn_launch_ks<3, 2>(st, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
+// one convolution at the dispatcher's tile
+static bool rn_conv(hipStream_t st, const RnCall& c, int mode) {
+    int BN, BM;
+    rn_tile(c.M, c.Cout, &BN, &BM);
+    return rn_launch(st, c, BN, BM, mode);
 }
 
-// one convolution of n images H x W x Cin -> Ho x Wo x Cout (Cout a multiple of 32, Cin of 16)
-static void rn_conv(hipStream_t st, int ks, int stride, const float* x, const float* w, const float* b, const float* res, float* y,
-                    int n, int H, int W, int Cin, int Cout, int relu) {
-    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
-    const long long M = (long long)n * Ho * Wo;
-    int BN, BM;
-    rn_tile(M, Cout, &BN, &BM);
-    rn_launch(st, ks, stride, BN, BM, x, w, b, res, y, H, W, Cin, Ho, Wo, Cout, M, relu);
+// the split mode needs a library whose device code went through the ISA audit (vbx_amd/build.py)
+static int rn_check_gemm(vbx_ctx* ctx, const char* name, int gemm) {
+    if (gemm != VBX_GEMM_EXACT && gemm != VBX_GEMM_SPLIT) FAIL(ctx, VBX_ERR_INVALID, "%s: gemm must be VBX_GEMM_EXACT or VBX_GEMM_SPLIT", name);
+#ifdef VBX_ISA_UNAUDITED
+    if (gemm == VBX_GEMM_SPLIT)
+        FAIL(ctx, VBX_ERR_UNSUPPORTED, "%s: VBX_GEMM_SPLIT: this library was built without the ISA audit (vbx_amd/build.py); rebuild with llvm-objdump available", name);
+#endif
+    return VBX_OK;
 }
 
 // ---- step-level entry points: one kernel of the network on host arrays (the kernel tests) ----
@@ -171,22 +210,19 @@ struct RnStep {
         (void)hipStreamSynchronize(ctx->stream);
         for (float* p : blocks) ctx_free(ctx, p);
     }
-    int up(const float* host, size_t count, float** dev) {
+    template <class T> int up(const float* host, size_t count, T** dev) {     // (a null host array: a null device one)
         *dev = nullptr;
-        if (!host) return VBX_OK;
-        const int rc = dmalloc(ctx, dev, count);
-        if (rc != VBX_OK) return rc;
-        blocks.push_back(*dev);
-        HIPCHK(ctx, hipMemcpyAsync(*dev, host, sizeof(float) * count, hipMemcpyHostToDevice, ctx->stream));
-        return VBX_OK;
+        return host ? up_bytes(host, sizeof(float) * count, dev) : VBX_OK;
     }
-    int up_bytes(const void* host, size_t bytes, void** dev) {
+    template <class T> int up_bytes(const void* host, size_t bytes, T** dev) {   // (a null host array: zeros)
+        void* p = nullptr;
         *dev = nullptr;
-        const int rc = dmalloc_bytes(ctx, dev, std::max<size_t>(bytes, 4));
+        const int rc = dmalloc_bytes(ctx, &p, std::max<size_t>(bytes, 4));
         if (rc != VBX_OK) return rc;
-        blocks.push_back((float*)*dev);
-        if (host) HIPCHK(ctx, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        else HIPCHK(ctx, hipMemsetAsync(*dev, 0, bytes, ctx->stream));
+        blocks.push_back((float*)p);
+        *dev = (T*)p;
+        if (host) HIPCHK(ctx, hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        else HIPCHK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
         return VBX_OK;
     }
     // the kernel has been launched: wait for it and bring the whole in/out buffer back
@@ -209,10 +245,10 @@ int vbx_resnet_destroy(vbx_resnet* net) {
     vbx_ctx* ctx = net->ctx;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : {(void*)net->d_par, (void*)net->d_emb_w, (void*)net->d_emb_b, (void*)net->d_in, (void*)net->d_x[0],
-                    (void*)net->d_x[1], (void*)net->d_t1, (void*)net->d_t2, (void*)net->d_sc, (void*)net->d_pool, (void*)net->d_out,
-                    (void*)net->d_wf, (void*)net->d_we, (void*)net->d_amax})
+    for (void* p : {(void*)net->d_par, (void*)net->d_emb_w, (void*)net->d_emb_b, (void*)net->d_in, (void*)net->d_pool,
+                    (void*)net->d_out, (void*)net->d_wf, (void*)net->d_we, (void*)net->d_amax})
         ctx_free(ctx, p);
+    for (float* p : net->d_buf) ctx_free(ctx, p);
     for (auto& e : net->ev)
         if (e) (void)hipEventDestroy(e);
     delete net;
@@ -300,26 +336,20 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
     if (!x || !out || n <= 0 || T <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // workspace for (n, T): every block output (ping-pong), the conv1 / conv2 outputs and the shortcut, at their largest
-    size_t mx = (size_t)n * RN_MEL * T * 32, mt1 = 0, mt2 = 0, msc = 0;
-    {
-        int H = RN_MEL, W = T;
-        for (int L = 0; L < 4; ++L)
-            for (int i = 0; i < RN_BLOCKS[L]; ++i) {
-                const int planes = RN_PLANES[L], s = i == 0 ? RN_STRIDE[L] : 1, Ho = rn_out(H, s), Wo = rn_out(W, s);
-                mt1 = std::max(mt1, (size_t)n * H * W * planes);
-                mt2 = std::max(mt2, (size_t)n * Ho * Wo * planes);
-                mx = std::max(mx, (size_t)n * Ho * Wo * 4 * planes);
-                if (i == 0) msc = std::max(msc, (size_t)n * Ho * Wo * 4 * planes);
-                H = Ho;
-                W = Wo;
-            }
+    if (net->plan_T != T) {
+        net->plan = rn_plan(T);
+        net->plan_T = T;
     }
-    int rc = fb_reserve(ctx, &net->d_x[0], &net->cap_x[0], mx);
-    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_x[1], &net->cap_x[1], mx);
-    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_t1, &net->cap_t1, mt1);
-    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_t2, &net->cap_t2, mt2);
-    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_sc, &net->cap_sc, msc);
+    // workspace for (n, T): every buffer at the largest output a step writes to it, the ping-pong pair alike (x[0] also
+    // takes the stem's output)
+    size_t need[RN_NBUF] = {(size_t)n * RN_MEL * T * 32};
+    for (const RnPlanStep& s : net->plan) {
+        const RnConv& c = net->convs[s.conv];
+        need[s.out] = std::max(need[s.out], (size_t)n * rn_out(s.H, c.stride) * rn_out(s.W, c.stride) * c.cout);
+    }
+    need[RN_X0] = need[RN_X1] = std::max(need[RN_X0], need[RN_X1]);
+    int rc = VBX_OK;
+    for (int i = 0; i < RN_NBUF && rc == VBX_OK; ++i) rc = fb_reserve(ctx, &net->d_buf[i], &net->cap_buf[i], need[i]);
     if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_pool, &net->cap_pool, (size_t)n * RN_POOL);
     if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_out, &net->cap_out, (size_t)n * net->Ep);
     if (rc == VBX_OK && !x_on_device) rc = fb_reserve(ctx, &net->d_in, &net->cap_in, (size_t)n * RN_MEL * T);
@@ -328,21 +358,7 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
     if (rc != VBX_OK) return rc;
     net->gemm_last = net->gemm;
     if (split) HIPCHK(ctx, hipMemsetAsync(net->d_amax, 0, sizeof(unsigned) * RN_AMAX_SLOTS * (size_t)n, st));
-    // one convolution in the run's mode; ax / ay: the max |.| slots of its input and (or null) of its output
-    auto conv = [&](const RnConv& c, const float* xs, const unsigned* ax, const float* res, float* ys, unsigned* ay, int H, int W,
-                    int relu) {
-        if (split) {
-            const int Ho = rn_out(H, c.stride), Wo = rn_out(W, c.stride);
-            const long long M = (long long)n * Ho * Wo;
-            int BN, BM;
-            rn_tile(M, c.cout, &BN, &BM);
-            rn_launch_split(st, c.ks, c.stride, BN, BM, xs, ax, net->d_wf + c.wf, net->d_we + c.we, net->d_par + c.b, res, ys, ay, H,
-                            W, c.cin, Ho, Wo, c.cout, M, relu);
-        } else {
-            rn_conv(st, c.ks, c.stride, xs, net->d_par + c.w, net->d_par + c.b, res, ys, n, H, W, c.cin, c.cout, relu);
-        }
-    };
-    auto slot = [&](int s) { return split ? net->d_amax + (size_t)s * n : nullptr; };
+    auto slot = [&](int s) { return split && s >= 0 ? net->d_amax + (size_t)s * n : nullptr; };
     const float* xin = x;
     if (!x_on_device) {
         HIPCHK(ctx, hipMemcpyAsync(net->d_in, x, sizeof(float) * (size_t)n * RN_MEL * T, hipMemcpyHostToDevice, st));
@@ -353,38 +369,39 @@ int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_
     HIPCHK(ctx, hipEventRecord(net->ev[0], st));
     const long long tot0 = (long long)n * RN_MEL * T * 32;
     hipLaunchKernelGGL(resnet_stem_kernel, dim3((unsigned)((tot0 + 255) / 256)), dim3(256), 0, st, xin, P + c0.w, P + c0.b,
-                       net->d_x[0], T, tot0);
-    if (split) rn_amax(st, net->d_x[0], n, (long long)RN_MEL * T * 32, slot(0));     // (the stem itself stays as it is)
+                       net->d_buf[RN_X0], T, tot0);
+    if (split) rn_amax(st, net->d_buf[RN_X0], n, (long long)RN_MEL * T * 32, slot(0));   // (the stem itself stays as it is)
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(net->ev[1], st));
-    int cur = 0, H = RN_MEL, W = T, k = 1, blk = 0;
-    for (int L = 0; L < 4; ++L) {
-        for (int i = 0; i < RN_BLOCKS[L]; ++i) {
-            const RnConv &a = net->convs[k], &b = net->convs[k + 1], &c = net->convs[k + 2];
-            const float* xs = net->d_x[cur];
-            float* ys = net->d_x[cur ^ 1];
-            const int s0 = 3 * blk;                            // slots: s0 the block's input, then conv1, conv2, the output
-            conv(a, xs, slot(s0), nullptr, net->d_t1, slot(s0 + 1), H, W, 1);
-            conv(b, net->d_t1, slot(s0 + 1), nullptr, net->d_t2, slot(s0 + 2), H, W, 1);
-            const float* res = xs;
-            if (i == 0) {
-                conv(net->convs[k + 3], xs, slot(s0), nullptr, net->d_sc, nullptr, H, W, 0);
-                res = net->d_sc;
-            }
-            H = rn_out(H, b.stride);
-            W = rn_out(W, b.stride);
-            conv(c, net->d_t2, slot(s0 + 2), res, ys, slot(s0 + 3), H, W, 1);
-            HIPCHK(ctx, hipGetLastError());
-            k += i == 0 ? 4 : 3;
-            cur ^= 1;
-            ++blk;
-        }
-        HIPCHK(ctx, hipEventRecord(net->ev[2 + L], st));
+    int stage = 0;
+    for (const RnPlanStep& s : net->plan) {
+        if (s.stage != stage) HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
+        stage = s.stage;
+        const RnConv& c = net->convs[s.conv];
+        RnCall call = rn_call(c.ks, c.stride, n, s.H, s.W, c.cin, c.cout, s.relu);
+        call.x = net->d_buf[s.in];
+        call.w = P + c.w;
+        call.b = P + c.b;
+        call.res = s.res == RN_NBUF ? nullptr : net->d_buf[s.res];
+        call.y = net->d_buf[s.out];
+        call.ax = slot(s.ain);
+        call.wf = net->d_wf + c.wf;
+        call.we = net->d_we + c.we;
+        call.ay = slot(s.aout);
+        if (!rn_conv(st, call, net->gemm)) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run: no kernel for convolution %d", s.conv);
+        HIPCHK(ctx, hipGetLastError());
     }
+    HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
+    const RnPlanStep& last = net->plan.back();
     const long long totp = (long long)n * RN_H4 * RN_C4;
-    hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((totp + 255) / 256)), dim3(256), 0, st, net->d_x[cur], net->d_pool, W,
-                       totp);
-    rn_conv(st, 1, 1, net->d_pool, net->d_emb_w, net->d_emb_b, nullptr, net->d_out, n, 1, 1, RN_POOL, net->Ep, 0);
+    hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((totp + 255) / 256)), dim3(256), 0, st, net->d_buf[last.out], net->d_pool,
+                       last.W, totp);
+    RnCall emb = rn_call(1, 1, n, 1, 1, RN_POOL, net->Ep, 0);  // (exact in both modes)
+    emb.x = net->d_pool;
+    emb.w = net->d_emb_w;
+    emb.b = net->d_emb_b;
+    emb.y = net->d_out;
+    rn_conv(st, emb, VBX_GEMM_EXACT);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(net->ev[6], st));
     HIPCHK(ctx, hipMemcpy2DAsync(out, sizeof(float) * net->E, net->d_out, sizeof(float) * net->Ep, sizeof(float) * net->E, (size_t)n,
@@ -403,12 +420,8 @@ int vbx_resnet_times(vbx_resnet* net, float* ms) {
 
 int vbx_resnet_set_gemm(vbx_resnet* net, int gemm) {
     if (!net) return VBX_ERR_INVALID;
-    if (gemm != VBX_GEMM_EXACT && gemm != VBX_GEMM_SPLIT)
-        FAIL(net->ctx, VBX_ERR_INVALID, "vbx_resnet_set_gemm takes VBX_GEMM_EXACT or VBX_GEMM_SPLIT");
-#ifdef VBX_ISA_UNAUDITED
-    if (gemm == VBX_GEMM_SPLIT)
-        FAIL(net->ctx, VBX_ERR_UNSUPPORTED, "VBX_GEMM_SPLIT: this library was built without the ISA audit (vbx_amd/build.py); rebuild with llvm-objdump available");
-#endif
+    const int rc = rn_check_gemm(net->ctx, "vbx_resnet_set_gemm", gemm);
+    if (rc != VBX_OK) return rc;
     net->gemm = gemm;
     return VBX_OK;
 }
@@ -423,10 +436,7 @@ int vbx_resnet_split_weights(int32_t K, int32_t Cout, const float* w, uint16_t* 
 
 int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm) {
     if (!bn || !bm || M <= 0 || Cout <= 0 || Cout % 32 != 0) return VBX_ERR_INVALID;
-    int BN, BM;
-    rn_tile(M, Cout, &BN, &BM);
-    *bn = BN;
-    *bm = BM;
+    rn_tile(M, Cout, bn, bm);
     return VBX_OK;
 }
 
@@ -435,11 +445,8 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
                         int32_t Cin, int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu,
                         int32_t bn, int32_t bm, float* y, int64_t pad, float* amax_y) {
     if (!ctx) return VBX_ERR_INVALID;
-    if (gemm != VBX_GEMM_EXACT && gemm != VBX_GEMM_SPLIT) FAIL(ctx, VBX_ERR_INVALID, "%s: gemm must be VBX_GEMM_EXACT or VBX_GEMM_SPLIT", name);
-#ifdef VBX_ISA_UNAUDITED
-    if (gemm == VBX_GEMM_SPLIT)
-        FAIL(ctx, VBX_ERR_UNSUPPORTED, "%s: VBX_GEMM_SPLIT: this library was built without the ISA audit (vbx_amd/build.py)", name);
-#endif
+    int rc = rn_check_gemm(ctx, name, gemm);
+    if (rc != VBX_OK) return rc;
     if (!x || !w || !bias || !y) FAIL(ctx, VBX_ERR_INVALID, "%s: x, w, bias and y must not be NULL", name);
     if (n <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || pad < 0)
         FAIL(ctx, VBX_ERR_INVALID, "%s: n = %d, H = %d, W = %d, Cin = %d, Cout = %d must be positive, pad = %lld not negative", name,
@@ -447,48 +454,43 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
     if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2))
         FAIL(ctx, VBX_ERR_INVALID, "%s: kernel size %d stride %d: built for 1 or 3 at stride 1 or 2", name, ks, stride);
     if (Cin % RN_BK != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cin = %d is not a multiple of %d", name, Cin, RN_BK);
-    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
-    const long long M = (long long)n * Ho * Wo;
+    RnCall c = rn_call(ks, stride, n, H, W, Cin, Cout, relu ? 1 : 0);
     int BN = bn, BM = bm;
     if (bn == 0 && bm == 0) {
         if (Cout % 32 != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of 32", name, Cout);
-        rn_tile(M, Cout, &BN, &BM);
+        rn_tile(c.M, Cout, &BN, &BM);
     } else {
-        const bool built = (bn == 128 && bm == 64) || (bn == 128 && bm == 128) || (bn == 64 && bm == 64) || (bn == 64 && bm == 128) ||
-                           (bn == 32 && bm == 128);
-        if (!built) FAIL(ctx, VBX_ERR_INVALID, "%s: no %d x %d tile (BN x BM: 128 x 64, 128 x 128, 64 x 64, 64 x 128, 32 x 128)", name, bn, bm);
+        if (!rn_tile_built(bn, bm)) FAIL(ctx, VBX_ERR_INVALID, "%s: no BN x BM = %d x %d tile is built (RN_TILES)", name, bn, bm);
         if (Cout % bn != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of the tile's BN = %d", name, Cout, bn);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RnStep s(ctx);
-    const size_t ny = (size_t)M * Cout + 2 * (size_t)pad;
-    float *dx, *dw = nullptr, *db, *dr, *dy;
-    int rc = s.up(x, (size_t)n * H * W * Cin, &dx);
-    if (rc == VBX_OK) rc = s.up(bias, (size_t)Cout, &db);
-    if (rc == VBX_OK) rc = s.up(res, (size_t)M * Cout, &dr);
+    const size_t ny = (size_t)c.M * Cout + 2 * (size_t)pad;
+    float* dy;
+    rc = s.up(x, (size_t)n * H * W * Cin, &c.x);
+    if (rc == VBX_OK) rc = s.up(bias, (size_t)Cout, &c.b);
+    if (rc == VBX_OK) rc = s.up(res, (size_t)c.M * Cout, &c.res);
     if (rc == VBX_OK) rc = s.up(y, ny, &dy);
+    if (rc == VBX_OK && gemm == VBX_GEMM_EXACT) rc = s.up(w, (size_t)ks * ks * Cin * Cout, &c.w);
     if (rc != VBX_OK) return rc;
-    if (gemm == VBX_GEMM_EXACT) {
-        rc = s.up(w, (size_t)ks * ks * Cin * Cout, &dw);
-        if (rc != VBX_OK) return rc;
-        rn_launch(ctx->stream, ks, stride, BN, BM, dx, dw, db, dr, dy + pad, H, W, Cin, Ho, Wo, Cout, M, relu ? 1 : 0);
-        return s.down(name, y, dy, ny);
-    }
+    c.y = dy + pad;
     const int K = ks * ks * Cin;
-    std::vector<uint16_t> wf((size_t)K * Cout * 2);
-    std::vector<int32_t> we(Cout);
-    rn_split_weights(w, K, Cout, wf.data(), we.data());
-    void *dwf, *dwe, *dax, *day;
-    rc = s.up_bytes(wf.data(), sizeof(uint16_t) * wf.size(), &dwf);
-    if (rc == VBX_OK) rc = s.up_bytes(we.data(), sizeof(int32_t) * we.size(), &dwe);
-    if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &dax);
-    if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &day);
-    if (rc != VBX_OK) return rc;
-    rn_amax(ctx->stream, dx, n, (long long)H * W * Cin, (unsigned*)dax);
-    rn_launch_split(ctx->stream, ks, stride, BN, BM, dx, (const unsigned*)dax, (const vbx::h8*)dwf, (const int*)dwe, db, dr, dy + pad,
-                    (unsigned*)day, H, W, Cin, Ho, Wo, Cout, M, relu ? 1 : 0);
-    if (amax_y) HIPCHK(ctx, hipMemcpyAsync(amax_y, day, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    return s.down(name, y, dy, ny);                            // (wf and we outlive the copies: down() synchronizes)
+    std::vector<uint16_t> wf(gemm == VBX_GEMM_SPLIT ? (size_t)K * Cout * 2 : 0);     // (wf and we outlive the copies: down()
+    std::vector<int32_t> we(Cout);                                                   // synchronizes)
+    if (gemm == VBX_GEMM_SPLIT) {
+        rn_split_weights(w, K, Cout, wf.data(), we.data());
+        unsigned* dax;
+        rc = s.up_bytes(wf.data(), sizeof(uint16_t) * wf.size(), &c.wf);
+        if (rc == VBX_OK) rc = s.up_bytes(we.data(), sizeof(int32_t) * we.size(), &c.we);
+        if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &dax);
+        if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &c.ay);
+        if (rc != VBX_OK) return rc;
+        rn_amax(ctx->stream, c.x, n, (long long)H * W * Cin, dax);
+        c.ax = dax;
+    }
+    if (!rn_launch(ctx->stream, c, BN, BM, gemm)) FAIL(ctx, VBX_ERR_INVALID, "%s: no kernel for this convolution", name);
+    if (c.ay && amax_y) HIPCHK(ctx, hipMemcpyAsync(amax_y, c.ay, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    return s.down(name, y, dy, ny);
 }
 
 int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,

@@ -30,6 +30,9 @@ using f32x16 = float __attribute__((ext_vector_type(16)));
 // relu(v) with NaN kept: (v < 0) is false for NaN.  fmaxf(v, 0) would return 0.
 __device__ __forceinline__ float rn_relu(float v) { return v < 0.0f ? 0.0f : v; }
 
+// the row of element r of a lane's 32 x 32 D fragment (its column is lane & 31); kh = lane >> 5
+__device__ __forceinline__ int rn_drow(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
+
 // y[m][n] = act(sum_k A[m][k] W[k][n] + bias[n] (+ res[m][n])), A[m][(r KS + s) Cin + c] = x[b][ho S - P + r][wo S - P + s][c].
 // w [K][Cout] (row k = tap r KS + s, input channel c), Cout a multiple of BN; grid (ceil(M / BM), Cout / BN).
 template <int KS, int S, int BN, int BM>
@@ -128,14 +131,13 @@ __global__ __launch_bounds__(256) void resnet_conv_kernel(const float* __restric
             __syncthreads();
         }
     }
-    // D: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int j = 0; j < NACC; ++j) {
         const int n = n0 + col0 + 32 * j + i;
         const float bn = bias[n];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long long m = m0 + row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const long long m = m0 + row0 + rn_drow(r, kh);
             if (m < M) {
                 const long long o = m * Cout + n;
                 float v = acc[j][r] + bn;

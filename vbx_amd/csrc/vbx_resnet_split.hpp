@@ -166,7 +166,6 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
             lds_barrier();
         }
     }
-    // D: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     const int row0 = wrb * 32;
     int am[16];
 #pragma unroll
@@ -180,12 +179,12 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
         float rv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const long long m = m0 + row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const long long m = m0 + row0 + rn_drow(r, kh);
             rv[r] = res && m < M ? res[m * Cout + n] : 0.0f;
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rl = row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const int rl = row0 + rn_drow(r, kh);
             const long long m = m0 + rl;
             if (m < M) {
                 const long long o = m * Cout + n;
@@ -211,7 +210,7 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int t = allreduce_max<32>(am[r]);
-                const long long m = m0 + row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const long long m = m0 + row0 + rn_drow(r, kh);
                 if (i == 0 && m < M && t > 0) atomicMax(amax_y + m / hw, (unsigned)t);
             }
         }

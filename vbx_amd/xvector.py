@@ -3,6 +3,7 @@
     load_checkpoint         torch.load(path)['state_dict'] (predict.py's ``--weights`` format), every tensor the network
                             needs checked by name and shape
     synthetic_state_dict    a seeded, well-scaled checkpoint (numpy only): tests, golden data, benchmarks
+    blocks, walk            the block structure, written once; every convolution with the size of its input at T frames
     fold                    BatchNorm folded into each convolution in f64, packed in the order libvbx_hip.so reads
     forward_reference       the network in f64 on the CPU from the raw checkpoint (torch.nn.functional): the referee
     forward_folded          the same from the folded, packed parameters (checks fold; run_folded: on any torch device)
@@ -30,19 +31,40 @@ POOL_DIM = 2 * H4 * C4                                # 16384
 BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
 
 
-def conv_specs():
-    """Every convolution in the order the device reads them: (conv key, BN key, kernel size, stride, Cin, Cout)."""
-    out = [('conv1', 'bn1', 3, 1, 1, M_CHANNELS)]
+def _out(n, stride):
+    return (n - 1) // stride + 1
+
+
+def blocks():
+    """The 33 Bottleneck blocks in network order: (key prefix, Cin, planes, stride, first of its stage).  The stride sits on
+    conv2; the first block of a stage also has the shortcut convolution (stride 2, or 32 != 128 in layer1)."""
     cin = M_CHANNELS
     for L, (n, planes, stride) in enumerate(zip(BLOCKS, PLANES, STRIDES), 1):
         for i in range(n):
-            p, s = f'layer{L}.{i}.', stride if i == 0 else 1
-            out += [(p + 'conv1', p + 'bn1', 1, 1, cin, planes), (p + 'conv2', p + 'bn2', 3, s, planes, planes),
-                    (p + 'conv3', p + 'bn3', 1, 1, planes, EXPANSION * planes)]
-            if i == 0:                                # stride 2, or 32 != 128 in layer1
-                out.append((p + 'shortcut.0', p + 'shortcut.1', 1, s, cin, EXPANSION * planes))
+            yield f'layer{L}.{i}.', cin, planes, stride if i == 0 else 1, i == 0
             cin = EXPANSION * planes
+
+
+def conv_specs():
+    """Every convolution in the order the device reads them: (conv key, BN key, kernel size, stride, Cin, Cout)."""
+    out = [('conv1', 'bn1', 3, 1, 1, M_CHANNELS)]
+    for p, cin, planes, s, first in blocks():
+        out += [(p + 'conv1', p + 'bn1', 1, 1, cin, planes), (p + 'conv2', p + 'bn2', 3, s, planes, planes),
+                (p + 'conv3', p + 'bn3', 1, 1, planes, EXPANSION * planes)]
+        if first:
+            out.append((p + 'shortcut.0', p + 'shortcut.1', 1, s, cin, EXPANSION * planes))
     return out
+
+
+def walk(T: int):
+    """(spec, H, W) of every convolution after the stem at T frames, in conv_specs() order: H x W is what it reads."""
+    specs, k, H, W = conv_specs(), 1, FEAT_DIM, T
+    for _, _, _, s, first in blocks():
+        Ho, Wo = _out(H, s), _out(W, s)
+        for hw in ((H, W), (H, W), (Ho, Wo), (H, W))[:4 if first else 3]:
+            yield (specs[k],) + hw
+            k += 1
+        H, W = Ho, Wo
 
 
 def required_shapes(embed_dim: int) -> dict:
@@ -151,10 +173,23 @@ def fold(sd) -> np.ndarray:
     return np.concatenate(parts)
 
 
-def _pool_embed(out, ew, eb, torch):
-    mean = out.mean(dim=-1)
-    std = torch.sqrt((out * out).mean(dim=-1) - mean ** 2 + 1e-10)
-    return torch.cat([mean.flatten(1), std.flatten(1)], 1) @ ew.T + eb
+def _run_network(x, conv, embed, pool_dtype=None):
+    """The network's one loop: the stem, the 33 blocks, the statistics over time, the embedding.  conv(k, h, stride, relu,
+    res) applies convolution k of conv_specs() to h (+ res, then ReLU); the pooling sums in pool_dtype (None: h's own);
+    embed(mean, std) [B][1024][8] each -> [B][E]."""
+    import torch
+    with torch.no_grad():
+        h, k = conv(0, x[:, None], 1, True, None), 1
+        for _, _, _, s, first in blocks():
+            o = conv(k + 1, conv(k, h, 1, True, None), s, True, None)
+            sc = conv(k + 3, h, s, False, None) if first else h
+            h = conv(k + 2, o, 1, True, sc)                    # (conv3 comes before the shortcut in the parameter order)
+            k += 4 if first else 3
+        if pool_dtype is not None:
+            h = h.to(pool_dtype)
+        mean = h.mean(dim=-1)
+        std = torch.sqrt((h * h).mean(dim=-1) - mean ** 2 + 1e-10)
+        return embed(mean, std)
 
 
 def forward_reference(sd, x) -> np.ndarray:
@@ -163,23 +198,21 @@ def forward_reference(sd, x) -> np.ndarray:
     import torch.nn.functional as F
     sd = check_state_dict(sd)
     t = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)) for k, v in sd.items()}
+    specs = conv_specs()
 
-    def cbn(h, conv, bn, stride, pad):
-        h = F.conv2d(h, t[conv + '.weight'], stride=stride, padding=pad)
-        return F.batch_norm(h, t[bn + '.running_mean'], t[bn + '.running_var'], t[bn + '.weight'], t[bn + '.bias'],
-                            training=False, eps=BN_EPS)
+    def conv(k, h, stride, relu, res):
+        key, bn, ks = specs[k][:3]
+        h = F.conv2d(h, t[key + '.weight'], stride=stride, padding=ks // 2)
+        h = F.batch_norm(h, t[bn + '.running_mean'], t[bn + '.running_var'], t[bn + '.weight'], t[bn + '.bias'],
+                         training=False, eps=BN_EPS)
+        if res is not None:
+            h = h + res
+        return F.relu(h) if relu else h
 
-    with torch.no_grad():
-        h = torch.from_numpy(np.asarray(x, dtype=np.float64))[:, None]
-        h = F.relu(cbn(h, 'conv1', 'bn1', 1, 1))
-        for L, (n, stride) in enumerate(zip(BLOCKS, STRIDES), 1):
-            for i in range(n):
-                p, s = f'layer{L}.{i}.', stride if i == 0 else 1
-                o = F.relu(cbn(h, p + 'conv1', p + 'bn1', 1, 0))
-                o = F.relu(cbn(o, p + 'conv2', p + 'bn2', s, 1))
-                o = cbn(o, p + 'conv3', p + 'bn3', 1, 0)
-                h = F.relu(o + (cbn(h, p + 'shortcut.0', p + 'shortcut.1', s, 0) if i == 0 else h))
-        return _pool_embed(h, t['embedding.weight'], t['embedding.bias'], torch).numpy()
+    def embed(mean, std):
+        return torch.cat([mean.flatten(1), std.flatten(1)], 1) @ t['embedding.weight'].T + t['embedding.bias']
+
+    return _run_network(torch.from_numpy(np.asarray(x, dtype=np.float64)), conv, embed).numpy()
 
 
 def folded_tensors(params, embed_dim: int, device='cpu', dtype=None) -> list:
@@ -199,33 +232,25 @@ def folded_tensors(params, embed_dim: int, device='cpu', dtype=None) -> list:
     return [(w.to(device=device, dtype=dtype).contiguous(), b.to(device=device, dtype=dtype)) for w, b in out]
 
 
+def _embed_folded(tensors):
+    """embed() of _run_network for folded_tensors(): the pooled vector in the device's order (h 1024 + c)."""
+    import torch
+    ew, eb = tensors[-1]
+    return lambda mean, std: torch.cat([mean.transpose(1, 2).flatten(1), std.transpose(1, 2).flatten(1)], 1).to(ew.dtype) @ ew + eb
+
+
 def run_folded(tensors, x):
     """The network on folded_tensors(): x [B][64][T] tensor of their device and dtype -> [B][E]."""
-    import torch
     import torch.nn.functional as F
-    it = iter(tensors)
 
-    def conv(h, stride, relu, res=None):
-        w, b = next(it)
+    def conv(k, h, stride, relu, res):
+        w, b = tensors[k]
         h = F.conv2d(h, w, b, stride=stride, padding=w.shape[-1] // 2)
         if res is not None:
             h = h + res
         return F.relu(h) if relu else h
 
-    with torch.no_grad():
-        h = conv(x[:, None], 1, True)
-        for n, stride in zip(BLOCKS, STRIDES):
-            for i in range(n):
-                s = stride if i == 0 else 1
-                o = conv(conv(h, 1, True), s, True)
-                c3 = next(it)
-                sc = conv(h, s, False) if i == 0 else h
-                h = F.relu(F.conv2d(o, c3[0], c3[1]) + sc)
-        mean = h.mean(dim=-1)                                              # [B][1024][8]
-        std = torch.sqrt((h * h).mean(dim=-1) - mean ** 2 + 1e-10)
-        pooled = torch.cat([mean.transpose(1, 2).flatten(1), std.transpose(1, 2).flatten(1)], 1)   # (h 1024 + c)
-        ew, eb = next(it)
-        return pooled @ ew + eb
+    return _run_network(x, conv, _embed_folded(tensors))
 
 
 def forward_folded(params, embed_dim: int, x) -> np.ndarray:
@@ -295,18 +320,19 @@ def forward_split_emulated(params, embed_dim: int, x) -> np.ndarray:
     import torch
     import torch.nn.functional as F
     tens = folded_tensors(np.asarray(params, dtype=np.float32), embed_dim, dtype=torch.float32)
-    it = iter(tens)
 
-    def conv(h, stride, relu, res=None):
-        w, b = next(it)
-        cout, cin, k, _ = w.shape
-        wk = w.permute(2, 3, 1, 0).reshape(k * k * cin, cout).numpy()
+    def conv(k, h, stride, relu, res):
+        w, b = tens[k]
+        cout, cin, ks, _ = w.shape
+        if k == 0:                                                             # the stem stays exact
+            return F.relu(F.conv2d(h, w, b, padding=1))
+        wk = w.permute(2, 3, 1, 0).reshape(ks * ks * cin, cout).numpy()
         whi, wlo, we = split_terms(wk, np.fmax.reduce(np.abs(wk), axis=0)[None, :])
         hn = h.numpy()
         ahi, alo, ae = split_terms(hn, _finite_amax(hn.reshape(len(hn), -1), 1)[:, None, None, None])
-        back = lambda a: torch.from_numpy(a.astype(np.float32).reshape(k, k, cin, cout)).permute(3, 2, 0, 1).contiguous()
+        back = lambda a: torch.from_numpy(a.astype(np.float32).reshape(ks, ks, cin, cout)).permute(3, 2, 0, 1).contiguous()
         t = lambda a: torch.from_numpy(a.astype(np.float32))
-        kw = dict(stride=stride, padding=k // 2)
+        kw = dict(stride=stride, padding=ks // 2)
         acc = F.conv2d(t(alo), back(whi), **kw) + F.conv2d(t(ahi), back(wlo), **kw) + F.conv2d(t(ahi), back(whi), **kw)
         scale = np.ldexp(np.float32(1), -(ae.reshape(-1, 1, 1, 1) + we.reshape(1, -1, 1, 1))).astype(np.float32)
         y = acc * torch.from_numpy(scale) + b.reshape(1, -1, 1, 1)
@@ -314,25 +340,8 @@ def forward_split_emulated(params, embed_dim: int, x) -> np.ndarray:
             y = y + res
         return F.relu(y) if relu else y
 
-    with torch.no_grad():
-        w, b = next(it)
-        h = F.relu(F.conv2d(torch.from_numpy(np.asarray(x, dtype=np.float32))[:, None], w, b, padding=1))
-        for n, stride in zip(BLOCKS, STRIDES):
-            for i in range(n):
-                s = stride if i == 0 else 1
-                o = conv(conv(h, 1, True), s, True)
-                # (conv3 comes before the shortcut in the parameter order)
-                c3 = next(it)
-                sc = conv(h, s, False) if i == 0 else h
-                it, rest = iter([c3]), it
-                h = conv(o, 1, True, res=sc)
-                it = rest
-        hd = h.double()
-        mean = hd.mean(dim=-1)
-        std = torch.sqrt((hd * hd).mean(dim=-1) - mean ** 2 + 1e-10)
-        pooled = torch.cat([mean.transpose(1, 2).flatten(1), std.transpose(1, 2).flatten(1)], 1).float()
-        ew, eb = next(it)
-        return (pooled @ ew + eb).numpy()
+    x = torch.from_numpy(np.asarray(x, dtype=np.float32))
+    return _run_network(x, conv, _embed_folded(tens), pool_dtype=torch.float64).numpy()
 
 
 class ResNet101:
@@ -400,19 +409,8 @@ class ResNet101:
 
 def flops(T: int) -> dict:
     """Multiply-add FLOPs (2 per MAC) of one window of T frames, per stage."""
-    out, H, W = {'stem': 2 * 9 * M_CHANNELS * FEAT_DIM * T}, FEAT_DIM, T
-    specs = conv_specs()[1:]
-    k = 0
-    for L, (n, stride) in enumerate(zip(BLOCKS, STRIDES), 1):
-        f = 0
-        for i in range(n):
-            c1, c2, c3 = specs[k:k + 3]
-            s = c2[3]
-            Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-            f += 2 * H * W * c1[4] * c1[5] + 2 * Ho * Wo * 9 * c2[4] * c2[5] + 2 * Ho * Wo * c3[4] * c3[5]
-            if i == 0:
-                f += 2 * Ho * Wo * specs[k + 3][4] * specs[k + 3][5]
-            k += 4 if i == 0 else 3
-            H, W = Ho, Wo
-        out[f'layer{L}'] = f
+    out = {'stem': 2 * 9 * M_CHANNELS * FEAT_DIM * T}
+    for (key, _, ks, s, cin, cout), H, W in walk(T):
+        stage = key.partition('.')[0]                      # 'layer1' .. 'layer4'
+        out[stage] = out.get(stage, 0) + 2 * _out(H, s) * _out(W, s) * ks * ks * cin * cout
     return out
