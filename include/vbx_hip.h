@@ -94,6 +94,20 @@ extern "C" {
                                    ONE synchronize instead of 64 (ABI 7) */
 #define VBX_GEMM_EXACT 0
 #define VBX_GEMM_SPLIT 1
+#define VBX_OPT_STREAM_LOADS 16 /* cache policy of the loads of rho in the two fused per-chunk kernels of the split mode
+                                   (VBX_OPT_GEMM): VBX_STREAM_LOADS_ON fetches the f16 copies of rho with non-temporal loads
+                                   (every line of them is read once per launch), VBX_STREAM_LOADS_OFF with the default policy,
+                                   VBX_STREAM_LOADS_AUTO (default) picks ON where one copy of the x-vectors that iterate
+                                   together -- all sub-batches of a stream group, a shared rho counted once -- is larger than
+                                   the 256 MiB Infinity Cache (vbx_stream_loads_auto): below that a batch finds rho in the
+                                   caches again one iteration later and the default policy keeps it there.  64 recordings of
+                                   T = 10 000: 6-8 % of the step.  Where it is in effect chunk_post leaves the last level of
+                                   the boundary walk to a launch of its own (no FOLD).  Results do not depend on it, bit for
+                                   bit.  Ignored where the split kernels do not run: exact f32, fp64, S > 64
+                                   (vbx_batch_stream_loads_in_effect tells) */
+#define VBX_STREAM_LOADS_AUTO 0
+#define VBX_STREAM_LOADS_ON 1
+#define VBX_STREAM_LOADS_OFF 2
 #define VBX_OPT_FUSE 5          /* per-chunk fused kernels when the lattices fit in LDS: 0 none, 1 chunk_post,
                                    2 (default) chunk_post + chunk_loglik.  On the fused path the responsibilities are
                                    written once, when vbx_batch_run returns (they are not needed between iterations) */
@@ -221,6 +235,12 @@ int vbx_batch_stream_of(const vbx_batch* b, int rec);
  * recording cannot carry at 22 bits: vbx_split.hpp.  In a batch on several streams the guard acts per sub-batch and the
  * answer is VBX_GEMM_SPLIT only if every sub-batch multiplied that way). */
 int vbx_batch_gemm_in_effect(const vbx_batch* b);
+/* 1 if the per-chunk kernels of the last vbx_batch_run fetched rho with non-temporal loads (VBX_OPT_STREAM_LOADS asks, the
+ * batch's size and kernels decide; a batch on several streams: every sub-batch), else 0. */
+int vbx_batch_stream_loads_in_effect(const vbx_batch* b);
+/* The rule of VBX_STREAM_LOADS_AUTO as a function of the bytes of ONE copy of the x-vectors that iterate together (sum of
+ * T x padded D x element size over the recordings that own their x-vectors): 1 = non-temporal loads.  Host only. */
+int vbx_stream_loads_auto(int64_t rho_bytes);
 
 /* ---- one-shot: a single recording, host buffers in / out (= one reference VBx call) ---- */
 typedef struct {

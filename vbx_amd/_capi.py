@@ -19,6 +19,9 @@ OPT_GEMM = 14                # how the fp32 path multiplies: GEMM_EXACT (f32 MFM
 GEMM_EXACT, GEMM_SPLIT = 0, 1
 GEMM_NAMES = {'exact': GEMM_EXACT, 'split': GEMM_SPLIT}
 OPT_ASYNC_UPLOAD = 15        # setters only enqueue; one synchronize when the next run begins (Batch.set_async_upload)
+OPT_STREAM_LOADS = 16        # non-temporal loads of rho in the per-chunk kernels: auto (by the bytes that iterate together) | on | off
+STREAM_LOADS_AUTO, STREAM_LOADS_ON, STREAM_LOADS_OFF = 0, 1, 2
+STREAM_LOADS_NAMES = {'auto': STREAM_LOADS_AUTO, 'on': STREAM_LOADS_ON, 'off': STREAM_LOADS_OFF}
 K_NAMES = ['prep', 'mstep_acc', 'mstep_fin', 'loglik', 'fb', 'fb_aux', 'post', 'iter_fin', 'chunk_loglik',
            'chunk_post']
 MAX_SPEAKERS = 16384
@@ -34,7 +37,7 @@ ABI_SYMBOLS = [
     'vbx_scores_destroy',
     'vbx_xvectors_project', 'vbx_xvectors_get', 'vbx_xvectors_destroy', 'vbx_cos_similarity_resident',
     'vbx_batch_set_recording_resident', 'vbx_batch_get_labels', 'vbx_batch_set_recording_shared',
-    'vbx_batch_gemm_in_effect',
+    'vbx_batch_gemm_in_effect', 'vbx_batch_stream_loads_in_effect', 'vbx_stream_loads_auto',
     'vbx_batch_stream_of', 'vbx_batch_sync_uploads', 'vbx_batch_get_results', 'vbx_host_alloc', 'vbx_host_free',
     'vbx_fbank_create', 'vbx_fbank_run', 'vbx_fbank_get', 'vbx_fbank_windows', 'vbx_fbank_times', 'vbx_fbank_destroy',
     'vbx_resnet_create', 'vbx_resnet_input', 'vbx_resnet_run', 'vbx_resnet_times', 'vbx_resnet_destroy',
@@ -91,6 +94,8 @@ def load():
     lib.vbx_batch_kernel_times.argtypes = [vp, vp, vp]
     lib.vbx_batch_streams.argtypes = [vp]
     lib.vbx_batch_gemm_in_effect.argtypes = [vp]
+    lib.vbx_batch_stream_loads_in_effect.argtypes = [vp]
+    lib.vbx_stream_loads_auto.argtypes = [i64]
     lib.vbx_run.argtypes = [vp, vp, vp]
     lib.vbx_forward_backward.argtypes = [vp, i64, i32, vp, vp, vp, dbl, C.c_int, C.c_int, vp, C.POINTER(dbl),
                                          vp, vp, vp]
@@ -811,6 +816,17 @@ class Batch:
         """'split' when the iterations of the last run multiplied with f16 operand pairs (VBX_OPT_GEMM in effect), else
         'exact'."""
         return 'split' if int(self._lib.vbx_batch_gemm_in_effect(self._h)) == GEMM_SPLIT else 'exact'
+
+    def set_stream_loads(self, mode: str):
+        """'auto' | 'on' | 'off': non-temporal loads of rho in the per-chunk kernels (VBX_OPT_STREAM_LOADS)."""
+        if mode not in STREAM_LOADS_NAMES:
+            raise ValueError(f'stream_loads={mode!r}: expected one of {", ".join(map(repr, STREAM_LOADS_NAMES))}')
+        self.set_option(OPT_STREAM_LOADS, STREAM_LOADS_NAMES[mode])
+
+    @property
+    def stream_loads(self) -> bool:
+        """True when the per-chunk kernels of the last run fetched rho with non-temporal loads (VBX_OPT_STREAM_LOADS in effect)."""
+        return bool(self._lib.vbx_batch_stream_loads_in_effect(self._h))
 
     def kernel_times(self):
         ms = np.zeros(len(K_NAMES))

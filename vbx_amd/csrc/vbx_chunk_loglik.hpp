@@ -29,10 +29,15 @@ constexpr int kSplitLoglikWaves = 6;              // workgroups per CU of the sp
 // what its bytes take at (bytes in flight) / (memory latency) -- and a workgroup that fetches its rho slab one K-block ahead has
 // a quarter of it in flight: 632 workgroups x 16 KB / 2 us = 5 TB/s whatever the memory system could deliver.  LAT requests the
 // whole slab before the first product (64 registers per lane: fine at three or four workgroups per CU) -- for Dp <= 128.
-template <typename R, int SP, bool SPLIT = false, bool LAT = false>
+// POLICY = StreamLoads (STREAM, split mode): rho_a is fetched with non-temporal loads -- every line of it is read once per launch, and in a batch whose
+// rho is larger than the Infinity Cache none of it is there again one iteration later (VBX_OPT_STREAM_LOADS, vbx_host_launch.hpp).
+// The exact f32 and fp64 instances gain nothing from it (64 recordings: 0.2468 -> 0.2463 / 0.5121 -> 0.5149 ms per step) and have none.
+template <typename R, int SP, bool SPLIT = false, bool LAT = false, typename... POLICY>
 __global__ __launch_bounds__(256, (LAT ? (SP * (int)sizeof(R) <= 128 ? 4 : 2)
                                        : SP * (int)sizeof(R) <= 128 ? (SPLIT && SP == 32 ? kSplitLoglikWaves : 8) : SP * (int)sizeof(R) <= 256 ? 4 : 2)) void chunk_loglik_kernel(BatchView<R> bt) {
     static_assert(!SPLIT || sizeof(R) == 4, "the split GEMM is a mode of the fp32 path");
+    constexpr bool STREAM = stream_loads_asked<POLICY...>();
+    static_assert(!STREAM || SPLIT, "streaming loads: the split instances only");
     using M = Mfma16<R>;
     using acc_t = typename M::acc_t;
     using R4 = typename Vec<R>::v4;
@@ -98,8 +103,8 @@ __global__ __launch_bounds__(256, (LAT ? (SP * (int)sizeof(R) <= 128 ? 4 : 2)
             auto load_a = [&](int buf, int kk) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
-                    a[buf][m][0] = ra[((long long)m * KK + kk) * 128];
-                    a[buf][m][1] = ra[((long long)m * KK + kk) * 128 + 64];
+                    a[buf][m][0] = load_policy<STREAM>(ra + ((long long)m * KK + kk) * 128);
+                    a[buf][m][1] = load_policy<STREAM>(ra + ((long long)m * KK + kk) * 128 + 64);
                 }
             };
             load_a(0, 0);

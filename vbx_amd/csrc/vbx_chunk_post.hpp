@@ -59,9 +59,14 @@ template <typename R, int SP> struct ChunkPostCfg {
 // launch streams at (bytes in flight) / (latency).  Measured (8 recordings): 66.2 -> 64.1 us per iteration.  NOT in exact f32
 // (232 registers: two workgroups per CU, i.e. 512 slots for the 632 workgroups of eight recordings: 70.9 -> 79.9 us) nor in
 // fp64.  Since the end of round 6 every split instance with SP >= 32 does the same (kAllAhead below).
-template <typename R, int SP, bool REPLAY, bool SPLIT = false, bool FOLD = false>
+// POLICY = StreamLoads (STREAM, split mode): rho_b is fetched with non-temporal loads, as chunk_loglik fetches rho_a (VBX_OPT_STREAM_LOADS): the one
+// input of this kernel that no other launch of the iteration has just written.  The b tile stays on the default policy: streamed
+// too it measured 0.2099 against 0.2083 ms per step (NOTES.md).  Never together with FOLD.
+template <typename R, int SP, bool REPLAY, bool SPLIT = false, bool FOLD = false, typename... POLICY>
 __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post_kernel(BatchView<R> bt) {
     static_assert(!SPLIT || (sizeof(R) == 4 && !REPLAY), "the split GEMM is a mode of the fp32 iteration");
+    constexpr bool STREAM = stream_loads_asked<POLICY...>();
+    static_assert(!STREAM || (SPLIT && !FOLD), "streaming loads: the split iteration of a batch beyond the caches");
     using M = Mfma16<R>;
     using acc_t = typename M::acc_t;
     using R2 = typename Vec<R>::v2;
@@ -501,8 +506,8 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
         auto load_kstep = [&](int buf, int slab, int kk) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                bs[buf][h][0] = rb[((long long)(2 * slab + h) * 4 + kk) * 128];
-                bs[buf][h][1] = rb[((long long)(2 * slab + h) * 4 + kk) * 128 + 64];
+                bs[buf][h][0] = load_policy<STREAM>(rb + ((long long)(2 * slab + h) * 4 + kk) * 128);
+                bs[buf][h][1] = load_policy<STREAM>(rb + ((long long)(2 * slab + h) * 4 + kk) * 128 + 64);
             }
         };
         // Split mode: the wave's whole slab of the accumulation is requested NOW, between the re-run and the posterior pass (its

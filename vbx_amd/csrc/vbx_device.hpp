@@ -249,6 +249,21 @@ __device__ __forceinline__ void stage_to_lds(V* dst, const V* __restrict__ src, 
     }
 }
 
+// Non-temporal loads (global_load_dwordx4 ... nt) for data a launch reads exactly once and that is larger than the caches:
+// the h8 fragments of the f16 copies of rho of a big batch (VBX_OPT_STREAM_LOADS, vbx_host_launch.hpp).  The policy is a
+// template parameter of the kernels: load_policy<false> IS the plain load, so the other instances keep their code.  A kernel takes it as a trailing tag type (`..., StreamLoads>`; nothing = the default policy), so that the
+// instances without it also keep their NAMES in traces, profiles and the tools that read them.
+struct StreamLoads {};
+template <typename... POLICY> constexpr bool stream_loads_asked() {
+    static_assert(sizeof...(POLICY) <= 1, "one cache policy");
+    return (std::is_same<POLICY, StreamLoads>::value || ...);
+}
+template <typename V> __device__ __forceinline__ V load_stream(const V* p) { return __builtin_nontemporal_load(p); }
+template <bool STREAM, typename V> __device__ __forceinline__ V load_policy(const V* p) {
+    if constexpr (STREAM) return load_stream(p);
+    else return *p;
+}
+
 // Running product with an integer exponent on the side: prod * 2^expo, renormalised now and
 // then so that thousands of per-frame scales can be multiplied without a log per frame.
 struct ScaledProduct {

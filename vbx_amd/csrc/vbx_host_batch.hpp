@@ -257,6 +257,11 @@ static int leaf_set_option(vbx_batch* b, int option, int64_t value) {
 #endif
             b->gemm = (int)value;
             return VBX_OK;
+        case VBX_OPT_STREAM_LOADS:
+            if (value < VBX_STREAM_LOADS_AUTO || value > VBX_STREAM_LOADS_OFF)
+                FAIL(b->ctx, VBX_ERR_INVALID, "VBX_OPT_STREAM_LOADS takes VBX_STREAM_LOADS_AUTO, _ON or _OFF");
+            b->stream_loads = (int)value;
+            return VBX_OK;
         case VBX_OPT_ASYNC_UPLOAD:
             if (value != 0 && value != 1) FAIL(b->ctx, VBX_ERR_INVALID, "VBX_OPT_ASYNC_UPLOAD takes 0 or 1");
             if (!value && b->async_upload)

@@ -306,6 +306,16 @@ int vbx_batch_run(vbx_batch* b, int max_iters, double epsilon) {
     // stream) are issued in parallel and the streams drift out of phase by themselves.  Fed round-robin from ONE
     // thread (also with the streams started a fraction of a period apart) the same streams gave no gain at all.
     const int K = (int)b->kids.size();
+    // (the cache policy of the rho loads is a property of what iterates TOGETHER: every sub-batch gets the group's total, the
+    //  x-vectors a sweep shares across sub-batches counted once -- VBX_OPT_STREAM_LOADS.  This is a rule, not a count of
+    //  physical bytes: every sub-batch that runs points of a sweep holds a device clone of the shared rows
+    //  (leaf_set_recording_cloned), and the clones are deliberately NOT counted -- the nine-point sweep over T = 200 000 on three
+    //  streams reads 3 x 102 MB of distinct rho lines, more than the 256 MiB, and is classed as 102 MB.  That case keeps the
+    //  default policy because its rate is unchanged by construction; streaming loads were never measured on it)
+    long long rho_bytes = 0;
+    for (int i = 0; i < b->n_rec; ++i)
+        if (b->root_of[i] == i) rho_bytes += (long long)b->all_T[i] * b->kids[0]->Dp * (long long)b->kids[0]->rsize;
+    for (vbx_batch* k : b->kids) k->group_rho_bytes = rho_bytes;
     // The feeding threads are created with the group and sleep between runs: a VBx() call is a few dozen
     // iterations, and starting three threads (with their first HIP call each) cost as much as two of them.
     GroupThreads& g = *b->threads;
@@ -460,6 +470,16 @@ int vbx_batch_stream_of(const vbx_batch* b, int rec) {
     if (!b || rec < 0 || rec >= b->n_rec) return -1;
     return b->kids.empty() ? 0 : b->kid_of[rec];
 }
+
+int vbx_batch_stream_loads_in_effect(const vbx_batch* b) {
+    if (!b) return 0;
+    if (b->kids.empty()) return b->stream_now ? 1 : 0;
+    for (const vbx_batch* k : b->kids)
+        if (!k->stream_now) return 0;
+    return 1;
+}
+
+int vbx_stream_loads_auto(int64_t rho_bytes) { return stream_loads_auto((long long)rho_bytes) ? 1 : 0; }
 
 int vbx_batch_gemm_in_effect(const vbx_batch* b) {
     if (!b) return VBX_GEMM_EXACT;

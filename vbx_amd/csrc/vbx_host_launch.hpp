@@ -117,9 +117,22 @@ static int small_kernel_threads(const vbx_batch* b, int from_tiles) {
 // mat-vecs per workgroup cost more than the launch they replace).
 // A batch that does not fill the chip: the small-batch instances of the chunk kernels (FOLD / LAT).
 static bool small_batch_wanted(const vbx_batch* b) { return b->ntiles_total <= 2048; }
+// Non-temporal loads of rho in the per-chunk kernels (VBX_OPT_STREAM_LOADS)?  Each launch reads every line of its rho copy once.
+// Where one copy is larger than the Infinity Cache nothing of it is left when the next iteration comes, and the lines it would
+// push through the caches only evict what the iteration produces and consumes (b, the operators, the partial sums); a smaller
+// batch streams its rho FROM the caches (four recordings: 9.6 TB/s out of L2) and must keep the default policy.
+constexpr long long kInfinityCacheBytes = 256ll << 20;
+static bool stream_loads_auto(long long rho_bytes) { return rho_bytes > kInfinityCacheBytes; }
+static bool stream_loads_wanted(const vbx_batch* b) {
+    if (b->stream_loads != VBX_STREAM_LOADS_AUTO) return b->stream_loads == VBX_STREAM_LOADS_ON;
+    long long own = 0;                            // one copy of this batch's rho, a shared one counted once
+    for (int i = 0; i < b->n_rec; ++i)
+        if (b->share_src[i] == i) own += b->recs[i].T * (long long)b->Dp * (long long)b->rsize;
+    return stream_loads_auto(b->group_rho_bytes > 0 ? b->group_rho_bytes : own);
+}
 template <int SP> bool fold_walk_wanted(const vbx_batch* b) {
     if (SP > 32 || b->sgroup <= 1 || b->sgroup - 1 > kTileFrames / SP) return false;
-    return small_batch_wanted(b);
+    return small_batch_wanted(b) && !b->stream_now;       // (no streaming FOLD instance: the last level is a launch of its own then)
 }
 
 template <typename R, int SP, bool REPLAY> void launch_chunk_post(vbx_batch* b, const BatchView<R>& v) {
@@ -134,7 +147,8 @@ template <typename R, int SP, bool REPLAY> void launch_chunk_post(vbx_batch* b, 
                         return;
                     }
                 }
-                hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
+                if (b->stream_now) hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true, false, StreamLoads>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
+                else hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
                 return;
             }
         }
@@ -162,11 +176,15 @@ template <typename R, int SP> void launch_scan(vbx_batch* b, const BatchView<R>&
                 if (v.rho_a) {                               // rho alpha^T on the f16 matrix cores (vbx_split.hpp)
                     if constexpr (SP <= 32) {
                         if (lat) {
-                            hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
+                            if (b->stream_now) hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, true, StreamLoads>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
+                            else hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
                             launched = true;
                         }
                     }
-                    if (!launched) hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
+                    if (!launched) {
+                        if (b->stream_now) hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, false, StreamLoads>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
+                        else hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
+                    }
                     launched = true;
                 }
             }
@@ -310,6 +328,7 @@ static bool split_available(const vbx_batch* b) { return split_wanted(b) && !b->
 template <typename R> void launch_iteration(vbx_batch* b, double eps) {
     b->fused_now = fused_available<R>(b);
     b->split_now = b->d_rho_a != nullptr && split_available(b);
+    b->stream_now = b->split_now && b->fused_now && stream_loads_wanted(b);
     // the previous iteration of this run (if any) is finished by the launch that starts this one; the last one of a run
     // by run_end
     const int fin_mode = b->fin_pending ? 3 : 1;

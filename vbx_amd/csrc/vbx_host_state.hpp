@@ -135,6 +135,9 @@ struct vbx_batch {
     int split_tiles = 0;                          // option: 0 auto, 1 on, 2 off (VBX_OPT_SPLIT_TILES)
     int gemm = VBX_GEMM_EXACT;                    // option VBX_OPT_GEMM: how the fp32 path multiplies (vbx_split.hpp)
     bool split_now = false;                       // in effect for the launches being issued: f16 operand pairs
+    int stream_loads = VBX_STREAM_LOADS_AUTO;     // option VBX_OPT_STREAM_LOADS: non-temporal loads of rho in the per-chunk kernels
+    long long group_rho_bytes = 0;                // a sub-batch of a stream group: one copy of the rho of the WHOLE group (vbx_batch_run)
+    bool stream_now = false;                      // in effect for the launches being issued: the streaming instances
     std::vector<char> split_dirty;                // recording -> its rho has changed since its f16 copies were made
     std::vector<char> split_bad;                  // recording -> its rho spans more than kSplitRangeBits between frames (rho_absmax_kernel)
     bool split_declined = false;                  // ... for any recording: the batch multiplies exactly (vbx_batch_gemm_in_effect says so)
