@@ -30,6 +30,8 @@
 extern "C" {
 #endif
 
+/* The ABI only grows within a version: entry points are added (the *_ragged ones came after 7 was set), none changes its
+ * signature or its meaning. */
 #define VBX_ABI_VERSION 7
 
 /* error codes */
@@ -394,6 +396,11 @@ int vbx_fbank_get(vbx_fbank* fb, int which, int64_t row0, int64_t nrows, void* d
 /* n windows of len rows of the CMN features starting at rows starts[n], transposed to dst [n][n_mel][len] f32 (the
  * embedding model's [B, C, T] input, predict.py:68-70).  Synchronises before it returns. */
 int vbx_fbank_windows(vbx_fbank* fb, int32_t n, const int64_t* starts, int32_t len, float* dst, int dst_on_device);
+/* Windows of mixed lengths in one call: window w is lens[w] >= 1 rows from row starts[w], transposed to [n_mel][lens[w]];
+ * dst receives the n blocks end to end (n_mel * sum(lens) f32): the input of vbx_resnet_run_ragged.  One kernel, one
+ * synchronize, where vbx_fbank_windows needs a call per length.  VBX_ERR_INVALID with a message: n <= 0, a NULL pointer, a
+ * lens[w] <= 0, a window past the feature rows. */
+int vbx_fbank_windows_ragged(vbx_fbank* fb, int32_t n, const int64_t* starts, const int32_t* lens, float* dst, int dst_on_device);
 /* device milliseconds (HIP events) of the last run: ms[0] upload, [1] frame kernel, [2] CMN; ms[3] the last windows call. */
 int vbx_fbank_times(vbx_fbank* fb, float* ms);
 int vbx_fbank_destroy(vbx_fbank* fb);
@@ -413,6 +420,18 @@ int vbx_resnet_input(vbx_resnet* net, int32_t n, int32_t T, float** d_in);
 /* embeddings [n][embed_dim] f32 of n windows x [n][64][T] (host or device memory).  Workspace grows to the largest
  * (n, T) seen.  One synchronize, after the copy out. */
 int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_on_device, float* out, int out_on_device);
+/* A ragged batch: n windows of T[b] >= 1 frames each, in any order, through the network in one walk.  x is the windows'
+ * [64][T[b]] blocks end to end (64 * sum(T) f32, host or device memory); out [n][embed_dim].  At level l = 0 .. 3 (64 >> l
+ * rows; a window's width W_{b,l} is (W - 1) / 2 + 1 applied l times to T[b]) an activation tensor is the windows'
+ * [H_l][W_{b,l}][C] blocks end to end; the host uploads where each starts (pos [4][n + 1], int64) and how wide it is (wid
+ * [4][n], int32), and a kernel row finds its window by a binary search of pos.  Nothing is padded to a common width.  Every
+ * embedding has the bits vbx_resnet_run gives that window alone, in both gemm modes.  Workspace grows to the largest
+ * sum seen; vbx_resnet_times and vbx_resnet_gemm_in_effect speak of it as of any run.  VBX_ERR_INVALID with a message:
+ * n <= 0, a NULL pointer, a T[b] <= 0. */
+int vbx_resnet_run_ragged(vbx_resnet* net, int32_t n, const int32_t* T, const float* x, int x_on_device, float* out,
+                          int out_on_device);
+/* vbx_resnet_input for a ragged batch: a device buffer of 64 * sum(T) f32 that vbx_fbank_windows_ragged may fill. */
+int vbx_resnet_input_ragged(vbx_resnet* net, int32_t n, const int32_t* T, float** d_in);
 /* device milliseconds of the last run: ms[0] stem, [1..4] layer1..layer4, [5] pooling + embedding. */
 int vbx_resnet_times(vbx_resnet* net, float* ms);
 int vbx_resnet_destroy(vbx_resnet* net);
@@ -451,6 +470,13 @@ int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t
 int vbx_resnet_conv_gemm(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin,
                          int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn,
                          int32_t bm, float* y, int64_t pad, float* amax_y);
+/* vbx_resnet_conv_gemm over a ragged batch: n windows of H rows and W[b] >= 1 columns.  x is the windows' [H][W[b]][Cin]
+ * blocks end to end, res and the payload of y the [Ho][Wo[b]][Cout] blocks end to end (M = sum Ho Wo[b] positions), amax_y
+ * [n].  The ragged kernel of the (dispatcher's, for this M, or forced) tile runs; guard band, tiles and refusals as
+ * vbx_resnet_conv, and n <= 0, W NULL or a W[b] <= 0 refused with a message. */
+int vbx_resnet_conv_ragged(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, const int32_t* W, int32_t Cin,
+                           int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn,
+                           int32_t bm, float* y, int64_t pad, float* amax_y);
 /* The split mode's weights (host code, needs no device): w [K][Cout] f32, K a multiple of 16, Cout of 32  ->  e [Cout], the
  * exponent of every output channel's power-of-two scale, and frag [K / 16][Cout / 32][hi | lo][64 lanes][8] f16 bits, the
  * fragment order of the B operand of v_mfma_f32_32x32x16_f16: lane l holds B[k = 8 (l >> 5) + j][column l & 31]. */
@@ -458,6 +484,12 @@ int vbx_resnet_split_weights(int32_t K, int32_t Cout, const float* w, uint16_t* 
 /* The stem: conv 3 x 3 of one input channel to 32, + bias, ReLU.  x [n][64][T], w [9][32] (row r 3 + s), bias [32]
  * ->  y [pad + n 64 T 32 + pad], the payload [n][64][T][32]. */
 int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const float* w, const float* bias, float* y, int64_t pad);
+/* The stem over a ragged batch: x the [64][T[b]] blocks end to end  ->  the payload of y the [64][T[b]][32] blocks. */
+int vbx_resnet_stem_ragged(vbx_ctx* ctx, int32_t n, const int32_t* T, const float* x, const float* w, const float* bias, float* y,
+                           int64_t pad);
+/* Statistics pooling over a ragged batch: x the [8][W4[b]][1024] blocks end to end, every window divided by its own W4[b]
+ * ->  the payload [n][16384]. */
+int vbx_resnet_pool_ragged(vbx_ctx* ctx, int32_t n, const int32_t* W4, const float* x, float* out, int64_t pad);
 /* Statistics pooling: x [n][8][W4][1024]  ->  out [pad + n 16384 + pad], the payload [n][16384]: [h 1024 + c] the mean
  * over the W4 frames, [8192 + h 1024 + c] sqrt(mean(x^2) - mean^2 + 1e-10), summed in f64. */
 int vbx_resnet_pool(vbx_ctx* ctx, int32_t n, int32_t W4, const float* x, float* out, int64_t pad);

@@ -7,6 +7,14 @@ random N(0, 1) windows.
 
 --gemm both measures the two modes of the network in one process on the same inputs and prints both tables.
 
+    python tools/bench_xvec.py --tails 400 [--ways grouped|ragged|both] [--gemm ...] [--batch 128] [--frames 144]
+
+times the windows of one synthetic file that are NOT full ones -- --tails windows, their lengths drawn uniformly from
+10 .. frames - 1 -- both ways predict can run them: grouped by exact length, one run of the network per distinct length
+(ResNet101.embed), and as ragged batches of at most batch x frames frames in all (ResNet101.embed_ragged).  Device time
+is the sum of the runs' HIP-event times; wall time includes every run's launches and its synchronize.  --ways grouped
+needs nothing but ResNet101.embed.
+
 Prints a table and one JSON line.  FLOPs are counted from the architecture (xvector.flops, 2 per multiply-add); TF/s is
 that count over the device time of the stage (once per multiply-add in the split mode too, not once per f16 matrix
 instruction); the f32 matrix peak is 155 TF (MI355X_MICROARCH.md)."""
@@ -60,6 +68,63 @@ def measure(net, xt, a, gemm):
             'hour_s': total * HOUR_WINDOWS / B / 1e3, 'wall_ms': 1e3 * float(np.median(wall))}, y
 
 
+def measure_tails(net, a, gemm, dev):
+    """The tails of one synthetic file both ways; -> its result dict."""
+    rng = np.random.default_rng(a.seed)
+    lengths = rng.integers(10, a.frames, a.tails)
+    xs = [rng.standard_normal((64, int(T))).astype(np.float32) for T in lengths]
+    ways, out = {}, {}
+    if a.ways in ('grouped', 'both'):
+        groups = {}
+        for i, T in enumerate(lengths):
+            groups.setdefault(int(T), []).append(i)
+        batches = [(idx, torch.from_numpy(np.stack([xs[i] for i in idx])).to(dev)) for idx in groups.values()]
+        ways['grouped'] = (batches, lambda xt: net.embed(xt))
+    if a.ways in ('ragged', 'both'):
+        batches, cur, frames = [], [], 0
+        for i, T in enumerate(lengths):                       # (predict.ragged_batches)
+            if cur and frames + T > a.batch * a.frames:
+                batches.append(cur)
+                cur, frames = [], 0
+            cur.append(i)
+            frames += int(T)
+        batches.append(cur)
+        batches = [(idx, (torch.from_numpy(np.concatenate([xs[i].reshape(-1) for i in idx])).to(dev), [int(lengths[i]) for i in idx]))
+                   for idx in batches]
+        ways['ragged'] = (batches, lambda xl: net.embed_ragged(*xl))
+    res = {'gemm': gemm, 'tails': int(a.tails), 'frames_total': int(lengths.sum()), 'distinct_lengths': len(set(lengths.tolist())),
+           'cap_frames': a.batch * a.frames}
+    print(f'ResNet101 ({gemm}), {a.tails} tail windows of 10 .. {a.frames - 1} frames ({res["frames_total"]} frames, '
+          f'{res["distinct_lengths"]} distinct lengths), median of {a.reps} runs after {a.warmup}')
+    print(f'{"way":<10}{"runs":>6}{"device ms":>12}{"min":>10}{"max":>10}{"wall ms":>10}')
+    for way, (batches, run) in ways.items():
+        dev_ms, wall = [], []
+        emb = np.empty((a.tails, net.embed_dim), dtype=np.float32)
+        for rep_ in range(a.warmup + a.reps):
+            t0, ms = time.perf_counter(), 0.0
+            for idx, arg in batches:
+                y = run(arg)
+                ms += sum(net.times().values())
+                if rep_ == 0:
+                    emb[idx] = y.cpu().numpy()
+            if rep_ >= a.warmup:
+                dev_ms.append(ms)
+                wall.append(1e3 * (time.perf_counter() - t0))
+        assert net.gemm_in_effect() == gemm
+        out[way] = emb
+        res[way] = {'runs': len(batches), 'device_ms': float(np.median(dev_ms)), 'device_ms_min': float(min(dev_ms)),
+                    'device_ms_max': float(max(dev_ms)), 'wall_ms': float(np.median(wall))}
+        r = res[way]
+        print(f'{way:<10}{r["runs"]:>6}{r["device_ms"]:>12.3f}{r["device_ms_min"]:>10.3f}{r["device_ms_max"]:>10.3f}{r["wall_ms"]:>10.3f}')
+    if len(out) == 2:
+        res['same_bits'] = bool(np.array_equal(out['grouped'].view(np.uint32), out['ragged'].view(np.uint32)))
+        res['ragged_over_grouped_device'] = res['ragged']['device_ms'] / res['grouped']['device_ms']
+        res['ragged_over_grouped_wall'] = res['ragged']['wall_ms'] / res['grouped']['wall_ms']
+        print(f'ragged / grouped: device time {res["ragged_over_grouped_device"]:.3f}, wall time {res["ragged_over_grouped_wall"]:.3f}; '
+              f'same bits: {res["same_bits"]}')
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=128)
@@ -70,9 +135,19 @@ def main():
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--no-torch', action='store_true')
     ap.add_argument('--gemm', default='exact', choices=['exact', 'split', 'both'])
+    ap.add_argument('--tails', type=int, default=0, help='time this many tail windows of one synthetic file instead')
+    ap.add_argument('--ways', default='both', choices=['grouped', 'ragged', 'both'])
     a = ap.parse_args()
     B, T = a.batch, a.frames
     sd = xvector.synthetic_state_dict(a.seed)
+    if a.tails > 0:
+        results = []
+        for gemm in ['exact', 'split'] if a.gemm == 'both' else [a.gemm]:
+            net = xvector.ResNet101(sd, a.device, gemm=gemm)
+            results.append(measure_tails(net, a, gemm, torch.device('cuda', a.device)))
+            del net
+        print(json.dumps({'tails_bench': results}))
+        return
     x = np.random.default_rng(a.seed).standard_normal((B, 64, T)).astype(np.float32)
     dev = torch.device('cuda', a.device)
     xt = torch.from_numpy(x).to(dev)

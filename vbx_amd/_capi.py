@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     'vbx_resnet_create', 'vbx_resnet_input', 'vbx_resnet_run', 'vbx_resnet_times', 'vbx_resnet_destroy',
     'vbx_resnet_conv_tile', 'vbx_resnet_conv', 'vbx_resnet_stem', 'vbx_resnet_pool',
     'vbx_resnet_set_gemm', 'vbx_resnet_gemm_in_effect', 'vbx_resnet_conv_gemm', 'vbx_resnet_split_weights',
+    'vbx_fbank_windows_ragged', 'vbx_resnet_run_ragged', 'vbx_resnet_input_ragged',
+    'vbx_resnet_conv_ragged', 'vbx_resnet_stem_ragged', 'vbx_resnet_pool_ragged',
 ]
 
 
@@ -147,6 +149,12 @@ def load():
     lib.vbx_resnet_gemm_in_effect.argtypes = [vp]
     lib.vbx_resnet_conv_gemm.argtypes = [vp, C.c_int, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_int, i32, i32, vp, i64, vp]
     lib.vbx_resnet_split_weights.argtypes = [i32, i32, vp, vp, vp]
+    lib.vbx_fbank_windows_ragged.argtypes = [vp, i32, vp, vp, vp, C.c_int]
+    lib.vbx_resnet_run_ragged.argtypes = [vp, i32, vp, vp, C.c_int, vp, C.c_int]
+    lib.vbx_resnet_input_ragged.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    lib.vbx_resnet_conv_ragged.argtypes = [vp, C.c_int, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, C.c_int, i32, i32, vp, i64, vp]
+    lib.vbx_resnet_stem_ragged.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64]
+    lib.vbx_resnet_pool_ragged.argtypes = [vp, i32, vp, vp, vp, i64]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -399,6 +407,21 @@ class FbankDevice:
                                                    int(out is None)), 'vbx_fbank_windows')
         return out
 
+    def windows_ragged(self, starts, lengths, dst_ptr=None):
+        """Windows of mixed lengths (vbx_fbank_windows_ragged): window w is lengths[w] rows from row starts[w]; their
+        [n_mel][lengths[w]] f32 blocks end to end, as one flat host array or into device memory at dst_ptr."""
+        starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if starts.shape != lengths.shape:
+            raise ValueError(f'windows_ragged: {starts.shape[0]} starts, {lengths.shape[0]} lengths')
+        out = None
+        if dst_ptr is None:
+            out = np.empty(self.n_mel * int(np.maximum(lengths, 0).sum(dtype=np.int64)), dtype=np.float32)
+            dst_ptr = out.ctypes.data
+        self.ctx.check(self._lib.vbx_fbank_windows_ragged(self._h, starts.shape[0], _ptr(starts), _ptr(lengths),
+                                                          C.c_void_p(dst_ptr), int(out is None)), 'vbx_fbank_windows_ragged')
+        return out
+
     def times(self):
         """device ms of the last run: upload, frame kernel, CMN, and of the last windows call: gather."""
         ms = np.zeros(4, dtype=np.float32)
@@ -466,6 +489,34 @@ class ResNetDevice:
             out_ptr = out.ctypes.data
         self.ctx.check(self._lib.vbx_resnet_run(self._h, int(n), int(T), src, on_dev, C.c_void_p(out_ptr), int(out is None)),
                        'vbx_resnet_run')
+        return out
+
+    def input_buffer_ragged(self, lengths) -> int:
+        """Device address of the network's own input buffer for a ragged batch: 64 sum(lengths) f32 (vbx_resnet_input_ragged)."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        p = C.c_void_p()
+        self.ctx.check(self._lib.vbx_resnet_input_ragged(self._h, lengths.shape[0], _ptr(lengths), C.byref(p)),
+                       'vbx_resnet_input_ragged')
+        return p.value
+
+    def run_ragged(self, lengths, x=None, x_ptr=None, out_ptr=None):
+        """Embeddings [n][E] f32 of n windows of lengths[b] frames (vbx_resnet_run_ragged): x the flat host array of their
+        [64][lengths[b]] blocks end to end, or device memory at x_ptr; into a new host array, or device memory at out_ptr."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        n = lengths.shape[0]
+        if x_ptr is None:
+            x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+            if x.size != 64 * int(np.maximum(lengths, 0).sum(dtype=np.int64)):
+                raise ValueError(f'run_ragged: x holds {x.size} values, the lengths ask for 64 x {int(lengths.sum())}')
+            src, on_dev = _ptr(x), 0
+        else:
+            src, on_dev = C.c_void_p(x_ptr), 1
+        out = None
+        if out_ptr is None:
+            out = np.empty((n, self.embed_dim), dtype=np.float32)
+            out_ptr = out.ctypes.data
+        self.ctx.check(self._lib.vbx_resnet_run_ragged(self._h, n, _ptr(lengths), src, on_dev, C.c_void_p(out_ptr), int(out is None)),
+                       'vbx_resnet_run_ragged')
         return out
 
     def times(self):
@@ -552,6 +603,61 @@ def resnet_conv_gemm(ctx: 'Context', gemm, x, w, bias, ks, stride, res=None, rel
     def call(*a):
         ctx.check(ctx._lib.vbx_resnet_conv_gemm(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), *a, _ptr(amax)), 'vbx_resnet_conv_gemm')
     return _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad) + (amax[:n],)
+
+
+def resnet_conv_ragged(ctx: 'Context', gemm, xs, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
+    """One convolution over a ragged batch (vbx_resnet_conv_ragged; gemm 'exact' or 'split'): xs a list of [H][W_b][Cin]
+    windows, res a list of [Ho][Wo_b][Cout] or None.  -> (ys: the list of [Ho][Wo_b][Cout] outputs, guard, unwritten, amax_y [n])."""
+    xs = [_f32(x) for x in xs]
+    w, bias = _f32(w), _f32(bias)
+    n, H, Cin, Cout = len(xs), xs[0].shape[0], xs[0].shape[2], w.shape[1]
+    assert all(x.ndim == 3 and x.shape[0] == H and x.shape[2] == Cin for x in xs)
+    widths = np.array([x.shape[1] for x in xs], dtype=np.int32)
+    s = max(int(stride), 1)
+    Ho, Wo = (H - 1) // s + 1, [(int(W) - 1) // s + 1 for W in widths]
+    counts = [Ho * W * Cout for W in Wo]
+    count = sum(counts)
+    x = np.concatenate([x.reshape(-1) for x in xs])
+    r = None if res is None else np.concatenate([_f32(a).reshape(-1) for a in res])
+    assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (r is None or r.size == count)
+    bn, bm = tile or (0, 0)
+    buf = _guarded(count, pad)
+    amax = np.zeros(n, dtype=np.float32)
+    ctx.check(ctx._lib.vbx_resnet_conv_ragged(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), n, H, _ptr(widths), Cin, Cout, _ptr(x),
+                                              _ptr(w), _ptr(bias), _ptr(r), int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad),
+                                              _ptr(amax)), 'vbx_resnet_conv_ragged')
+    y, guard, unwritten = _unguard(buf, count, pad)
+    offs = np.concatenate([[0], np.cumsum(counts)])
+    return [y[offs[b]:offs[b + 1]].reshape(Ho, Wo[b], Cout) for b in range(n)], guard, unwritten, amax
+
+
+def resnet_stem_ragged(ctx: 'Context', xs, w, bias, pad=RN_PAD):
+    """The stem over a ragged batch (vbx_resnet_stem_ragged): xs a list of [64][T_b] -> (list of [64][T_b][32], guard, unwritten)."""
+    xs, w, bias = [_f32(x) for x in xs], _f32(w), _f32(bias)
+    assert all(x.ndim == 2 and x.shape[0] == 64 for x in xs) and w.shape == (9, 32) and bias.shape == (32,)
+    T = np.array([x.shape[1] for x in xs], dtype=np.int32)
+    x = np.concatenate([x.reshape(-1) for x in xs])
+    count = 64 * 32 * int(T.sum())
+    buf = _guarded(count, pad)
+    ctx.check(ctx._lib.vbx_resnet_stem_ragged(ctx._h, len(xs), _ptr(T), _ptr(x), _ptr(w), _ptr(bias), _ptr(buf), int(pad)),
+              'vbx_resnet_stem_ragged')
+    y, guard, unwritten = _unguard(buf, count, pad)
+    offs = np.concatenate([[0], np.cumsum(64 * 32 * T.astype(np.int64))])
+    return [y[offs[b]:offs[b + 1]].reshape(64, int(T[b]), 32) for b in range(len(xs))], guard, unwritten
+
+
+def resnet_pool_ragged(ctx: 'Context', xs, pad=RN_PAD):
+    """Statistics pooling over a ragged batch (vbx_resnet_pool_ragged): xs a list of [8][W4_b][1024] -> (out [n][16384],
+    guard, unwritten)."""
+    xs = [_f32(x) for x in xs]
+    assert all(x.ndim == 3 and x.shape[0] == 8 and x.shape[2] == 1024 for x in xs)
+    W4 = np.array([x.shape[1] for x in xs], dtype=np.int32)
+    x = np.concatenate([x.reshape(-1) for x in xs])
+    count = len(xs) * 16384
+    buf = _guarded(count, pad)
+    ctx.check(ctx._lib.vbx_resnet_pool_ragged(ctx._h, len(xs), _ptr(W4), _ptr(x), _ptr(buf), int(pad)), 'vbx_resnet_pool_ragged')
+    out, guard, unwritten = _unguard(buf, count, pad)
+    return out.reshape(len(xs), 16384), guard, unwritten
 
 
 def resnet_split_weights(w):

@@ -11,7 +11,8 @@
 //                        padded signal is never formed), frames x M^T on the matrix cores, power in LDS (f32), Mel + log
 //                        accumulated in f64, log-Mel rows out in f64
 //   fbank_cmn_kernel     cmvn_floating_kaldi(fea, LC, RC, norm_vars=False) per segment, cast to f32
-//   fbank_gather_kernel  windows [n][64][len] (the model's [B, C, T] layout) from the CMN rows
+//   fbank_gather_kernel  windows [n][64][len] (the model's [B, C, T] layout) from the CMN rows; fbank_gather_ragged_kernel:
+//                        windows of mixed lengths, their [64][len_w] blocks laid end to end
 #pragma once
 #include "vbx_device.hpp"
 
@@ -126,6 +127,28 @@ __global__ __launch_bounds__(256) void fbank_gather_kernel(const float* __restri
     __shared__ float tile[128][FB_MEL + 1];
     const long long w = blockIdx.x, row0 = starts[w];
     float* __restrict__ o = out + w * FB_MEL * (long long)len;
+    for (int c0 = 0; c0 < len; c0 += 128) {
+        const int nc = min(128, len - c0);
+        for (int e = threadIdx.x; e < nc * FB_MEL; e += 256)
+            tile[e >> 6][e & 63] = fea[(row0 + c0) * FB_MEL + e];
+        __syncthreads();
+        for (int e = threadIdx.x; e < nc * FB_MEL; e += 256) {
+            const int c = e / nc, t = e - c * nc;
+            o[(long long)c * len + c0 + t] = tile[t][c];
+        }
+        __syncthreads();
+    }
+}
+
+// windows of mixed lengths, one workgroup each: window w is rows tab[w] .. + tab[2 n + w] and goes, transposed to
+// [64][len], to out + 64 tab[n + w] (tab [3][n]: the first row, the frames before the window in the output, the length):
+// the concatenated input of a ragged batch of the embedding network
+__global__ __launch_bounds__(256) void fbank_gather_ragged_kernel(const float* __restrict__ fea, const long long* __restrict__ tab,
+                                                                  int n, float* __restrict__ out) {
+    __shared__ float tile[128][FB_MEL + 1];
+    const long long w = blockIdx.x, row0 = tab[w];
+    const int len = (int)tab[2 * (long long)n + w];
+    float* __restrict__ o = out + tab[n + w] * FB_MEL;
     for (int c0 = 0; c0 < len; c0 += 128) {
         const int nc = min(128, len - c0);
         for (int e = threadIdx.x; e < nc * FB_MEL; e += 256)

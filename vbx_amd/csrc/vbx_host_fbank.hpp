@@ -233,6 +233,50 @@ int vbx_fbank_windows(vbx_fbank* fb, int32_t n, const int64_t* starts, int32_t l
     return VBX_OK;
 }
 
+int vbx_fbank_windows_ragged(vbx_fbank* fb, int32_t n, const int64_t* starts, const int32_t* lens, float* dst, int dst_on_device) {
+    if (!fb) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = fb->ctx;
+    if (!starts || !lens || !dst) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_windows_ragged: starts, lens and dst must not be NULL");
+    if (n <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_windows_ragged: n = %d windows, need at least one", n);
+    std::vector<long long> tab(3 * (size_t)n);                 // the first rows | the frames before each window | the lengths
+    long long frames = 0;
+    for (int w = 0; w < n; ++w) {
+        if (lens[w] <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_windows_ragged: window %d has lens = %d, need at least 1", w, lens[w]);
+        if (starts[w] < 0 || starts[w] + lens[w] > fb->rows)
+            FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_windows_ragged: window %d (rows %lld + %d) past the %lld feature rows", w,
+                 (long long)starts[w], lens[w], fb->rows);
+        tab[w] = starts[w];
+        tab[(size_t)n + w] = frames;
+        tab[2 * (size_t)n + w] = lens[w];
+        frames += lens[w];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipStreamSynchronize(st));                     // (a smaller table may still be read by queued work)
+    int rc = fb_reserve(ctx, &fb->d_starts, &fb->cap_starts, tab.size());
+    if (rc != VBX_OK) return rc;
+    const size_t bytes = sizeof(float) * (size_t)frames * FB_MEL;
+    float* out = dst;
+    void* tmp = nullptr;
+    if (!dst_on_device) {
+        rc = dmalloc_bytes(ctx, &tmp, bytes);
+        if (rc != VBX_OK) return rc;
+        out = (float*)tmp;
+    }
+    hipError_t e = hipMemcpyAsync(fb->d_starts, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(fb->ev[4], st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(fbank_gather_ragged_kernel, dim3((unsigned)n), dim3(256), 0, st, fb->d_fea, fb->d_starts, n, out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(fb->ev[5], st);
+    if (e == hipSuccess && tmp) e = hipMemcpyAsync(dst, tmp, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);         // (tab is pageable: its copy has left the host by now)
+    ctx_free(ctx, tmp);
+    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "vbx_fbank_windows_ragged: %s", hipGetErrorString(e));
+    return VBX_OK;
+}
+
 int vbx_fbank_times(vbx_fbank* fb, float* ms) {
     if (!fb || !ms) return VBX_ERR_INVALID;
     vbx_ctx* ctx = fb->ctx;

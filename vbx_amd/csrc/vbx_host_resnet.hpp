@@ -16,7 +16,7 @@ enum RnBuf { RN_X0, RN_X1, RN_T1, RN_T2, RN_SC, RN_NBUF };     // the block outp
 struct RnPlanStep {
     int conv;                                                  // index into vbx_resnet::convs
     int in, out, res;                                          // RnBuf; res: RN_NBUF for none
-    int H, W, relu;                                            // the input's size
+    int lvl, relu;                                             // the input's level (rn_levels); the output's: + 1 at stride 2
     int ain, aout;                                             // split mode: the max |.| slots of its input and (or -1) its output
     int stage;                                                 // 0 .. 3: layer1 .. layer4 (the events)
 };
@@ -25,8 +25,7 @@ struct vbx_resnet {
     vbx_ctx* ctx = nullptr;
     int E = 0, Ep = 0;                                         // embedding width, padded to 32 columns on the device
     std::vector<RnConv> convs;                                 // [0] the stem, then 3 or 4 per block
-    std::vector<RnPlanStep> plan;                              // the launch sequence at plan_T frames
-    int plan_T = 0;
+    std::vector<RnPlanStep> plan;                              // the launch sequence (rn_plan)
     float *d_par = nullptr, *d_emb_w = nullptr, *d_emb_b = nullptr;
     float *d_in = nullptr, *d_buf[RN_NBUF] = {}, *d_pool = nullptr, *d_out = nullptr;
     size_t cap_in = 0, cap_buf[RN_NBUF] = {}, cap_pool = 0, cap_out = 0;
@@ -38,6 +37,9 @@ struct vbx_resnet {
     int* d_we = nullptr;
     unsigned* d_amax = nullptr;
     size_t cap_amax = 0;
+    long long* d_pos = nullptr;                                // ragged runs: RnLevels' tables
+    int* d_wid = nullptr;
+    size_t cap_pos = 0, cap_wid = 0;
 };
 
 constexpr int RN_BLOCKS[4] = {3, 4, 23, 3}, RN_PLANES[4] = {32, 64, 128, 256}, RN_STRIDE[4] = {1, 2, 2, 2};
@@ -75,19 +77,67 @@ static size_t rn_layout(std::vector<RnConv>& convs) {
     return off;
 }
 
-// the convolutions of layer1 .. layer4 at T frames in launch order: per block conv1, conv2, the shortcut (from the block's
-// input), conv3 + residual.  Slots: 3 blk the block's input, then conv1, conv2, the output.
-static std::vector<RnPlanStep> rn_plan(int T) {
+// The batch of a run at the four spatial levels l = 0 .. 3 (H_l = 64 >> l rows, a window's width W_l = rn_out(., 2) of
+// its frames l times): M[l] positions in all.  Uniform: every window W[l] wide.  Ragged: window b is wid[l n + b] wide
+// and its [H_l][W_{b,l}][C] block starts at position pos[l (n + 1) + b]; pos[l (n + 1) + n] = M[l].  vbx_amd/xvector.py:
+// ragged_layout is the same in numpy.
+constexpr int RN_LEVELS = 4;
+struct RnLevels {
+    int n = 0;
+    bool ragged = false;
+    int W[RN_LEVELS] = {};
+    long long M[RN_LEVELS] = {};
+    std::vector<long long> pos;                                // [4][n + 1]
+    std::vector<int> wid;                                      // [4][n]
+    const long long* d_pos = nullptr;                          // their device copies
+    const int* d_wid = nullptr;
+    int H(int l) const { return RN_MEL >> l; }
+    // the kernels' view of a convolution from level li to level lo
+    vbx::RnRag rag(int li, int lo) const {
+        return vbx::RnRag{d_pos + (size_t)li * (n + 1), d_pos + (size_t)lo * (n + 1), d_wid + (size_t)li * n, d_wid + (size_t)lo * n, n};
+    }
+};
+
+static RnLevels rn_levels_uniform(int n, int T) {
+    RnLevels g;
+    g.n = n;
+    for (int l = 0, W = T; l < RN_LEVELS; ++l, W = rn_out(W, 2)) {
+        g.W[l] = W;
+        g.M[l] = (long long)n * g.H(l) * W;
+    }
+    return g;
+}
+
+static RnLevels rn_levels_ragged(int n, const int32_t* T) {
+    RnLevels g;
+    g.n = n;
+    g.ragged = true;
+    g.pos.assign((size_t)RN_LEVELS * (n + 1), 0);
+    g.wid.resize((size_t)RN_LEVELS * n);
+    for (int l = 0; l < RN_LEVELS; ++l) {
+        long long* pos = &g.pos[(size_t)l * (n + 1)];
+        for (int b = 0; b < n; ++b) {
+            const int W = l == 0 ? T[b] : rn_out(g.wid[(size_t)(l - 1) * n + b], 2);
+            g.wid[(size_t)l * n + b] = W;
+            pos[b + 1] = pos[b] + (long long)g.H(l) * W;
+        }
+        g.M[l] = pos[n];
+    }
+    return g;
+}
+
+// the convolutions of layer1 .. layer4 in launch order: per block conv1, conv2, the shortcut (from the block's input),
+// conv3 + residual.  Slots: 3 blk the block's input, then conv1, conv2, the output.
+static std::vector<RnPlanStep> rn_plan() {
     std::vector<RnPlanStep> plan;
-    int H = RN_MEL, W = T, k = 1, x = RN_X0, s0 = 0;
+    int lvl = 0, k = 1, x = RN_X0, s0 = 0;
     rn_for_blocks([&](int L, int, int, int s, bool first) {
         const int y = x == RN_X0 ? RN_X1 : RN_X0;
-        plan.push_back({k, x, RN_T1, RN_NBUF, H, W, 1, s0, s0 + 1, L});
-        plan.push_back({k + 1, RN_T1, RN_T2, RN_NBUF, H, W, 1, s0 + 1, s0 + 2, L});
-        if (first) plan.push_back({k + 3, x, RN_SC, RN_NBUF, H, W, 0, s0, -1, L});
-        H = rn_out(H, s);
-        W = rn_out(W, s);
-        plan.push_back({k + 2, RN_T2, y, first ? RN_SC : x, H, W, 1, s0 + 2, s0 + 3, L});
+        plan.push_back({k, x, RN_T1, RN_NBUF, lvl, 1, s0, s0 + 1, L});
+        plan.push_back({k + 1, RN_T1, RN_T2, RN_NBUF, lvl, 1, s0 + 1, s0 + 2, L});
+        if (first) plan.push_back({k + 3, x, RN_SC, RN_NBUF, lvl, 0, s0, -1, L});
+        lvl += s == 2;
+        plan.push_back({k + 2, RN_T2, y, first ? RN_SC : x, lvl, 1, s0 + 2, s0 + 3, L});
         k += first ? 4 : 3;
         x = y;
         s0 += 3;
@@ -105,11 +155,19 @@ struct RnCall {
     unsigned* ay = nullptr;
     const vbx::h8* wf = nullptr;                               // the weights' fragments and exponents
     const int* we = nullptr;
+    vbx::RnRag g;                                              // a ragged batch (g.pos_out set): H, Cin, Cout, M and g say it all
 };
 
 static RnCall rn_call(int ks, int stride, int n, int H, int W, int Cin, int Cout, int relu) {
     const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
     return RnCall{ks, stride, H, W, Cin, Ho, Wo, Cout, relu, (long long)n * Ho * Wo};
+}
+
+// the same over a ragged batch of windows of H rows, M output positions in all
+static RnCall rn_call_ragged(int ks, int stride, int H, int Cin, int Cout, int relu, const vbx::RnRag& g, long long M) {
+    RnCall c{ks, stride, H, 0, Cin, rn_out(H, stride), 0, Cout, relu, M};
+    c.g = g;
+    return c;
 }
 
 // the instantiations of both convolution kernels: every (KS, S) at every BN x BM tile
@@ -128,12 +186,18 @@ template <int I = 0> static bool rn_launch(hipStream_t st, const RnCall& c, int 
         constexpr int KS = RN_KS_STRIDE[I / 5][0], S = RN_KS_STRIDE[I / 5][1], bn = RN_TILES[I % 5][0], bm = RN_TILES[I % 5][1];
         if (c.ks != KS || c.stride != S || BN != bn || BM != bm) return rn_launch<I + 1>(st, c, BN, BM, mode);
         const dim3 grid((unsigned)((c.M + bm - 1) / bm), (unsigned)(c.Cout / bn)), blk(256);
-        if (mode == VBX_GEMM_SPLIT)
+        if (c.g.pos_out && mode == VBX_GEMM_SPLIT)
+            hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, bn, bm, true>), grid, blk, 0, st, c.x, c.ax, c.wf, c.we, c.b, c.res, c.y,
+                               c.ay, c.H, c.W, c.Cin, c.Ho, c.Wo, c.Cout, c.M, c.relu, RnGeom<true>{c.g});
+        else if (c.g.pos_out)
+            hipLaunchKernelGGL((resnet_conv_kernel<KS, S, bn, bm, true>), grid, blk, 0, st, c.x, c.w, c.b, c.res, c.y, c.H, c.W, c.Cin,
+                               c.Ho, c.Wo, c.Cout, c.M, c.relu, RnGeom<true>{c.g});
+        else if (mode == VBX_GEMM_SPLIT)
             hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, bn, bm>), grid, blk, 0, st, c.x, c.ax, c.wf, c.we, c.b, c.res, c.y, c.ay,
-                               c.H, c.W, c.Cin, c.Ho, c.Wo, c.Cout, c.M, c.relu);
+                               c.H, c.W, c.Cin, c.Ho, c.Wo, c.Cout, c.M, c.relu, RnGeom<false>{});
         else
             hipLaunchKernelGGL((resnet_conv_kernel<KS, S, bn, bm>), grid, blk, 0, st, c.x, c.w, c.b, c.res, c.y, c.H, c.W, c.Cin, c.Ho,
-                               c.Wo, c.Cout, c.M, c.relu);
+                               c.Wo, c.Cout, c.M, c.relu, RnGeom<false>{});
         return true;
     }
     return false;
@@ -143,6 +207,12 @@ template <int I = 0> static bool rn_launch(hipStream_t st, const RnCall& c, int 
 static void rn_amax(hipStream_t st, const float* x, int n, long long per_window, unsigned* amax) {
     const int bpw = (int)std::min<long long>(64, (per_window / 4 + 255) / 256);
     hipLaunchKernelGGL(resnet_amax_kernel, dim3((unsigned)n * bpw), dim3(256), 0, st, x, per_window, bpw, amax);
+}
+
+// the same for a ragged batch of M positions of C channels (a multiple of 4), window b at positions pos[b] .. pos[b + 1]
+static void rn_amax_ragged(hipStream_t st, const float* x, int n, const long long* pos, long long M, int C, unsigned* amax) {
+    const int bpw = (int)std::max<long long>(1, std::min<long long>(64, (M / n * C / 4 + 255) / 256));
+    hipLaunchKernelGGL(resnet_amax_ragged_kernel, dim3((unsigned)n * bpw), dim3(256), 0, st, x, pos, C, bpw, amax);
 }
 
 // w [K][Cout] f32 (K a multiple of 16, Cout of 32) -> frag [K / 16][Cout / 32][hi | lo][64][8] f16 bits, e [Cout]: the B
@@ -238,6 +308,118 @@ struct RnStep {
     }
 };
 
+// n and T of a ragged call
+static int rn_check_lengths(vbx_ctx* ctx, const char* name, int32_t n, const int32_t* T) {
+    if (n <= 0) FAIL(ctx, VBX_ERR_INVALID, "%s: n = %d windows, need at least one", name, n);
+    if (!T) FAIL(ctx, VBX_ERR_INVALID, "%s: T must not be NULL", name);
+    for (int b = 0; b < n; ++b)
+        if (T[b] <= 0) FAIL(ctx, VBX_ERR_INVALID, "%s: window %d has T = %d frames, need at least 1", name, b, T[b]);
+    return VBX_OK;
+}
+
+// ragged: g's tables to the device (the stream is idle between runs: every run ends with a synchronize)
+static int rn_upload_levels(vbx_resnet* net, RnLevels& g) {
+    vbx_ctx* ctx = net->ctx;
+    int rc = fb_reserve(ctx, &net->d_pos, &net->cap_pos, g.pos.size());
+    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_wid, &net->cap_wid, g.wid.size());
+    if (rc != VBX_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(net->d_pos, g.pos.data(), sizeof(long long) * g.pos.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(net->d_wid, g.wid.data(), sizeof(int) * g.wid.size(), hipMemcpyHostToDevice, ctx->stream));
+    g.d_pos = net->d_pos;
+    g.d_wid = net->d_wid;
+    return VBX_OK;
+}
+
+// the network over the batch g, uniform or ragged: x is g.M[0] floats (the windows' [64][T] blocks)
+static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x, int x_on_device, float* out, int out_on_device) {
+    vbx_ctx* ctx = net->ctx;
+    const int n = g.n;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // workspace: every buffer at the largest output a step writes to it, the ping-pong pair alike (x[0] also takes the
+    // stem's output)
+    size_t need[RN_NBUF] = {(size_t)g.M[0] * 32};
+    for (const RnPlanStep& s : net->plan) {
+        const RnConv& c = net->convs[s.conv];
+        need[s.out] = std::max(need[s.out], (size_t)g.M[s.lvl + (c.stride == 2)] * c.cout);
+    }
+    need[RN_X0] = need[RN_X1] = std::max(need[RN_X0], need[RN_X1]);
+    int rc = VBX_OK;
+    for (int i = 0; i < RN_NBUF && rc == VBX_OK; ++i) rc = fb_reserve(ctx, &net->d_buf[i], &net->cap_buf[i], need[i]);
+    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_pool, &net->cap_pool, (size_t)n * RN_POOL);
+    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_out, &net->cap_out, (size_t)n * net->Ep);
+    if (rc == VBX_OK && !x_on_device) rc = fb_reserve(ctx, &net->d_in, &net->cap_in, (size_t)g.M[0]);
+    const bool split = net->gemm == VBX_GEMM_SPLIT;
+    if (rc == VBX_OK && split) rc = fb_reserve(ctx, &net->d_amax, &net->cap_amax, (size_t)RN_AMAX_SLOTS * n);
+    if (rc == VBX_OK && g.ragged) rc = rn_upload_levels(net, g);
+    if (rc != VBX_OK) return rc;
+    net->gemm_last = net->gemm;
+    if (split) HIPCHK(ctx, hipMemsetAsync(net->d_amax, 0, sizeof(unsigned) * RN_AMAX_SLOTS * (size_t)n, st));
+    auto slot = [&](int s) { return split && s >= 0 ? net->d_amax + (size_t)s * n : nullptr; };
+    const float* xin = x;
+    if (!x_on_device) {
+        HIPCHK(ctx, hipMemcpyAsync(net->d_in, x, sizeof(float) * (size_t)g.M[0], hipMemcpyHostToDevice, st));
+        xin = net->d_in;
+    }
+    const float* P = net->d_par;
+    const RnConv& c0 = net->convs[0];
+    HIPCHK(ctx, hipEventRecord(net->ev[0], st));
+    const long long tot0 = g.M[0] * 32;
+    const dim3 grid0((unsigned)((tot0 + 255) / 256));
+    if (g.ragged)
+        hipLaunchKernelGGL(resnet_stem_ragged_kernel, grid0, dim3(256), 0, st, xin, P + c0.w, P + c0.b, net->d_buf[RN_X0], g.d_pos,
+                           g.d_wid, n, tot0);
+    else
+        hipLaunchKernelGGL(resnet_stem_kernel, grid0, dim3(256), 0, st, xin, P + c0.w, P + c0.b, net->d_buf[RN_X0], g.W[0], tot0);
+    if (split) {                                               // (the stem itself stays as it is)
+        if (g.ragged) rn_amax_ragged(st, net->d_buf[RN_X0], n, g.d_pos, g.M[0], 32, slot(0));
+        else rn_amax(st, net->d_buf[RN_X0], n, (long long)RN_MEL * g.W[0] * 32, slot(0));
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(net->ev[1], st));
+    int stage = 0;
+    for (const RnPlanStep& s : net->plan) {
+        if (s.stage != stage) HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
+        stage = s.stage;
+        const RnConv& c = net->convs[s.conv];
+        const int lo = s.lvl + (c.stride == 2);
+        RnCall call = g.ragged ? rn_call_ragged(c.ks, c.stride, g.H(s.lvl), c.cin, c.cout, s.relu, g.rag(s.lvl, lo), g.M[lo])
+                               : rn_call(c.ks, c.stride, n, g.H(s.lvl), g.W[s.lvl], c.cin, c.cout, s.relu);
+        call.x = net->d_buf[s.in];
+        call.w = P + c.w;
+        call.b = P + c.b;
+        call.res = s.res == RN_NBUF ? nullptr : net->d_buf[s.res];
+        call.y = net->d_buf[s.out];
+        call.ax = slot(s.ain);
+        call.wf = net->d_wf + c.wf;
+        call.we = net->d_we + c.we;
+        call.ay = slot(s.aout);
+        if (!rn_conv(st, call, net->gemm)) FAIL(ctx, VBX_ERR_INVALID, "%s: no kernel for convolution %d", name, s.conv);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
+    const RnPlanStep& last = net->plan.back();
+    const long long totp = (long long)n * RN_H4 * RN_C4;
+    const dim3 gridp((unsigned)((totp + 255) / 256));
+    if (g.ragged)
+        hipLaunchKernelGGL(resnet_pool_ragged_kernel, gridp, dim3(256), 0, st, net->d_buf[last.out], net->d_pool,
+                           g.d_pos + (size_t)3 * (n + 1), g.d_wid + (size_t)3 * n, totp);
+    else
+        hipLaunchKernelGGL(resnet_pool_kernel, gridp, dim3(256), 0, st, net->d_buf[last.out], net->d_pool, g.W[3], totp);
+    RnCall emb = rn_call(1, 1, n, 1, 1, RN_POOL, net->Ep, 0);  // (exact in both modes)
+    emb.x = net->d_pool;
+    emb.w = net->d_emb_w;
+    emb.b = net->d_emb_b;
+    emb.y = net->d_out;
+    rn_conv(st, emb, VBX_GEMM_EXACT);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(net->ev[6], st));
+    HIPCHK(ctx, hipMemcpy2DAsync(out, sizeof(float) * net->E, net->d_out, sizeof(float) * net->Ep, sizeof(float) * net->E, (size_t)n,
+                                 out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return VBX_OK;
+}
+
 extern "C" {
 
 int vbx_resnet_destroy(vbx_resnet* net) {
@@ -246,7 +428,7 @@ int vbx_resnet_destroy(vbx_resnet* net) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (void* p : {(void*)net->d_par, (void*)net->d_emb_w, (void*)net->d_emb_b, (void*)net->d_in, (void*)net->d_pool,
-                    (void*)net->d_out, (void*)net->d_wf, (void*)net->d_we, (void*)net->d_amax})
+                    (void*)net->d_out, (void*)net->d_wf, (void*)net->d_we, (void*)net->d_amax, (void*)net->d_pos, (void*)net->d_wid})
         ctx_free(ctx, p);
     for (float* p : net->d_buf) ctx_free(ctx, p);
     for (auto& e : net->ev)
@@ -264,6 +446,7 @@ int vbx_resnet_create(vbx_ctx* ctx, int32_t embed_dim, const float* params, int6
     net->E = embed_dim;
     net->Ep = round_up(embed_dim, 32);
     const size_t nconv = rn_layout(net->convs);
+    net->plan = rn_plan();
     const size_t want = nconv + (size_t)RN_POOL * embed_dim + embed_dim;
     if ((size_t)n_params != want) {
         delete net;
@@ -330,84 +513,39 @@ int vbx_resnet_input(vbx_resnet* net, int32_t n, int32_t T, float** d_in) {
     return VBX_OK;
 }
 
+int vbx_resnet_input_ragged(vbx_resnet* net, int32_t n, const int32_t* T, float** d_in) {
+    if (!net) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = net->ctx;
+    const int rc0 = rn_check_lengths(ctx, "vbx_resnet_input_ragged", n, T);
+    if (rc0 != VBX_OK) return rc0;
+    if (!d_in) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_input_ragged: d_in must not be NULL");
+    size_t frames = 0;
+    for (int b = 0; b < n; ++b) frames += (size_t)T[b];
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (a smaller buffer may still be read by queued work)
+    const int rc = fb_reserve(ctx, &net->d_in, &net->cap_in, frames * RN_MEL);
+    if (rc != VBX_OK) return rc;
+    *d_in = net->d_in;
+    return VBX_OK;
+}
+
 int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_on_device, float* out, int out_on_device) {
     if (!net) return VBX_ERR_INVALID;
     vbx_ctx* ctx = net->ctx;
     if (!x || !out || n <= 0 || T <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run: bad argument");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (net->plan_T != T) {
-        net->plan = rn_plan(T);
-        net->plan_T = T;
-    }
-    // workspace for (n, T): every buffer at the largest output a step writes to it, the ping-pong pair alike (x[0] also
-    // takes the stem's output)
-    size_t need[RN_NBUF] = {(size_t)n * RN_MEL * T * 32};
-    for (const RnPlanStep& s : net->plan) {
-        const RnConv& c = net->convs[s.conv];
-        need[s.out] = std::max(need[s.out], (size_t)n * rn_out(s.H, c.stride) * rn_out(s.W, c.stride) * c.cout);
-    }
-    need[RN_X0] = need[RN_X1] = std::max(need[RN_X0], need[RN_X1]);
-    int rc = VBX_OK;
-    for (int i = 0; i < RN_NBUF && rc == VBX_OK; ++i) rc = fb_reserve(ctx, &net->d_buf[i], &net->cap_buf[i], need[i]);
-    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_pool, &net->cap_pool, (size_t)n * RN_POOL);
-    if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_out, &net->cap_out, (size_t)n * net->Ep);
-    if (rc == VBX_OK && !x_on_device) rc = fb_reserve(ctx, &net->d_in, &net->cap_in, (size_t)n * RN_MEL * T);
-    const bool split = net->gemm == VBX_GEMM_SPLIT;
-    if (rc == VBX_OK && split) rc = fb_reserve(ctx, &net->d_amax, &net->cap_amax, (size_t)RN_AMAX_SLOTS * n);
+    RnLevels g = rn_levels_uniform(n, T);
+    return rn_run(net, "vbx_resnet_run", g, x, x_on_device, out, out_on_device);
+}
+
+int vbx_resnet_run_ragged(vbx_resnet* net, int32_t n, const int32_t* T, const float* x, int x_on_device, float* out,
+                          int out_on_device) {
+    if (!net) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = net->ctx;
+    const int rc = rn_check_lengths(ctx, "vbx_resnet_run_ragged", n, T);
     if (rc != VBX_OK) return rc;
-    net->gemm_last = net->gemm;
-    if (split) HIPCHK(ctx, hipMemsetAsync(net->d_amax, 0, sizeof(unsigned) * RN_AMAX_SLOTS * (size_t)n, st));
-    auto slot = [&](int s) { return split && s >= 0 ? net->d_amax + (size_t)s * n : nullptr; };
-    const float* xin = x;
-    if (!x_on_device) {
-        HIPCHK(ctx, hipMemcpyAsync(net->d_in, x, sizeof(float) * (size_t)n * RN_MEL * T, hipMemcpyHostToDevice, st));
-        xin = net->d_in;
-    }
-    const float* P = net->d_par;
-    const RnConv& c0 = net->convs[0];
-    HIPCHK(ctx, hipEventRecord(net->ev[0], st));
-    const long long tot0 = (long long)n * RN_MEL * T * 32;
-    hipLaunchKernelGGL(resnet_stem_kernel, dim3((unsigned)((tot0 + 255) / 256)), dim3(256), 0, st, xin, P + c0.w, P + c0.b,
-                       net->d_buf[RN_X0], T, tot0);
-    if (split) rn_amax(st, net->d_buf[RN_X0], n, (long long)RN_MEL * T * 32, slot(0));   // (the stem itself stays as it is)
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(net->ev[1], st));
-    int stage = 0;
-    for (const RnPlanStep& s : net->plan) {
-        if (s.stage != stage) HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
-        stage = s.stage;
-        const RnConv& c = net->convs[s.conv];
-        RnCall call = rn_call(c.ks, c.stride, n, s.H, s.W, c.cin, c.cout, s.relu);
-        call.x = net->d_buf[s.in];
-        call.w = P + c.w;
-        call.b = P + c.b;
-        call.res = s.res == RN_NBUF ? nullptr : net->d_buf[s.res];
-        call.y = net->d_buf[s.out];
-        call.ax = slot(s.ain);
-        call.wf = net->d_wf + c.wf;
-        call.we = net->d_we + c.we;
-        call.ay = slot(s.aout);
-        if (!rn_conv(st, call, net->gemm)) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run: no kernel for convolution %d", s.conv);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
-    const RnPlanStep& last = net->plan.back();
-    const long long totp = (long long)n * RN_H4 * RN_C4;
-    hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((totp + 255) / 256)), dim3(256), 0, st, net->d_buf[last.out], net->d_pool,
-                       last.W, totp);
-    RnCall emb = rn_call(1, 1, n, 1, 1, RN_POOL, net->Ep, 0);  // (exact in both modes)
-    emb.x = net->d_pool;
-    emb.w = net->d_emb_w;
-    emb.b = net->d_emb_b;
-    emb.y = net->d_out;
-    rn_conv(st, emb, VBX_GEMM_EXACT);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(net->ev[6], st));
-    HIPCHK(ctx, hipMemcpy2DAsync(out, sizeof(float) * net->E, net->d_out, sizeof(float) * net->Ep, sizeof(float) * net->E, (size_t)n,
-                                 out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return VBX_OK;
+    if (!x || !out) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run_ragged: x and out must not be NULL");
+    RnLevels g = rn_levels_ragged(n, T);
+    return rn_run(net, "vbx_resnet_run_ragged", g, x, x_on_device, out, out_on_device);
 }
 
 int vbx_resnet_times(vbx_resnet* net, float* ms) {
@@ -440,9 +578,24 @@ int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm) {
     return VBX_OK;
 }
 
-// vbx_resnet_conv and vbx_resnet_conv_gemm: one convolution on host arrays in either mode
+// the tables of one ragged convolution step on host arrays: n windows of H rows and Wv[b] columns, stride s
+struct RnStepTables {
+    std::vector<long long> pos;                                // [2][n + 1]: the input's, the output's
+    std::vector<int> wid;                                      // [2][n]
+    RnStepTables(int n, int H, const int32_t* Wv, int s) : pos(2 * (size_t)(n + 1), 0), wid(2 * (size_t)n) {
+        for (int b = 0; b < n; ++b) {
+            wid[b] = Wv[b];
+            wid[n + b] = rn_out(Wv[b], s);
+            pos[b + 1] = pos[b] + (long long)H * wid[b];
+            pos[n + 1 + b + 1] = pos[n + 1 + b] + (long long)rn_out(H, s) * wid[n + b];
+        }
+    }
+};
+
+// vbx_resnet_conv, vbx_resnet_conv_gemm and vbx_resnet_conv_ragged: one convolution on host arrays in either mode; Wv: the
+// windows' widths of a ragged batch, or null (then all of them W wide)
 static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W,
-                        int32_t Cin, int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu,
+                        const int32_t* Wv, int32_t Cin, int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu,
                         int32_t bn, int32_t bm, float* y, int64_t pad, float* amax_y) {
     if (!ctx) return VBX_ERR_INVALID;
     int rc = rn_check_gemm(ctx, name, gemm);
@@ -455,6 +608,16 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
         FAIL(ctx, VBX_ERR_INVALID, "%s: kernel size %d stride %d: built for 1 or 3 at stride 1 or 2", name, ks, stride);
     if (Cin % RN_BK != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cin = %d is not a multiple of %d", name, Cin, RN_BK);
     RnCall c = rn_call(ks, stride, n, H, W, Cin, Cout, relu ? 1 : 0);
+    size_t nx = (size_t)n * H * W * Cin;
+    std::vector<long long> pos;                                // (outlive the copies, as wf and we below)
+    std::vector<int> wid;
+    if (Wv) {
+        RnStepTables t(n, H, Wv, stride);
+        pos.swap(t.pos);
+        wid.swap(t.wid);
+        c = rn_call_ragged(ks, stride, H, Cin, Cout, relu ? 1 : 0, RnRag{}, pos[2 * (size_t)n + 1]);
+        nx = (size_t)pos[n] * Cin;
+    }
     int BN = bn, BM = bm;
     if (bn == 0 && bm == 0) {
         if (Cout % 32 != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of 32", name, Cout);
@@ -467,7 +630,14 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
     RnStep s(ctx);
     const size_t ny = (size_t)c.M * Cout + 2 * (size_t)pad;
     float* dy;
-    rc = s.up(x, (size_t)n * H * W * Cin, &c.x);
+    rc = s.up(x, nx, &c.x);
+    if (rc == VBX_OK && Wv) {
+        long long* dpos;
+        int* dwid;
+        rc = s.up_bytes(pos.data(), sizeof(long long) * pos.size(), &dpos);
+        if (rc == VBX_OK) rc = s.up_bytes(wid.data(), sizeof(int) * wid.size(), &dwid);
+        if (rc == VBX_OK) c.g = RnRag{dpos, dpos + n + 1, dwid, dwid + n, n};
+    }
     if (rc == VBX_OK) rc = s.up(bias, (size_t)Cout, &c.b);
     if (rc == VBX_OK) rc = s.up(res, (size_t)c.M * Cout, &c.res);
     if (rc == VBX_OK) rc = s.up(y, ny, &dy);
@@ -485,7 +655,8 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
         if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &dax);
         if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &c.ay);
         if (rc != VBX_OK) return rc;
-        rn_amax(ctx->stream, c.x, n, (long long)H * W * Cin, dax);
+        if (Wv) rn_amax_ragged(ctx->stream, c.x, n, c.g.pos_in, pos[n], Cin, dax);
+        else rn_amax(ctx->stream, c.x, n, (long long)H * W * Cin, dax);
         c.ax = dax;
     }
     if (!rn_launch(ctx->stream, c, BN, BM, gemm)) FAIL(ctx, VBX_ERR_INVALID, "%s: no kernel for this convolution", name);
@@ -496,14 +667,24 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
 int vbx_resnet_conv(vbx_ctx* ctx, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                     const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn, int32_t bm,
                     float* y, int64_t pad) {
-    return rn_conv_step("vbx_resnet_conv", ctx, VBX_GEMM_EXACT, ks, stride, n, H, W, Cin, Cout, x, w, bias, res, relu, bn, bm, y, pad,
+    return rn_conv_step("vbx_resnet_conv", ctx, VBX_GEMM_EXACT, ks, stride, n, H, W, nullptr, Cin, Cout, x, w, bias, res, relu, bn, bm, y, pad,
                         nullptr);
 }
 
 int vbx_resnet_conv_gemm(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W, int32_t Cin,
                          int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn,
                          int32_t bm, float* y, int64_t pad, float* amax_y) {
-    return rn_conv_step("vbx_resnet_conv_gemm", ctx, gemm, ks, stride, n, H, W, Cin, Cout, x, w, bias, res, relu, bn, bm, y, pad,
+    return rn_conv_step("vbx_resnet_conv_gemm", ctx, gemm, ks, stride, n, H, W, nullptr, Cin, Cout, x, w, bias, res, relu, bn, bm, y,
+                        pad, amax_y);
+}
+
+int vbx_resnet_conv_ragged(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, const int32_t* W, int32_t Cin,
+                           int32_t Cout, const float* x, const float* w, const float* bias, const float* res, int relu, int32_t bn,
+                           int32_t bm, float* y, int64_t pad, float* amax_y) {
+    if (!ctx) return VBX_ERR_INVALID;
+    const int rc = rn_check_lengths(ctx, "vbx_resnet_conv_ragged", n, W);
+    if (rc != VBX_OK) return rc;
+    return rn_conv_step("vbx_resnet_conv_ragged", ctx, gemm, ks, stride, n, H, 1, W, Cin, Cout, x, w, bias, res, relu, bn, bm, y, pad,
                         amax_y);
 }
 
@@ -523,6 +704,55 @@ int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const fl
     hipLaunchKernelGGL(resnet_stem_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dw, db, dy + pad, T,
                        total);
     return s.down("vbx_resnet_stem", y, dy, ny);
+}
+
+int vbx_resnet_stem_ragged(vbx_ctx* ctx, int32_t n, const int32_t* T, const float* x, const float* w, const float* bias, float* y,
+                           int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    int rc = rn_check_lengths(ctx, "vbx_resnet_stem_ragged", n, T);
+    if (rc != VBX_OK) return rc;
+    if (!x || !w || !bias || !y || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_stem_ragged: x, w, bias and y must not be NULL, pad not negative");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnStep s(ctx);
+    const RnStepTables t(n, RN_MEL, T, 1);
+    const long long total = t.pos[n] * 32;
+    const size_t ny = (size_t)total + 2 * (size_t)pad;
+    float *dx, *dw, *db, *dy;
+    long long* dpos;
+    int* dwid;
+    rc = s.up(x, (size_t)t.pos[n], &dx);
+    if (rc == VBX_OK) rc = s.up(w, 9 * 32, &dw);
+    if (rc == VBX_OK) rc = s.up(bias, 32, &db);
+    if (rc == VBX_OK) rc = s.up(y, ny, &dy);
+    if (rc == VBX_OK) rc = s.up_bytes(t.pos.data(), sizeof(long long) * (n + 1), &dpos);
+    if (rc == VBX_OK) rc = s.up_bytes(t.wid.data(), sizeof(int) * n, &dwid);
+    if (rc != VBX_OK) return rc;
+    hipLaunchKernelGGL(resnet_stem_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dw, db,
+                       dy + pad, dpos, dwid, n, total);
+    return s.down("vbx_resnet_stem_ragged", y, dy, ny);
+}
+
+int vbx_resnet_pool_ragged(vbx_ctx* ctx, int32_t n, const int32_t* W4, const float* x, float* out, int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    int rc = rn_check_lengths(ctx, "vbx_resnet_pool_ragged", n, W4);
+    if (rc != VBX_OK) return rc;
+    if (!x || !out || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_pool_ragged: x and out must not be NULL, pad not negative");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnStep s(ctx);
+    const RnStepTables t(n, RN_H4, W4, 1);
+    const long long total = (long long)n * RN_H4 * RN_C4;
+    const size_t ny = (size_t)n * RN_POOL + 2 * (size_t)pad;
+    float *dx, *dy;
+    long long* dpos;
+    int* dwid;
+    rc = s.up(x, (size_t)t.pos[n] * RN_C4, &dx);
+    if (rc == VBX_OK) rc = s.up(out, ny, &dy);
+    if (rc == VBX_OK) rc = s.up_bytes(t.pos.data(), sizeof(long long) * (n + 1), &dpos);
+    if (rc == VBX_OK) rc = s.up_bytes(t.wid.data(), sizeof(int) * n, &dwid);
+    if (rc != VBX_OK) return rc;
+    hipLaunchKernelGGL(resnet_pool_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dy + pad, dpos,
+                       dwid, total);
+    return s.down("vbx_resnet_pool_ragged", out, dy, ny);
 }
 
 int vbx_resnet_pool(vbx_ctx* ctx, int32_t n, int32_t W4, const float* x, float* out, int64_t pad) {

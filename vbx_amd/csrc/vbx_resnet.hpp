@@ -14,6 +14,12 @@
 // The embedding Linear(16384 -> E) is resnet_conv_kernel at H = W = 1.  No atomics and no split of K: every output element
 // is one thread's fixed-order chain, so a window's embedding does not depend on the batch it is run in.  ReLU keeps NaN as
 // F.relu does (a NaN window must reach the embedding: predict.py skips it).
+//
+// Ragged batches (windows of mixed lengths in one run): at spatial level l (H_l = 64, 32, 16, 8) an activation tensor is the
+// concatenation of the windows' [H_l][W_{b,l}][C] blocks, window b starting at position pos_l[b] (RnRag).  The *_ragged
+// kernels are the same code with one change: a row m finds its window by a search of pos (rn_window) and takes its widths
+// and its input base from the tables, where the uniform kernels divide by Ho Wo (rn_row).  Taps, k order and zeros are the
+// same, so every window has the bits it has when it is run alone.
 #pragma once
 #include "vbx_device.hpp"
 
@@ -33,13 +39,69 @@ __device__ __forceinline__ float rn_relu(float v) { return v < 0.0f ? 0.0f : v; 
 // the row of element r of a lane's 32 x 32 D fragment (its column is lane & 31); kh = lane >> 5
 __device__ __forceinline__ int rn_drow(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
 
+// a ragged batch at one convolution: window b's block starts at position pos_in[b] of the input and pos_out[b] of the
+// output (both [n + 1], ascending from 0, pos[n] = M) and is wid_in[b] / wid_out[b] positions wide; every window has the
+// same H.
+struct RnRag {
+    const long long* pos_in = nullptr;
+    const long long* pos_out = nullptr;
+    const int* wid_in = nullptr;
+    const int* wid_out = nullptr;
+    int n = 0;
+};
+// the last argument of both convolution kernels: the tables in the ragged instantiations, nothing in the uniform ones
+template <bool RAG> struct RnGeom {};
+template <> struct RnGeom<true> {
+    RnRag t;
+};
+
+// the window of position m < pos[n]: the last b with pos[b] <= m (an upper bound minus one: log2 n steps)
+__device__ __forceinline__ int rn_window(const long long* __restrict__ pos, int n, long long m) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pos[mid] <= m) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// output row m -> its window b, its position (ho, wo) there, the width W of the window's input and the input's base xb
+// (floats).  A row past M (valid false) gets zeros.
+struct RnRow {
+    long long b, xb;
+    int ho, wo, W;
+};
+template <bool RAG>
+__device__ __forceinline__ RnRow rn_row(long long m, bool valid, int H, int W, int Cin, int Ho, int Wo, const RnGeom<RAG>& g) {
+    RnRow r;
+    if constexpr (RAG) {
+        r.b = valid ? rn_window(g.t.pos_out, g.t.n, m) : 0;
+        const int wout = g.t.wid_out[r.b], rem = valid ? (int)(m - g.t.pos_out[r.b]) : 0;
+        r.ho = rem / wout;
+        r.wo = rem - r.ho * wout;
+        r.W = g.t.wid_in[r.b];
+        r.xb = g.t.pos_in[r.b] * Cin;
+    } else {
+        const long long hw = (long long)Ho * Wo;
+        r.b = valid ? m / hw : 0;
+        const int rem = valid ? (int)(m - r.b * hw) : 0;
+        r.ho = rem / Wo;
+        r.wo = rem - r.ho * Wo;
+        r.W = W;
+        r.xb = r.b * H * W * (long long)Cin;
+    }
+    return r;
+}
+
 // y[m][n] = act(sum_k A[m][k] W[k][n] + bias[n] (+ res[m][n])), A[m][(r KS + s) Cin + c] = x[b][ho S - P + r][wo S - P + s][c].
 // w [K][Cout] (row k = tap r KS + s, input channel c), Cout a multiple of BN; grid (ceil(M / BM), Cout / BN).
-template <int KS, int S, int BN, int BM>
+// RAG: a ragged batch g.t of windows of H rows, M = g.t.pos_out[g.t.n]; W, Ho and Wo are not read.
+template <int KS, int S, int BN, int BM, bool RAG = false>
 __global__ __launch_bounds__(256) void resnet_conv_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, const float* __restrict__ res,
                                                           float* __restrict__ y, int H, int W, int Cin, int Ho, int Wo,
-                                                          int Cout, long long M, int relu) {
+                                                          int Cout, long long M, int relu, RnGeom<RAG> g) {
     constexpr int P = KS / 2;
     constexpr int WM = BM / 32, WN = 4 / WM;                   // waves along M and N
     constexpr int NACC = BN / WN / 32;
@@ -58,29 +120,28 @@ __global__ __launch_bounds__(256) void resnet_conv_kernel(const float* __restric
 
     // A: BM rows x 16 k, NA float4 per thread: quad kq of rows (tid >> 2) + 64 p
     const int kq = tid & 3;
-    int hb[NA], wb[NA];
+    int hb[NA], wb[NA], wW[NA];
     long long xb[NA];
     bool mv[NA];
 #pragma unroll
     for (int p = 0; p < NA; ++p) {
         const long long m = m0 + (tid >> 2) + 64 * p;
         mv[p] = m < M;
-        const long long hw = (long long)Ho * Wo;
-        const long long b = mv[p] ? m / hw : 0;
-        const int rem = mv[p] ? (int)(m - b * hw) : 0, ho = rem / Wo, wo = rem - ho * Wo;
-        hb[p] = ho * S - P;
-        wb[p] = wo * S - P;
-        xb[p] = b * H * W * (long long)Cin;
+        const RnRow row = rn_row<RAG>(m, mv[p], H, W, Cin, Ho, Wo, g);
+        hb[p] = row.ho * S - P;
+        wb[p] = row.wo * S - P;
+        wW[p] = row.W;
+        xb[p] = row.xb;
     }
     f4 ra[NA], rb[NBL];
     auto load = [&](int k0) {
         const int tap = k0 / Cin, c0 = k0 - tap * Cin, r = tap / KS, s = tap - r * KS;
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
-            const int hi = hb[p] + r, wi = wb[p] + s;
+            const int hi = hb[p] + r, wi = wb[p] + s, Wp = RAG ? wW[p] : W;
             ra[p] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (mv[p] && hi >= 0 && hi < H && wi >= 0 && wi < W)
-                ra[p] = *reinterpret_cast<const f4*>(x + xb[p] + ((long long)hi * W + wi) * Cin + c0 + 4 * kq);
+            if (mv[p] && hi >= 0 && hi < H && wi >= 0 && wi < Wp)
+                ra[p] = *reinterpret_cast<const f4*>(x + xb[p] + ((long long)hi * Wp + wi) * Cin + c0 + 4 * kq);
         }
 #pragma unroll
         for (int q = 0; q < NBL; ++q) {
@@ -174,6 +235,32 @@ __global__ __launch_bounds__(256) void resnet_stem_kernel(const float* __restric
     y[idx] = rn_relu(acc + bias[c]);
 }
 
+// the stem over a ragged batch: x the concatenation of the windows' [64][T_b] blocks, y of their [64][T_b][32] blocks; window
+// b starts at position pos[b] of both (pos [n + 1] = 64 times the running sum of T, wid[b] = T_b); total = 32 pos[n]
+__global__ __launch_bounds__(256) void resnet_stem_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 const float* __restrict__ bias, float* __restrict__ y,
+                                                                 const long long* __restrict__ pos, const int* __restrict__ wid,
+                                                                 int n, long long total) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx & 31);
+    const long long m = idx >> 5;
+    const int b = rn_window(pos, n, m), W = wid[b], rem = (int)(m - pos[b]), h = rem / W, wo = rem - h * W;
+    const float* __restrict__ xb = x + pos[b];
+    float acc = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int hi = h + r - 1;
+        if (hi < 0 || hi >= RN_MEL) continue;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int wi = wo + s - 1;
+            if (wi >= 0 && wi < W) acc = fmaf(xb[(long long)hi * W + wi], w[(r * 3 + s) * 32 + c], acc);
+        }
+    }
+    y[idx] = rn_relu(acc + bias[c]);
+}
+
 // x [B][8][W4][1024] -> out [B][16384]: [h 1024 + c] = mean over time, [8192 + h 1024 + c] = sqrt(mean(x^2) - mean^2 + 1e-10)
 // (resnet.py:138-140, summed in f64).  The embedding matrix's columns are permuted on the host to this order.
 __global__ __launch_bounds__(256) void resnet_pool_kernel(const float* __restrict__ x, float* __restrict__ out, int W4,
@@ -185,6 +272,31 @@ __global__ __launch_bounds__(256) void resnet_pool_kernel(const float* __restric
     const int h = (int)(bh & (RN_H4 - 1));
     const long long b = bh >> 3;
     const float* __restrict__ p = x + bh * W4 * RN_C4 + c;
+    double s = 0.0, s2 = 0.0;
+    for (int t = 0; t < W4; ++t) {
+        const double v = p[(long long)t * RN_C4];
+        s += v;
+        s2 += v * v;
+    }
+    const double mean = s / W4;
+    float* __restrict__ o = out + b * RN_POOL + h * RN_C4 + c;
+    o[0] = (float)mean;
+    o[RN_POOL / 2] = (float)sqrt(s2 / W4 - mean * mean + 1e-10);
+}
+
+// the pooling over a ragged batch: x the concatenation of the windows' [8][W4_b][1024] blocks, window b at position pos[b],
+// wid[b] = W4_b frames wide: its own divisor
+__global__ __launch_bounds__(256) void resnet_pool_ragged_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                                 const long long* __restrict__ pos, const int* __restrict__ wid,
+                                                                 long long total) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx & (RN_C4 - 1));
+    const long long bh = idx >> 10;
+    const int h = (int)(bh & (RN_H4 - 1));
+    const long long b = bh >> 3;
+    const int W4 = wid[b];
+    const float* __restrict__ p = x + (pos[b] + (long long)h * W4) * RN_C4 + c;
     double s = 0.0, s2 = 0.0;
     for (int t = 0; t < W4; ++t) {
         const double v = p[(long long)t * RN_C4];

@@ -47,15 +47,48 @@ __global__ __launch_bounds__(256) void resnet_amax_kernel(const float* __restric
     if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(amax + b, (unsigned)m);
 }
 
+// the same over a ragged batch of C-channel tensors (C a multiple of 4): window b is positions pos[b] .. pos[b + 1]
+__global__ __launch_bounds__(256) void resnet_amax_ragged_kernel(const float* __restrict__ x, const long long* __restrict__ pos,
+                                                                 int C, int bpw, unsigned* __restrict__ amax) {
+    using f4 = Vec<float>::v4;
+    const long long b = blockIdx.x / bpw;
+    const int part = blockIdx.x - (int)(b * bpw);
+    const f4* __restrict__ src = reinterpret_cast<const f4*>(x + pos[b] * C);
+    const long long n4 = (pos[b + 1] - pos[b]) * C >> 2;
+    int m = 0;
+    for (long long q = (long long)part * 256 + threadIdx.x; q < n4; q += 256LL * bpw) {
+        const f4 v = src[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int a = __builtin_bit_cast(int, v[j]) & 0x7fffffff;
+            m = vmax(m, a < 0x7f800000 ? a : 0);
+        }
+    }
+    m = allreduce_max<64>(m);
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(amax + b, (unsigned)m);
+}
+
+// the window of every row of a ragged tile, kept in LDS from the prologue for the epilogue (no LDS in the uniform kernels)
+template <int BM, bool RAG> __device__ __forceinline__ int* rs_row_windows() {
+    if constexpr (RAG) {
+        __shared__ int Ws[BM];
+        return Ws;
+    } else {
+        return nullptr;
+    }
+}
+
 // resnet_conv_kernel's contract (x, bias, res, y, geometry, grid (ceil(M / BM), Cout / BN)) with
 //   amax_x [n]  max |x| per window (bits), wf / we the split weights and their per-channel exponents,
 //   amax_y [n]  or null: receives max |y| per window (zeroed beforehand)
-template <int KS, int S, int BN, int BM>
+//   RAG         a ragged batch g.t (vbx_resnet.hpp); amax_x and amax_y [g.t.n]
+template <int KS, int S, int BN, int BM, bool RAG = false>
 __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __restrict__ x, const unsigned* __restrict__ amax_x,
                                                                 const h8* __restrict__ wf, const int* __restrict__ we,
                                                                 const float* __restrict__ bias, const float* __restrict__ res,
                                                                 float* __restrict__ y, unsigned* __restrict__ amax_y, int H,
-                                                                int W, int Cin, int Ho, int Wo, int Cout, long long M, int relu) {
+                                                                int W, int Cin, int Ho, int Wo, int Cout, long long M, int relu,
+                                                                RnGeom<RAG> g) {
     constexpr int P = KS / 2;
     constexpr int WM = BM / 32, WN = 4 / WM;                   // waves along M and N
     constexpr int NACC = BN / WN / 32;
@@ -66,6 +99,7 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
     __shared__ h8 As[2 * 2 * RB * 64];                         // [k-step][hi | lo][row block][lane]
     __shared__ h8 Bs[2 * CB * 2 * 64];                         // [k-step][column block][hi | lo][lane]
     __shared__ int Es[BM];                                     // the exponent of every row's window
+    int* const Ws = rs_row_windows<BM, RAG>();                 // ragged: the window itself
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long m0 = (long long)blockIdx.x * BM;
     const int n0 = blockIdx.y * BN;
@@ -75,7 +109,7 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
 
     // A: unit (row (tid >> 2) + 64 p, k-step ks_ = (tid >> 1) & 1, half kh_ = tid & 1): 8 consecutive channels of one tap
     const int ks_ = (tid >> 1) & 1, kh_ = tid & 1;
-    int hb[NU], wb[NU], ea[NU];
+    int hb[NU], wb[NU], wW[NU], ea[NU];
     long long xb[NU];
     bool mv[NU];
 #pragma unroll
@@ -83,13 +117,15 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
         const int rl = (tid >> 2) + 64 * p;
         const long long m = m0 + rl;
         mv[p] = m < M;
-        const long long b = mv[p] ? m / hw : 0;
-        const int rem = mv[p] ? (int)(m - b * hw) : 0, ho = rem / Wo, wo = rem - ho * Wo;
-        hb[p] = ho * S - P;
-        wb[p] = wo * S - P;
-        xb[p] = b * H * W * (long long)Cin;
-        ea[p] = mv[p] ? split_exponent(__builtin_bit_cast(float, amax_x[b])) : 0;
+        const RnRow row = rn_row<RAG>(m, mv[p], H, W, Cin, Ho, Wo, g);
+        hb[p] = row.ho * S - P;
+        wb[p] = row.wo * S - P;
+        wW[p] = row.W;
+        xb[p] = row.xb;
+        ea[p] = mv[p] ? split_exponent(__builtin_bit_cast(float, amax_x[row.b])) : 0;
         if ((tid & 3) == 0) Es[rl] = ea[p];
+        if constexpr (RAG)
+            if ((tid & 3) == 0) Ws[rl] = (int)row.b;
     }
     f4 ra[NU][2];
     h8 rb[NBU];
@@ -99,10 +135,10 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
         const int tap = k / Cin, c0 = k - tap * Cin + 8 * kh_, r = tap / KS, s = tap - r * KS;
 #pragma unroll
         for (int p = 0; p < NU; ++p) {
-            const int hi = hb[p] + r, wi = wb[p] + s;
+            const int hi = hb[p] + r, wi = wb[p] + s, Wp = RAG ? wW[p] : W;
             ra[p][0] = ra[p][1] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-            if (kv && mv[p] && hi >= 0 && hi < H && wi >= 0 && wi < W) {
-                const f4* src = reinterpret_cast<const f4*>(x + xb[p] + ((long long)hi * W + wi) * Cin + c0);
+            if (kv && mv[p] && hi >= 0 && hi < H && wi >= 0 && wi < Wp) {
+                const f4* src = reinterpret_cast<const f4*>(x + xb[p] + ((long long)hi * Wp + wi) * Cin + c0);
                 ra[p][0] = src[0];
                 ra[p][1] = src[1];
             }
@@ -199,8 +235,8 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
     }
     if (amax_y && m0 + row0 < M) {                            // (wave-uniform)
         const long long mlast = m0 + row0 + 31 < M ? m0 + row0 + 31 : M - 1;
-        const long long bf = (m0 + row0) / hw;
-        if (bf == mlast / hw) {                               // the wave's 32 rows lie in one window
+        const long long bf = RAG ? Ws[row0] : (m0 + row0) / hw;
+        if (bf == (RAG ? Ws[(int)(mlast - m0)] : mlast / hw)) {   // the wave's 32 rows lie in one window
             int t = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) t = vmax(t, am[r]);
@@ -211,7 +247,7 @@ __global__ __launch_bounds__(256) void resnet_conv_split_kernel(const float* __r
             for (int r = 0; r < 16; ++r) {
                 const int t = allreduce_max<32>(am[r]);
                 const long long m = m0 + row0 + rn_drow(r, kh);
-                if (i == 0 && m < M && t > 0) atomicMax(amax_y + m / hw, (unsigned)t);
+                if (i == 0 && m < M && t > 0) atomicMax(amax_y + (RAG ? Ws[(int)(m - m0)] : m / hw), (unsigned)t);
             }
         }
     }

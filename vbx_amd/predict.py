@@ -4,8 +4,10 @@ The command line is predict.py's.  The features of a file come from the device f
 filterbank, floating CMN, windows cut straight into the model's [B, 64, 144] layout); the embedding model is either
 ResNet101 from a checkpoint in predict.py's ``--weights`` format (``--checkpoint``, run by vbx_amd.xvector in HIP, the
 windows gathered straight into its input buffer) or a TorchScript module (``--model-file``) run by PyTorch on the same
-device.  Full windows go ``--batch-size`` at a time and the tail windows are grouped by length.  The ark file and the
-segments file are the ones predict.py writes, in its order.  The dither of the next file is drawn on the host while the
+device.  Full windows go ``--batch-size`` at a time.  The other windows of a file -- one tail of its own length per VAD
+segment -- go through the ``--checkpoint`` network together, as ragged batches of at most ``--batch-size`` x ``--seg-len``
+frames (every embedding has the bits its window gives alone); a ``--model-file`` module takes them grouped by length.
+The ark file and the segments file are the ones predict.py writes, in its order.  The dither of the next file is drawn on the host while the
 device works on the current one.
 
 Not supported: ``--backend onnx`` and ``--model/--weights`` (pass the ResNet101 weights with ``--checkpoint``).
@@ -82,20 +84,46 @@ def _load(args, fn):
     return sr, sig, segs
 
 
-def embed_file(embed, fe, fn, sig, segs, sr, args):
+def ragged_batches(lengths, max_frames):
+    """Consecutive runs of the windows (indices into lengths) of at most max_frames frames in all -- at least one window
+    each: what bounds the workspace of a ragged run."""
+    out, cur, frames = [], [], 0
+    for i, n in enumerate(lengths):
+        if cur and frames + n > max_frames:
+            out.append(cur)
+            cur, frames = [], 0
+        cur.append(i)
+        frames += n
+    if cur:
+        out.append(cur)
+    return out
+
+
+def embed_file(embed, fe, fn, sig, segs, sr, args, embed_ragged=None):
     """(key, segments line, embedding) of every window of one file, in predict.py's order.  embed(fe, starts, length):
-    the embeddings [n][E] (numpy) of the windows of `length` frames from feature rows `starts`."""
+    the embeddings [n][E] (numpy) of the windows of `length` frames from feature rows `starts`.  embed_ragged(fe, starts,
+    lengths), if given, takes the windows that are not full ones, of whatever lengths, in one call; without it they are
+    grouped by length."""
     rows = fe.run([(sig, segs)])[0]
     plan = fbank.window_plan(fn, segs, sr, args.seg_len, args.seg_jump)
     emb = [None] * len(plan)
+    start = lambda i: rows[plan[i].seg] + plan[i].start
     groups = {}
     for i, w in enumerate(plan):
         groups.setdefault(w.end - w.start, []).append(i)
+    if embed_ragged is not None:
+        rest = [i for i, w in enumerate(plan) if w.end - w.start != args.seg_len]
+        groups = {n: idx for n, idx in groups.items() if n == args.seg_len}
+        lengths = [plan[i].end - plan[i].start for i in rest]
+        for part in ragged_batches(lengths, args.batch_size * args.seg_len):
+            y = embed_ragged(fe, [start(rest[j]) for j in part], [lengths[j] for j in part])
+            for j, v in zip(part, y):
+                emb[rest[j]] = v
     for length, idx in groups.items():
         step = args.batch_size if length == args.seg_len else len(idx)
         for b0 in range(0, len(idx), step):
             part = idx[b0:b0 + step]
-            y = embed(fe, [rows[plan[i].seg] + plan[i].start for i in part], length)
+            y = embed(fe, [start(i) for i in part], length)
             for i, v in zip(part, y):
                 emb[i] = v
     return [(w.key, w.line, e) for w, e in zip(plan, emb)]
@@ -116,8 +144,9 @@ def main(argv=None):
             raise SystemExit(f'--checkpoint {args.checkpoint}: {exc}')
         net = xvector.ResNet101(sd, device, gemm=args.gemm)
         del sd
-        embed = net.embed_windows
+        embed, embed_ragged = net.embed_windows, net.embed_windows_ragged
     else:
+        embed_ragged = None
         model = torch.jit.load(args.model_file, map_location=torch.device('cuda', device))
         model.eval()
 
@@ -132,7 +161,7 @@ def main(argv=None):
             sr, sig, segs = nxt.result()
             nxt = pool.submit(_load, args, file_names[k + 1]) if k + 1 < len(file_names) else None
             fe = fbank.front_end(sr, device)
-            for key, line, vec in embed_file(embed, fe, fn, sig, segs, sr, args):
+            for key, line, vec in embed_file(embed, fe, fn, sig, segs, sr, args, embed_ragged):
                 if np.isnan(vec).any():
                     logger.warning(f'NaN found, not processing: {key}{os.linesep}')
                     continue

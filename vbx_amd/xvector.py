@@ -8,7 +8,9 @@
     forward_reference       the network in f64 on the CPU from the raw checkpoint (torch.nn.functional): the referee
     forward_folded          the same from the folded, packed parameters (checks fold; run_folded: on any torch device)
     ResNet101               the device path (vbx_resnet.hpp): windows [B][64][T] -> embeddings [B][E] f32; gemm='split'
-                            runs layer1 .. layer4 on the f16 matrix cores with error-compensated operands
+                            runs layer1 .. layer4 on the f16 matrix cores with error-compensated operands; embed_ragged:
+                            windows of mixed lengths in one run, bit for bit what each gives alone
+    ragged_layout           where every window of a ragged batch sits at the network's four spatial levels
     split_terms             the representation of the split mode (x 2^e = hi + lo in f16), its one definition
     pack_split_weights      the split weights in the device's fragment order (unpack_split_weights: back)
     forward_split_emulated  the split mode's arithmetic on the CPU (torch, f32 accumulation)
@@ -65,6 +67,29 @@ def walk(T: int):
             yield (specs[k],) + hw
             k += 1
         H, W = Ho, Wo
+
+
+LEVELS = 4                                             # spatial levels of the network: 64, 32, 16, 8 rows
+
+
+def ragged_layout(lengths):
+    """The layout of a ragged batch -- windows of lengths[b] >= 1 frames, in any order -- as the device builds it
+    (vbx_host_resnet.hpp: rn_levels_ragged): -> (pos int64 [4][n + 1], wid int32 [4][n]).  At level l (64 >> l rows) window b
+    is wid[l][b] wide (the stride-2 output size applied l times to lengths[b]) and its [H_l][wid[l][b]][C] block starts at
+    position pos[l][b] of the concatenated activation tensor; pos[l][n] = M_l, all positions of the level."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.size == 0:
+        raise ValueError('ragged_layout: no windows')
+    if lengths.min() <= 0:
+        b = int(np.argmax(lengths <= 0))
+        raise ValueError(f'ragged_layout: window {b} has {int(lengths[b])} frames, need at least 1')
+    wid = np.empty((LEVELS, lengths.size), dtype=np.int64)
+    wid[0] = lengths
+    for l in range(1, LEVELS):
+        wid[l] = _out(wid[l - 1], 2)
+    pos = np.zeros((LEVELS, lengths.size + 1), dtype=np.int64)
+    pos[:, 1:] = np.cumsum(wid * (FEAT_DIM >> np.arange(LEVELS))[:, None], axis=1)
+    return pos, wid.astype(np.int32)
 
 
 def required_shapes(embed_dim: int) -> dict:
@@ -401,6 +426,51 @@ class ResNet101:
         ptr = self.dev.input_buffer(len(starts), length)
         fe.dev.windows(starts, length, dst_ptr=ptr)
         return self.dev.run(len(starts), length, x_ptr=ptr)
+
+    def embed_ragged(self, windows, lengths=None):
+        """Embeddings [n][E] of windows of mixed lengths in one run of the network; every one has the bits ``embed`` gives
+        that window alone.  windows: a list of [64][T_b] f32 arrays; or, with ``lengths`` [n], their blocks end to end as one
+        flat array of 64 sum(lengths) values -- numpy, or a torch tensor on the device (then the result is one too)."""
+        if lengths is None:
+            windows = [np.ascontiguousarray(w, dtype=np.float32) for w in windows]
+            for b, w in enumerate(windows):
+                if w.ndim != 2 or w.shape[0] != FEAT_DIM:
+                    raise ValueError(f'embed_ragged: window {b}: expected [{FEAT_DIM}][T], got {w.shape}')
+            lengths = [w.shape[1] for w in windows]
+            windows = np.concatenate([w.reshape(-1) for w in windows]) if windows else np.empty(0, np.float32)
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if lengths.size == 0:
+            return np.empty((0, self.embed_dim), dtype=np.float32)
+        if lengths.min() <= 0:
+            b = int(np.argmax(lengths <= 0))
+            raise ValueError(f'embed_ragged: window {b} has {int(lengths[b])} frames, need at least 1')
+        total = FEAT_DIM * int(lengths.sum())
+        if hasattr(windows, 'data_ptr'):
+            import torch
+            if windows.dtype != torch.float32 or not windows.is_cuda or windows.numel() != total:
+                raise ValueError(f'embed_ragged: expected a float32 tensor of {total} values on the GPU')
+            x = windows.contiguous()
+            out = torch.empty((lengths.size, self.embed_dim), dtype=torch.float32, device=x.device)
+            torch.cuda.current_stream(x.device).synchronize()      # x written, out's block free, on torch's stream
+            self.dev.run_ragged(lengths, x_ptr=x.data_ptr(), out_ptr=out.data_ptr())
+            return out
+        x = np.ascontiguousarray(windows, dtype=np.float32).reshape(-1)
+        if x.size != total:
+            raise ValueError(f'embed_ragged: {x.size} values given, the lengths ask for {FEAT_DIM} x {int(lengths.sum())}')
+        return self.dev.run_ragged(lengths, x)
+
+    def embed_windows_ragged(self, fe, starts, lengths) -> np.ndarray:
+        """Embeddings of the windows of lengths[w] frames from feature rows starts[w] of a front end on the same device:
+        one gather into the network's input buffer, one run of the network."""
+        starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+        lengths = np.asarray(lengths, dtype=np.int32).reshape(-1)
+        if starts.size != lengths.size:
+            raise ValueError(f'embed_windows_ragged: {starts.size} starts, {lengths.size} lengths')
+        if starts.size == 0:
+            return np.empty((0, self.embed_dim), dtype=np.float32)
+        ptr = self.dev.input_buffer_ragged(lengths)
+        fe.dev.windows_ragged(starts, lengths, dst_ptr=ptr)
+        return self.dev.run_ragged(lengths, x_ptr=ptr)
 
     def times(self) -> dict:
         """Device ms of the last run: stem, layer1 .. layer4, pool_embed."""
