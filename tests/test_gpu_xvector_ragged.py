@@ -123,6 +123,35 @@ def test_pool_ragged(ctx):
     assert np.isnan(out).sum() == 2                            # the mean and the deviation of one (h, c) of one window
 
 
+def test_an_equal_width_batch_has_the_same_bits_through_both_entries(ctx):
+    """The uniform and the ragged kernels are instantiations of one body chosen in one place: n = 3 windows of one width give
+    the same bits through the uniform entry (whose own window index -- m / (Ho Wo), t / 64, bh >> 3 -- the tests above see
+    at n = 1 only) as through the ragged one.  The convolution has M = 36 rows < BM: three windows inside one tile, the
+    first wave's 32-row slab over all three; in the split mode amax_y and y itself also compare the two amax kernels."""
+    rng = np.random.default_rng(9)
+
+    def same(a, b, what):
+        (ya, ga, ua), (yb, gb, ub) = a[:3], b[:3]
+        assert ga == 0 and gb == 0 and ua == 0 and ub == 0, (what, ga, gb, ua, ub)
+        assert len(ya) == len(yb) == 3, what
+        for j in range(3):
+            assert np.array_equal(bits(ya[j]), bits(yb[j])), (what, 'window', j)
+
+    xs = [rng.standard_normal((64, 5)).astype(np.float32) for _ in range(3)]
+    w = rng.standard_normal((9, 32)).astype(np.float32)
+    bias = rng.standard_normal(32).astype(np.float32)
+    same(_capi.resnet_stem(ctx, np.stack(xs), w, bias), _capi.resnet_stem_ragged(ctx, xs, w, bias), 'stem')
+    xs = [(3.0 + rng.standard_normal((8, 3, 1024))).astype(np.float32) for _ in range(3)]
+    same(_capi.resnet_pool(ctx, np.stack(xs)), _capi.resnet_pool_ragged(ctx, xs), 'pool')
+    xs, w, bias, res = make(rng, 3, 2, 8, [5, 5, 5], 16, 32)
+    for gemm in GEMMS:
+        a = _capi.resnet_conv_gemm(ctx, gemm, np.stack(xs), w, bias, 3, 2, res=np.stack(res), relu=True, tile=(32, 128))
+        b = _capi.resnet_conv_ragged(ctx, gemm, xs, w, bias, 3, 2, res=res, relu=True, tile=(32, 128))
+        same(a, b, ('conv', gemm))
+        assert np.array_equal(bits(a[3]), bits(b[3])), ('amax_y', gemm, a[3], b[3])
+        assert (a[3] > 0).all() == (gemm == 'split')
+
+
 def test_step_entry_points_refuse_bad_arguments(ctx):
     rng = np.random.default_rng(8)
     xs, w, bias, res = make(rng, 1, 1, 2, [3, 1, 4], 16, 32)

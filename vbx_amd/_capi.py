@@ -474,22 +474,24 @@ class ResNetDevice:
         self.ctx.check(self._lib.vbx_resnet_input(self._h, int(n), int(T), C.byref(p)), 'vbx_resnet_input')
         return p.value
 
+    def _run(self, name, n, shape, x, x_ptr, out_ptr):
+        """One run through the C entry `name` (shape: its arguments after the handle): the host array x or device memory
+        at x_ptr; into a new host array, or into device memory at out_ptr (returns None then)."""
+        src, on_dev = (_ptr(x), 0) if x_ptr is None else (C.c_void_p(x_ptr), 1)
+        out = None
+        if out_ptr is None:
+            out = np.empty((int(n), self.embed_dim), dtype=np.float32)
+            out_ptr = out.ctypes.data
+        self.ctx.check(getattr(self._lib, name)(self._h, *shape, src, on_dev, C.c_void_p(out_ptr), int(out is None)), name)
+        return out
+
     def run(self, n, T, x=None, x_ptr=None, out_ptr=None):
         """Embeddings [n][E] f32 of the host array x [n][64][T], or of device memory at x_ptr; into a new host array, or
         into device memory at out_ptr (returns None then)."""
         if x_ptr is None:
             x = np.ascontiguousarray(x, dtype=np.float32)
             assert x.shape == (n, 64, T)
-            src, on_dev = _ptr(x), 0
-        else:
-            src, on_dev = C.c_void_p(x_ptr), 1
-        out = None
-        if out_ptr is None:
-            out = np.empty((int(n), self.embed_dim), dtype=np.float32)
-            out_ptr = out.ctypes.data
-        self.ctx.check(self._lib.vbx_resnet_run(self._h, int(n), int(T), src, on_dev, C.c_void_p(out_ptr), int(out is None)),
-                       'vbx_resnet_run')
-        return out
+        return self._run('vbx_resnet_run', n, (int(n), int(T)), x, x_ptr, out_ptr)
 
     def input_buffer_ragged(self, lengths) -> int:
         """Device address of the network's own input buffer for a ragged batch: 64 sum(lengths) f32 (vbx_resnet_input_ragged)."""
@@ -508,16 +510,7 @@ class ResNetDevice:
             x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
             if x.size != 64 * int(np.maximum(lengths, 0).sum(dtype=np.int64)):
                 raise ValueError(f'run_ragged: x holds {x.size} values, the lengths ask for 64 x {int(lengths.sum())}')
-            src, on_dev = _ptr(x), 0
-        else:
-            src, on_dev = C.c_void_p(x_ptr), 1
-        out = None
-        if out_ptr is None:
-            out = np.empty((n, self.embed_dim), dtype=np.float32)
-            out_ptr = out.ctypes.data
-        self.ctx.check(self._lib.vbx_resnet_run_ragged(self._h, n, _ptr(lengths), src, on_dev, C.c_void_p(out_ptr), int(out is None)),
-                       'vbx_resnet_run_ragged')
-        return out
+        return self._run('vbx_resnet_run_ragged', n, (n, _ptr(lengths)), x, x_ptr, out_ptr)
 
     def times(self):
         ms = np.zeros(len(self.TIMES), dtype=np.float32)
@@ -568,82 +561,127 @@ def resnet_conv_tile(M, Cout):
     return bn.value, bm.value
 
 
-def _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad):
-    """The shape bookkeeping of one convolution step: call(n, H, W, Cin, Cout, x, w, bias, res, relu, bn, bm, buf, pad) runs
-    the C entry on the guarded output buffer.  -> (y [n][Ho][Wo][Cout], guard, unwritten)."""
+def _pack(arrays):
+    """Host arrays end to end as one flat f32 array (None: None)."""
+    return None if arrays is None else np.concatenate([_f32(a).reshape(-1) for a in arrays])
+
+
+def _widths(n, W):
+    """The widths of n windows given as one int for all (what the uniform C entries take) or as n ints (what the *_ragged ones
+    take): -> (int32 [n], the C argument)."""
+    if np.ndim(W) == 0:
+        return np.full(n, int(W), dtype=np.int32), int(W)
+    W = np.ascontiguousarray(W, dtype=np.int32)
+    return W, _ptr(W)
+
+
+def _step(ctx, name, args, count, pad):
+    """One step-level C entry `name` on host arrays: args(buf, pad) gives its arguments after the context, buf a guarded buffer
+    for its `count` output floats.  -> (the output, flat; guard-band words the kernel changed; output words it left unwritten)."""
+    buf = _guarded(count, pad)
+    ctx.check(getattr(ctx._lib, name)(ctx._h, *args(_ptr(buf), int(pad))), name)
+    return _unguard(buf, count, pad)
+
+
+def _split(y, shapes):
+    """The windows' outputs (shapes) out of y, where they lie end to end."""
+    offs = np.cumsum([0] + [int(np.prod(sh)) for sh in shapes])
+    return [y[offs[b]:offs[b + 1]].reshape(sh) for b, sh in enumerate(shapes)]
+
+
+def _conv_step(ctx, name, gemm, n, H, W, Cin, x, w, bias, ks, stride, res, relu, tile, pad):
+    """One convolution through the C entry `name` (gemm None: vbx_resnet_conv, which takes no mode and records no amax_y) of n
+    windows [H][W_b][Cin], x and res (or None) flat, W as _widths takes it.  -> (y flat, the windows' output shapes
+    (Ho, Wo_b, Cout), guard, unwritten, amax_y [n])."""
     x, w, bias, res = _f32(x), _f32(w), _f32(bias), _f32(res)
-    n, H, W, Cin = x.shape
+    widths, Warg = _widths(n, W)
     Cout = w.shape[1]
     s = max(int(stride), 1)
-    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-    count = n * Ho * Wo * Cout
+    shapes = [((H - 1) // s + 1, (int(Wb) - 1) // s + 1, Cout) for Wb in widths]
+    count = sum(int(np.prod(sh)) for sh in shapes)
     assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (res is None or res.size == count)
     bn, bm = tile or (0, 0)
-    buf = _guarded(count, pad)
-    call(n, H, W, Cin, Cout, _ptr(x), _ptr(w), _ptr(bias), _ptr(res), int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad))
-    y, guard, unwritten = _unguard(buf, count, pad)
-    return y.reshape(n, Ho, Wo, Cout), guard, unwritten
+    amax = np.zeros(max(n, 1), dtype=np.float32)
+    head, tail = ((), ()) if gemm is None else ((GEMM_NAMES[gemm],), (_ptr(amax),))
+
+    def args(buf, pad):
+        return head + (int(ks), int(stride), n, H, Warg, Cin, Cout, _ptr(x), _ptr(w), _ptr(bias), _ptr(res), int(bool(relu)),
+                       int(bn), int(bm), buf, pad) + tail
+    y, guard, unwritten = _step(ctx, name, args, count, pad)
+    return y, shapes, guard, unwritten, amax[:n]
+
+
+def _conv_stacked(ctx, name, gemm, x, w, bias, ks, stride, res, relu, tile, pad):
+    """_conv_step on one array x [n][H][W][Cin] through a uniform entry: -> (y [n][Ho][Wo][Cout], guard, unwritten, amax_y)."""
+    n, H, W, Cin = np.shape(x)
+    y, shapes, guard, unwritten, amax = _conv_step(ctx, name, gemm, n, H, W, Cin, x, w, bias, ks, stride, res, relu, tile, pad)
+    return y.reshape((n,) + shapes[0]), guard, unwritten, amax
 
 
 def resnet_conv(ctx: 'Context', x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
     """One convolution of the network (vbx_resnet_conv): x [n][H][W][Cin], w [ks ks Cin][Cout], bias [Cout], res
     [n][Ho][Wo][Cout] or None; tile None (the dispatcher's) or (BN, BM).  -> (y [n][Ho][Wo][Cout], guard-band words the
     kernel changed, output words it left unwritten)."""
-    def call(*a):
-        ctx.check(ctx._lib.vbx_resnet_conv(ctx._h, int(ks), int(stride), *a), 'vbx_resnet_conv')
-    return _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad)
+    return _conv_stacked(ctx, 'vbx_resnet_conv', None, x, w, bias, ks, stride, res, relu, tile, pad)[:3]
 
 
 def resnet_conv_gemm(ctx: 'Context', gemm, x, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
     """resnet_conv in either mode (vbx_resnet_conv_gemm; gemm 'exact' or 'split').  -> (y, guard, unwritten, amax_y [n]: max |y|
     over the finite outputs of every image as the split kernel records it for its consumer; zeros in the exact mode)."""
-    n = len(x)
-    amax = np.zeros(max(n, 1), dtype=np.float32)
-
-    def call(*a):
-        ctx.check(ctx._lib.vbx_resnet_conv_gemm(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), *a, _ptr(amax)), 'vbx_resnet_conv_gemm')
-    return _conv_step(call, x, w, bias, ks, stride, res, relu, tile, pad) + (amax[:n],)
+    return _conv_stacked(ctx, 'vbx_resnet_conv_gemm', gemm, x, w, bias, ks, stride, res, relu, tile, pad)
 
 
 def resnet_conv_ragged(ctx: 'Context', gemm, xs, w, bias, ks, stride, res=None, relu=False, tile=None, pad=RN_PAD):
     """One convolution over a ragged batch (vbx_resnet_conv_ragged; gemm 'exact' or 'split'): xs a list of [H][W_b][Cin]
     windows, res a list of [Ho][Wo_b][Cout] or None.  -> (ys: the list of [Ho][Wo_b][Cout] outputs, guard, unwritten, amax_y [n])."""
     xs = [_f32(x) for x in xs]
-    w, bias = _f32(w), _f32(bias)
-    n, H, Cin, Cout = len(xs), xs[0].shape[0], xs[0].shape[2], w.shape[1]
+    H, _, Cin = xs[0].shape
     assert all(x.ndim == 3 and x.shape[0] == H and x.shape[2] == Cin for x in xs)
-    widths = np.array([x.shape[1] for x in xs], dtype=np.int32)
-    s = max(int(stride), 1)
-    Ho, Wo = (H - 1) // s + 1, [(int(W) - 1) // s + 1 for W in widths]
-    counts = [Ho * W * Cout for W in Wo]
-    count = sum(counts)
-    x = np.concatenate([x.reshape(-1) for x in xs])
-    r = None if res is None else np.concatenate([_f32(a).reshape(-1) for a in res])
-    assert w.shape == (ks * ks * Cin, Cout) and bias.shape == (Cout,) and (r is None or r.size == count)
-    bn, bm = tile or (0, 0)
-    buf = _guarded(count, pad)
-    amax = np.zeros(n, dtype=np.float32)
-    ctx.check(ctx._lib.vbx_resnet_conv_ragged(ctx._h, GEMM_NAMES[gemm], int(ks), int(stride), n, H, _ptr(widths), Cin, Cout, _ptr(x),
-                                              _ptr(w), _ptr(bias), _ptr(r), int(bool(relu)), int(bn), int(bm), _ptr(buf), int(pad),
-                                              _ptr(amax)), 'vbx_resnet_conv_ragged')
-    y, guard, unwritten = _unguard(buf, count, pad)
-    offs = np.concatenate([[0], np.cumsum(counts)])
-    return [y[offs[b]:offs[b + 1]].reshape(Ho, Wo[b], Cout) for b in range(n)], guard, unwritten, amax
+    y, shapes, guard, unwritten, amax = _conv_step(ctx, 'vbx_resnet_conv_ragged', gemm, len(xs), H, [x.shape[1] for x in xs], Cin,
+                                                   _pack(xs), w, bias, ks, stride, _pack(res), relu, tile, pad)
+    return _split(y, shapes), guard, unwritten, amax
+
+
+def _stem_step(ctx, name, n, T, x, w, bias, pad):
+    """The stem through the C entry `name`: n windows [64][T_b], x flat, T as _widths takes it.  -> (y flat, the lengths [n],
+    guard, unwritten)."""
+    x, w, bias = _f32(x), _f32(w), _f32(bias)
+    assert w.shape == (9, 32) and bias.shape == (32,)
+    T, Targ = _widths(n, T)
+    count = 64 * 32 * int(T.sum(dtype=np.int64))
+    return (T,) + _step(ctx, name, lambda buf, pad: (n, Targ, _ptr(x), _ptr(w), _ptr(bias), buf, pad), count, pad)
+
+
+def resnet_stem(ctx: 'Context', x, w, bias, pad=RN_PAD):
+    """The stem (vbx_resnet_stem): x [n][64][T], w [9][32], bias [32] -> (y [n][64][T][32], guard, unwritten)."""
+    n, mel, T = np.shape(x)
+    assert mel == 64
+    _, y, guard, unwritten = _stem_step(ctx, 'vbx_resnet_stem', n, T, x, w, bias, pad)
+    return y.reshape(n, 64, T, 32), guard, unwritten
 
 
 def resnet_stem_ragged(ctx: 'Context', xs, w, bias, pad=RN_PAD):
     """The stem over a ragged batch (vbx_resnet_stem_ragged): xs a list of [64][T_b] -> (list of [64][T_b][32], guard, unwritten)."""
-    xs, w, bias = [_f32(x) for x in xs], _f32(w), _f32(bias)
-    assert all(x.ndim == 2 and x.shape[0] == 64 for x in xs) and w.shape == (9, 32) and bias.shape == (32,)
-    T = np.array([x.shape[1] for x in xs], dtype=np.int32)
-    x = np.concatenate([x.reshape(-1) for x in xs])
-    count = 64 * 32 * int(T.sum())
-    buf = _guarded(count, pad)
-    ctx.check(ctx._lib.vbx_resnet_stem_ragged(ctx._h, len(xs), _ptr(T), _ptr(x), _ptr(w), _ptr(bias), _ptr(buf), int(pad)),
-              'vbx_resnet_stem_ragged')
-    y, guard, unwritten = _unguard(buf, count, pad)
-    offs = np.concatenate([[0], np.cumsum(64 * 32 * T.astype(np.int64))])
-    return [y[offs[b]:offs[b + 1]].reshape(64, int(T[b]), 32) for b in range(len(xs))], guard, unwritten
+    xs = [_f32(x) for x in xs]
+    assert all(x.ndim == 2 and x.shape[0] == 64 for x in xs)
+    T, y, guard, unwritten = _stem_step(ctx, 'vbx_resnet_stem_ragged', len(xs), [x.shape[1] for x in xs], _pack(xs), w, bias, pad)
+    return _split(y, [(64, int(t), 32) for t in T]), guard, unwritten
+
+
+def _pool_step(ctx, name, n, W4, x, pad):
+    """Statistics pooling through the C entry `name`: n windows [8][W4_b][1024], x flat, W4 as _widths takes it.  -> (out
+    [n][16384], guard, unwritten)."""
+    x = _f32(x)
+    W4, W4arg = _widths(n, W4)                                # (W4: kept while W4arg points into it)
+    out, guard, unwritten = _step(ctx, name, lambda buf, pad: (n, W4arg, _ptr(x), buf, pad), n * 16384, pad)
+    return out.reshape(n, 16384), guard, unwritten
+
+
+def resnet_pool(ctx: 'Context', x, pad=RN_PAD):
+    """Statistics pooling (vbx_resnet_pool): x [n][8][W4][1024] -> (out [n][16384], guard, unwritten)."""
+    n, h, W4, c = np.shape(x)
+    assert h == 8 and c == 1024
+    return _pool_step(ctx, 'vbx_resnet_pool', n, W4, x, pad)
 
 
 def resnet_pool_ragged(ctx: 'Context', xs, pad=RN_PAD):
@@ -651,13 +689,7 @@ def resnet_pool_ragged(ctx: 'Context', xs, pad=RN_PAD):
     guard, unwritten)."""
     xs = [_f32(x) for x in xs]
     assert all(x.ndim == 3 and x.shape[0] == 8 and x.shape[2] == 1024 for x in xs)
-    W4 = np.array([x.shape[1] for x in xs], dtype=np.int32)
-    x = np.concatenate([x.reshape(-1) for x in xs])
-    count = len(xs) * 16384
-    buf = _guarded(count, pad)
-    ctx.check(ctx._lib.vbx_resnet_pool_ragged(ctx._h, len(xs), _ptr(W4), _ptr(x), _ptr(buf), int(pad)), 'vbx_resnet_pool_ragged')
-    out, guard, unwritten = _unguard(buf, count, pad)
-    return out.reshape(len(xs), 16384), guard, unwritten
+    return _pool_step(ctx, 'vbx_resnet_pool_ragged', len(xs), [x.shape[1] for x in xs], _pack(xs), pad)
 
 
 def resnet_split_weights(w):
@@ -671,30 +703,6 @@ def resnet_split_weights(w):
     if rc != 0:
         raise VbxError(f'vbx_resnet_split_weights(K={K}, Cout={Cout}) failed ({rc})')
     return frag, e
-
-
-def resnet_stem(ctx: 'Context', x, w, bias, pad=RN_PAD):
-    """The stem (vbx_resnet_stem): x [n][64][T], w [9][32], bias [32] -> (y [n][64][T][32], guard, unwritten)."""
-    x, w, bias = _f32(x), _f32(w), _f32(bias)
-    n, mel, T = x.shape
-    assert mel == 64 and w.shape == (9, 32) and bias.shape == (32,)
-    count = n * 64 * T * 32
-    buf = _guarded(count, pad)
-    ctx.check(ctx._lib.vbx_resnet_stem(ctx._h, n, T, _ptr(x), _ptr(w), _ptr(bias), _ptr(buf), int(pad)), 'vbx_resnet_stem')
-    y, guard, unwritten = _unguard(buf, count, pad)
-    return y.reshape(n, 64, T, 32), guard, unwritten
-
-
-def resnet_pool(ctx: 'Context', x, pad=RN_PAD):
-    """Statistics pooling (vbx_resnet_pool): x [n][8][W4][1024] -> (out [n][16384], guard, unwritten)."""
-    x = _f32(x)
-    n, h, W4, c = x.shape
-    assert h == 8 and c == 1024
-    count = n * 16384
-    buf = _guarded(count, pad)
-    ctx.check(ctx._lib.vbx_resnet_pool(ctx._h, n, W4, _ptr(x), _ptr(buf), int(pad)), 'vbx_resnet_pool')
-    out, guard, unwritten = _unguard(buf, count, pad)
-    return out.reshape(n, 16384), guard, unwritten
 
 
 class Scores:

@@ -28,6 +28,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 

@@ -1,6 +1,10 @@
 // vbx_host_resnet.hpp -- host runtime of the x-vector network (vbx_resnet.hpp): the folded parameters, the workspace and the
 // launch sequence of one batch of windows.  Included by vbx_capi.hip after vbx_host_fbank.hpp (fb_reserve).
 //
+// A batch's shape exists once, as an RnBatch (rn_batch builds it from one T or from T[]), for a run, for a convolution step
+// and for a stem or pooling step alike; whether it is uniform or ragged becomes the kernels' RAG in rn_by_kind and nowhere
+// else.
+//
 // Parameter blob (f32, vbx_amd/xvector.py:fold writes it in this order): for every convolution in network order -- the
 // stem, then per block conv1, conv2, conv3 and, in the first block of a stage, the shortcut -- its weights [kh kw Cin][Cout]
 // and its folded bias [Cout]; then the embedding [16384][E] (rows in the pooling kernel's order) and its bias [E].
@@ -16,7 +20,7 @@ enum RnBuf { RN_X0, RN_X1, RN_T1, RN_T2, RN_SC, RN_NBUF };     // the block outp
 struct RnPlanStep {
     int conv;                                                  // index into vbx_resnet::convs
     int in, out, res;                                          // RnBuf; res: RN_NBUF for none
-    int lvl, relu;                                             // the input's level (rn_levels); the output's: + 1 at stride 2
+    int lvl, relu;                                             // the input's level (RnBatch); the output's: + 1 at stride 2
     int ain, aout;                                             // split mode: the max |.| slots of its input and (or -1) its output
     int stage;                                                 // 0 .. 3: layer1 .. layer4 (the events)
 };
@@ -37,7 +41,7 @@ struct vbx_resnet {
     int* d_we = nullptr;
     unsigned* d_amax = nullptr;
     size_t cap_amax = 0;
-    long long* d_pos = nullptr;                                // ragged runs: RnLevels' tables
+    long long* d_pos = nullptr;                                // ragged runs: RnBatch's tables
     int* d_wid = nullptr;
     size_t cap_pos = 0, cap_wid = 0;
 };
@@ -77,53 +81,64 @@ static size_t rn_layout(std::vector<RnConv>& convs) {
     return off;
 }
 
-// The batch of a run at the four spatial levels l = 0 .. 3 (H_l = 64 >> l rows, a window's width W_l = rn_out(., 2) of
-// its frames l times): M[l] positions in all.  Uniform: every window W[l] wide.  Ragged: window b is wid[l n + b] wide
-// and its [H_l][W_{b,l}][C] block starts at position pos[l (n + 1) + b]; pos[l (n + 1) + n] = M[l].  vbx_amd/xvector.py:
-// ragged_layout is the same in numpy.
+// The geometry of a batch of n windows, the only one there is: at level l every window has H[l] rows and the batch M[l]
+// positions in all.  Uniform: every window is W[l] wide.  Ragged: window b is wid[l n + b] wide and its [H_l][W_{b,l}][C]
+// block starts at position pos[l (n + 1) + b]; pos[l (n + 1) + n] = M[l] (vbx_amd/xvector.py: ragged_layout is the same in
+// numpy).  A run has the network's four levels, a convolution step its input and its output, a stem or pooling step one.
 constexpr int RN_LEVELS = 4;
-struct RnLevels {
+struct RnBatch {
     int n = 0;
     bool ragged = false;
-    int W[RN_LEVELS] = {};
+    int H[RN_LEVELS] = {}, W[RN_LEVELS] = {};                  // (W: zero in a ragged batch)
     long long M[RN_LEVELS] = {};
-    std::vector<long long> pos;                                // [4][n + 1]
-    std::vector<int> wid;                                      // [4][n]
+    std::vector<long long> pos;                                // ragged: [levels][n + 1]
+    std::vector<int> wid;                                      // [levels][n]
     const long long* d_pos = nullptr;                          // their device copies
     const int* d_wid = nullptr;
-    int H(int l) const { return RN_MEL >> l; }
-    // the kernels' view of a convolution from level li to level lo
-    vbx::RnRag rag(int li, int lo) const {
-        return vbx::RnRag{d_pos + (size_t)li * (n + 1), d_pos + (size_t)lo * (n + 1), d_wid + (size_t)li * n, d_wid + (size_t)lo * n, n};
+    // the kernels' view of level l, and of a convolution from level li to level lo
+    template <bool RAG> RnLevel<RAG> level(int l) const {
+        if constexpr (RAG) return {d_pos + (size_t)l * (n + 1), d_wid + (size_t)l * n, n};
+        else return {W[l]};
+    }
+    template <bool RAG> RnGeom<RAG> conv(int li, int lo) const {
+        if constexpr (RAG) return {RnRag{level<true>(li).pos, level<true>(lo).pos, level<true>(li).wid, level<true>(lo).wid, n}};
+        else return {};
     }
 };
 
-static RnLevels rn_levels_uniform(int n, int T) {
-    RnLevels g;
+// n windows of H rows, all of them T wide or (Tv not null) window b Tv[b] wide, at `levels` levels: every level is
+// rn_out(., stride) of the one before it in rows and in widths
+static RnBatch rn_batch(int n, int H, int T, const int32_t* Tv, int levels, int stride = 2) {
+    RnBatch g;
     g.n = n;
-    for (int l = 0, W = T; l < RN_LEVELS; ++l, W = rn_out(W, 2)) {
-        g.W[l] = W;
-        g.M[l] = (long long)n * g.H(l) * W;
+    g.ragged = Tv != nullptr;
+    if (g.ragged) {
+        g.pos.assign((size_t)levels * (n + 1), 0);
+        g.wid.resize((size_t)levels * n);
+    }
+    for (int l = 0; l < levels; ++l) {
+        g.H[l] = l == 0 ? H : rn_out(g.H[l - 1], stride);
+        if (g.ragged) {
+            long long* pos = &g.pos[(size_t)l * (n + 1)];
+            for (int b = 0; b < n; ++b) {
+                const int W = l == 0 ? Tv[b] : rn_out(g.wid[(size_t)(l - 1) * n + b], stride);
+                g.wid[(size_t)l * n + b] = W;
+                pos[b + 1] = pos[b] + (long long)g.H[l] * W;
+            }
+            g.M[l] = pos[n];
+        } else {
+            g.W[l] = l == 0 ? T : rn_out(g.W[l - 1], stride);
+            g.M[l] = (long long)n * g.H[l] * g.W[l];
+        }
     }
     return g;
 }
 
-static RnLevels rn_levels_ragged(int n, const int32_t* T) {
-    RnLevels g;
-    g.n = n;
-    g.ragged = true;
-    g.pos.assign((size_t)RN_LEVELS * (n + 1), 0);
-    g.wid.resize((size_t)RN_LEVELS * n);
-    for (int l = 0; l < RN_LEVELS; ++l) {
-        long long* pos = &g.pos[(size_t)l * (n + 1)];
-        for (int b = 0; b < n; ++b) {
-            const int W = l == 0 ? T[b] : rn_out(g.wid[(size_t)(l - 1) * n + b], 2);
-            g.wid[(size_t)l * n + b] = W;
-            pos[b + 1] = pos[b] + (long long)g.H(l) * W;
-        }
-        g.M[l] = pos[n];
-    }
-    return g;
+// f(std::true_type) for a ragged batch, f(std::false_type) for a uniform one: the one place where a batch's kind becomes
+// the kernels' RAG
+template <class F> static void rn_by_kind(const RnBatch& g, F f) {
+    if (g.ragged) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 // the convolutions of layer1 .. layer4 in launch order: per block conv1, conv2, the shortcut (from the block's input),
@@ -145,29 +160,23 @@ static std::vector<RnPlanStep> rn_plan() {
     return plan;
 }
 
-// one call of a convolution kernel: n images H x W x Cin -> Ho x Wo x Cout (Cout a multiple of 32, Cin of 16).  Plain values.
+// one call of a convolution kernel: the batch g from its level li to its level lo, Cin -> Cout channels (Cout a multiple of
+// 32, Cin of 16).  Plain values.
 struct RnCall {
-    int ks, stride, H, W, Cin, Ho, Wo, Cout, relu;
-    long long M;
+    int ks, stride, Cin, Cout, relu;
+    const RnBatch* g;
+    int li, lo;
     const float *x = nullptr, *w = nullptr, *b = nullptr, *res = nullptr;      // w: the exact mode's weights
     float* y = nullptr;
     const unsigned* ax = nullptr;                              // split mode: the max |.| slots of x and (or null) of y,
     unsigned* ay = nullptr;
     const vbx::h8* wf = nullptr;                               // the weights' fragments and exponents
     const int* we = nullptr;
-    vbx::RnRag g;                                              // a ragged batch (g.pos_out set): H, Cin, Cout, M and g say it all
+    long long M() const { return g->M[lo]; }                   // output positions
 };
 
-static RnCall rn_call(int ks, int stride, int n, int H, int W, int Cin, int Cout, int relu) {
-    const int Ho = rn_out(H, stride), Wo = rn_out(W, stride);
-    return RnCall{ks, stride, H, W, Cin, Ho, Wo, Cout, relu, (long long)n * Ho * Wo};
-}
-
-// the same over a ragged batch of windows of H rows, M output positions in all
-static RnCall rn_call_ragged(int ks, int stride, int H, int Cin, int Cout, int relu, const vbx::RnRag& g, long long M) {
-    RnCall c{ks, stride, H, 0, Cin, rn_out(H, stride), 0, Cout, relu, M};
-    c.g = g;
-    return c;
+static RnCall rn_call(const RnConv& c, int relu, const RnBatch& g, int li, int lo) {
+    return RnCall{c.ks, c.stride, c.cin, c.cout, relu, &g, li, lo};
 }
 
 // the instantiations of both convolution kernels: every (KS, S) at every BN x BM tile
@@ -185,34 +194,51 @@ template <int I = 0> static bool rn_launch(hipStream_t st, const RnCall& c, int 
     if constexpr (I < 20) {
         constexpr int KS = RN_KS_STRIDE[I / 5][0], S = RN_KS_STRIDE[I / 5][1], bn = RN_TILES[I % 5][0], bm = RN_TILES[I % 5][1];
         if (c.ks != KS || c.stride != S || BN != bn || BM != bm) return rn_launch<I + 1>(st, c, BN, BM, mode);
-        const dim3 grid((unsigned)((c.M + bm - 1) / bm), (unsigned)(c.Cout / bn)), blk(256);
-        if (c.g.pos_out && mode == VBX_GEMM_SPLIT)
-            hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, bn, bm, true>), grid, blk, 0, st, c.x, c.ax, c.wf, c.we, c.b, c.res, c.y,
-                               c.ay, c.H, c.W, c.Cin, c.Ho, c.Wo, c.Cout, c.M, c.relu, RnGeom<true>{c.g});
-        else if (c.g.pos_out)
-            hipLaunchKernelGGL((resnet_conv_kernel<KS, S, bn, bm, true>), grid, blk, 0, st, c.x, c.w, c.b, c.res, c.y, c.H, c.W, c.Cin,
-                               c.Ho, c.Wo, c.Cout, c.M, c.relu, RnGeom<true>{c.g});
-        else if (mode == VBX_GEMM_SPLIT)
-            hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, bn, bm>), grid, blk, 0, st, c.x, c.ax, c.wf, c.we, c.b, c.res, c.y, c.ay,
-                               c.H, c.W, c.Cin, c.Ho, c.Wo, c.Cout, c.M, c.relu, RnGeom<false>{});
-        else
-            hipLaunchKernelGGL((resnet_conv_kernel<KS, S, bn, bm>), grid, blk, 0, st, c.x, c.w, c.b, c.res, c.y, c.H, c.W, c.Cin, c.Ho,
-                               c.Wo, c.Cout, c.M, c.relu, RnGeom<false>{});
+        const RnBatch& g = *c.g;
+        const int H = g.H[c.li], W = g.W[c.li], Ho = g.H[c.lo], Wo = g.W[c.lo];
+        const long long M = c.M();
+        const dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)(c.Cout / bn)), blk(256);
+        rn_by_kind(g, [&](auto rag) {
+            constexpr bool RAG = decltype(rag)::value;
+            if (mode == VBX_GEMM_SPLIT)
+                hipLaunchKernelGGL((resnet_conv_split_kernel<KS, S, bn, bm, RAG>), grid, blk, 0, st, c.x, c.ax, c.wf, c.we, c.b, c.res,
+                                   c.y, c.ay, H, W, c.Cin, Ho, Wo, c.Cout, M, c.relu, g.conv<RAG>(c.li, c.lo));
+            else
+                hipLaunchKernelGGL((resnet_conv_kernel<KS, S, bn, bm, RAG>), grid, blk, 0, st, c.x, c.w, c.b, c.res, c.y, H, W, c.Cin,
+                                   Ho, Wo, c.Cout, M, c.relu, g.conv<RAG>(c.li, c.lo));
+        });
         return true;
     }
     return false;
 }
 
-// max |x| per window of n windows of per_window floats (a multiple of 4) into amax[n], zeroed beforehand
-static void rn_amax(hipStream_t st, const float* x, int n, long long per_window, unsigned* amax) {
-    const int bpw = (int)std::min<long long>(64, (per_window / 4 + 255) / 256);
-    hipLaunchKernelGGL(resnet_amax_kernel, dim3((unsigned)n * bpw), dim3(256), 0, st, x, per_window, bpw, amax);
+// the stem over the batch g (level 0): x g.M[0] floats -> y [g.M[0]][32]
+static void rn_stem(hipStream_t st, const RnBatch& g, const float* x, const float* w, const float* b, float* y) {
+    const long long total = g.M[0] * 32;
+    rn_by_kind(g, [&](auto rag) {
+        hipLaunchKernelGGL(resnet_stem_kernel<decltype(rag)::value>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, w, b, y,
+                           total, g.level<decltype(rag)::value>(0));
+    });
 }
 
-// the same for a ragged batch of M positions of C channels (a multiple of 4), window b at positions pos[b] .. pos[b + 1]
-static void rn_amax_ragged(hipStream_t st, const float* x, int n, const long long* pos, long long M, int C, unsigned* amax) {
-    const int bpw = (int)std::max<long long>(1, std::min<long long>(64, (M / n * C / 4 + 255) / 256));
-    hipLaunchKernelGGL(resnet_amax_ragged_kernel, dim3((unsigned)n * bpw), dim3(256), 0, st, x, pos, C, bpw, amax);
+// the pooling of level l of g (RN_H4 rows, RN_C4 channels): x -> out [n][RN_POOL]
+static void rn_pool(hipStream_t st, const RnBatch& g, int l, const float* x, float* out) {
+    const long long total = (long long)g.n * RN_H4 * RN_C4;
+    rn_by_kind(g, [&](auto rag) {
+        hipLaunchKernelGGL(resnet_pool_kernel<decltype(rag)::value>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, out,
+                           total, g.level<decltype(rag)::value>(l));
+    });
+}
+
+// max |x| per window of level l of g with C channels (a multiple of 4) into amax[n], zeroed beforehand.  Blocks per window
+// from a window's floats: what every window has in a uniform batch, the mean in a ragged one.  (M / n is exact in a uniform
+// batch, H W, and at least one float4 there, so the max(1, .) never bites: the grids of both kinds are what they were.)
+static void rn_amax(hipStream_t st, const RnBatch& g, int l, int C, const float* x, unsigned* amax) {
+    const int bpw = (int)std::max<long long>(1, std::min<long long>(64, (g.M[l] / g.n * C / 4 + 255) / 256));
+    rn_by_kind(g, [&](auto rag) {
+        hipLaunchKernelGGL(resnet_amax_kernel<decltype(rag)::value>, dim3((unsigned)g.n * bpw), dim3(256), 0, st, x, g.H[l], C, bpw,
+                           amax, g.level<decltype(rag)::value>(l));
+    });
 }
 
 // w [K][Cout] f32 (K a multiple of 16, Cout of 32) -> frag [K / 16][Cout / 32][hi | lo][64][8] f16 bits, e [Cout]: the B
@@ -255,7 +281,7 @@ static void rn_tile(long long M, int Cout, int* bn, int* bm) {
 // one convolution at the dispatcher's tile
 static bool rn_conv(hipStream_t st, const RnCall& c, int mode) {
     int BN, BM;
-    rn_tile(c.M, c.Cout, &BN, &BM);
+    rn_tile(c.M(), c.Cout, &BN, &BM);
     return rn_launch(st, c, BN, BM, mode);
 }
 
@@ -295,6 +321,16 @@ struct RnStep {
         else HIPCHK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
         return VBX_OK;
     }
+    int tables(RnBatch& g) {                                   // a ragged batch's tables
+        if (!g.ragged) return VBX_OK;
+        long long* dpos = nullptr;
+        int* dwid = nullptr;
+        int rc = up_bytes(g.pos.data(), sizeof(long long) * g.pos.size(), &dpos);
+        if (rc == VBX_OK) rc = up_bytes(g.wid.data(), sizeof(int) * g.wid.size(), &dwid);
+        g.d_pos = dpos;
+        g.d_wid = dwid;
+        return rc;
+    }
     // the kernel has been launched: wait for it and bring the whole in/out buffer back
     int down(const char* what, float* host, const float* dev, size_t count) {
         hipError_t e = hipGetLastError();
@@ -318,7 +354,7 @@ static int rn_check_lengths(vbx_ctx* ctx, const char* name, int32_t n, const int
 }
 
 // ragged: g's tables to the device (the stream is idle between runs: every run ends with a synchronize)
-static int rn_upload_levels(vbx_resnet* net, RnLevels& g) {
+static int rn_upload_tables(vbx_resnet* net, RnBatch& g) {
     vbx_ctx* ctx = net->ctx;
     int rc = fb_reserve(ctx, &net->d_pos, &net->cap_pos, g.pos.size());
     if (rc == VBX_OK) rc = fb_reserve(ctx, &net->d_wid, &net->cap_wid, g.wid.size());
@@ -330,8 +366,8 @@ static int rn_upload_levels(vbx_resnet* net, RnLevels& g) {
     return VBX_OK;
 }
 
-// the network over the batch g, uniform or ragged: x is g.M[0] floats (the windows' [64][T] blocks)
-static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x, int x_on_device, float* out, int out_on_device) {
+// the network over the batch g (four levels), uniform or ragged: x is g.M[0] floats (the windows' [64][T] blocks)
+static int rn_run(vbx_resnet* net, const char* name, RnBatch& g, const float* x, int x_on_device, float* out, int out_on_device) {
     vbx_ctx* ctx = net->ctx;
     const int n = g.n;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -351,7 +387,7 @@ static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x
     if (rc == VBX_OK && !x_on_device) rc = fb_reserve(ctx, &net->d_in, &net->cap_in, (size_t)g.M[0]);
     const bool split = net->gemm == VBX_GEMM_SPLIT;
     if (rc == VBX_OK && split) rc = fb_reserve(ctx, &net->d_amax, &net->cap_amax, (size_t)RN_AMAX_SLOTS * n);
-    if (rc == VBX_OK && g.ragged) rc = rn_upload_levels(net, g);
+    if (rc == VBX_OK && g.ragged) rc = rn_upload_tables(net, g);
     if (rc != VBX_OK) return rc;
     net->gemm_last = net->gemm;
     if (split) HIPCHK(ctx, hipMemsetAsync(net->d_amax, 0, sizeof(unsigned) * RN_AMAX_SLOTS * (size_t)n, st));
@@ -364,17 +400,8 @@ static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x
     const float* P = net->d_par;
     const RnConv& c0 = net->convs[0];
     HIPCHK(ctx, hipEventRecord(net->ev[0], st));
-    const long long tot0 = g.M[0] * 32;
-    const dim3 grid0((unsigned)((tot0 + 255) / 256));
-    if (g.ragged)
-        hipLaunchKernelGGL(resnet_stem_ragged_kernel, grid0, dim3(256), 0, st, xin, P + c0.w, P + c0.b, net->d_buf[RN_X0], g.d_pos,
-                           g.d_wid, n, tot0);
-    else
-        hipLaunchKernelGGL(resnet_stem_kernel, grid0, dim3(256), 0, st, xin, P + c0.w, P + c0.b, net->d_buf[RN_X0], g.W[0], tot0);
-    if (split) {                                               // (the stem itself stays as it is)
-        if (g.ragged) rn_amax_ragged(st, net->d_buf[RN_X0], n, g.d_pos, g.M[0], 32, slot(0));
-        else rn_amax(st, net->d_buf[RN_X0], n, (long long)RN_MEL * g.W[0] * 32, slot(0));
-    }
+    rn_stem(st, g, xin, P + c0.w, P + c0.b, net->d_buf[RN_X0]);
+    if (split) rn_amax(st, g, 0, 32, net->d_buf[RN_X0], slot(0));  // (the stem itself stays as it is)
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(net->ev[1], st));
     int stage = 0;
@@ -382,9 +409,7 @@ static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x
         if (s.stage != stage) HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
         stage = s.stage;
         const RnConv& c = net->convs[s.conv];
-        const int lo = s.lvl + (c.stride == 2);
-        RnCall call = g.ragged ? rn_call_ragged(c.ks, c.stride, g.H(s.lvl), c.cin, c.cout, s.relu, g.rag(s.lvl, lo), g.M[lo])
-                               : rn_call(c.ks, c.stride, n, g.H(s.lvl), g.W[s.lvl], c.cin, c.cout, s.relu);
+        RnCall call = rn_call(c, s.relu, g, s.lvl, s.lvl + (c.stride == 2));
         call.x = net->d_buf[s.in];
         call.w = P + c.w;
         call.b = P + c.b;
@@ -399,14 +424,9 @@ static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x
     }
     HIPCHK(ctx, hipEventRecord(net->ev[2 + stage], st));
     const RnPlanStep& last = net->plan.back();
-    const long long totp = (long long)n * RN_H4 * RN_C4;
-    const dim3 gridp((unsigned)((totp + 255) / 256));
-    if (g.ragged)
-        hipLaunchKernelGGL(resnet_pool_ragged_kernel, gridp, dim3(256), 0, st, net->d_buf[last.out], net->d_pool,
-                           g.d_pos + (size_t)3 * (n + 1), g.d_wid + (size_t)3 * n, totp);
-    else
-        hipLaunchKernelGGL(resnet_pool_kernel, gridp, dim3(256), 0, st, net->d_buf[last.out], net->d_pool, g.W[3], totp);
-    RnCall emb = rn_call(1, 1, n, 1, 1, RN_POOL, net->Ep, 0);  // (exact in both modes)
+    rn_pool(st, g, RN_LEVELS - 1, net->d_buf[last.out], net->d_pool);
+    const RnBatch rows = rn_batch(n, 1, 1, nullptr, 1);        // the embedding: n positions; exact in both modes
+    RnCall emb = rn_call(RnConv{1, 1, RN_POOL, net->Ep}, 0, rows, 0, 0);
     emb.x = net->d_pool;
     emb.w = net->d_emb_w;
     emb.b = net->d_emb_b;
@@ -418,6 +438,52 @@ static int rn_run(vbx_resnet* net, const char* name, RnLevels& g, const float* x
                                  out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return VBX_OK;
+}
+
+// vbx_resnet_stem and vbx_resnet_stem_ragged: the stem on host arrays
+static int rn_stem_step(const char* name, vbx_ctx* ctx, bool ragged, int32_t n, int32_t T, const int32_t* Tv, const float* x,
+                        const float* w, const float* bias, float* y, int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    int rc = ragged ? rn_check_lengths(ctx, name, n, Tv) : VBX_OK;
+    if (rc != VBX_OK) return rc;
+    const bool ok = x && w && bias && y && pad >= 0;
+    if (ragged && !ok) FAIL(ctx, VBX_ERR_INVALID, "%s: x, w, bias and y must not be NULL, pad not negative", name);
+    if (!ragged && (!ok || n <= 0 || T <= 0)) FAIL(ctx, VBX_ERR_INVALID, "%s: bad argument", name);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnBatch g = rn_batch(n, RN_MEL, T, Tv, 1);                 // (outlives s and its copies)
+    RnStep s(ctx);
+    const size_t ny = (size_t)g.M[0] * 32 + 2 * (size_t)pad;
+    float *dx, *dw, *db, *dy;
+    rc = s.up(x, (size_t)g.M[0], &dx);
+    if (rc == VBX_OK) rc = s.up(w, 9 * 32, &dw);
+    if (rc == VBX_OK) rc = s.up(bias, 32, &db);
+    if (rc == VBX_OK) rc = s.up(y, ny, &dy);
+    if (rc == VBX_OK) rc = s.tables(g);
+    if (rc != VBX_OK) return rc;
+    rn_stem(ctx->stream, g, dx, dw, db, dy + pad);
+    return s.down(name, y, dy, ny);
+}
+
+// vbx_resnet_pool and vbx_resnet_pool_ragged: the pooling on host arrays
+static int rn_pool_step(const char* name, vbx_ctx* ctx, bool ragged, int32_t n, int32_t W4, const int32_t* W4v, const float* x,
+                        float* out, int64_t pad) {
+    if (!ctx) return VBX_ERR_INVALID;
+    int rc = ragged ? rn_check_lengths(ctx, name, n, W4v) : VBX_OK;
+    if (rc != VBX_OK) return rc;
+    const bool ok = x && out && pad >= 0;
+    if (ragged && !ok) FAIL(ctx, VBX_ERR_INVALID, "%s: x and out must not be NULL, pad not negative", name);
+    if (!ragged && (!ok || n <= 0 || W4 <= 0)) FAIL(ctx, VBX_ERR_INVALID, "%s: bad argument", name);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    RnBatch g = rn_batch(n, RN_H4, W4, W4v, 1);                // (outlives s and its copies)
+    RnStep s(ctx);
+    const size_t ny = (size_t)n * RN_POOL + 2 * (size_t)pad;
+    float *dx, *dy;
+    rc = s.up(x, (size_t)g.M[0] * RN_C4, &dx);
+    if (rc == VBX_OK) rc = s.up(out, ny, &dy);
+    if (rc == VBX_OK) rc = s.tables(g);
+    if (rc != VBX_OK) return rc;
+    rn_pool(ctx->stream, g, 0, dx, dy + pad);
+    return s.down(name, out, dy, ny);
 }
 
 extern "C" {
@@ -501,39 +567,38 @@ int vbx_resnet_create(vbx_ctx* ctx, int32_t embed_dim, const float* params, int6
     return VBX_OK;
 }
 
-int vbx_resnet_input(vbx_resnet* net, int32_t n, int32_t T, float** d_in) {
-    if (!net) return VBX_ERR_INVALID;
+// the network's own input buffer at `floats` or more
+static int rn_input(vbx_resnet* net, size_t floats, float** d_in) {
     vbx_ctx* ctx = net->ctx;
-    if (!d_in || n <= 0 || T <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_input: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (a smaller buffer may still be read by queued work)
-    const int rc = fb_reserve(ctx, &net->d_in, &net->cap_in, (size_t)n * RN_MEL * T);
+    const int rc = fb_reserve(ctx, &net->d_in, &net->cap_in, floats);
     if (rc != VBX_OK) return rc;
     *d_in = net->d_in;
     return VBX_OK;
 }
 
+int vbx_resnet_input(vbx_resnet* net, int32_t n, int32_t T, float** d_in) {
+    if (!net) return VBX_ERR_INVALID;
+    if (!d_in || n <= 0 || T <= 0) FAIL(net->ctx, VBX_ERR_INVALID, "vbx_resnet_input: bad argument");
+    return rn_input(net, (size_t)n * RN_MEL * T, d_in);
+}
+
 int vbx_resnet_input_ragged(vbx_resnet* net, int32_t n, const int32_t* T, float** d_in) {
     if (!net) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = net->ctx;
-    const int rc0 = rn_check_lengths(ctx, "vbx_resnet_input_ragged", n, T);
-    if (rc0 != VBX_OK) return rc0;
-    if (!d_in) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_input_ragged: d_in must not be NULL");
+    const int rc = rn_check_lengths(net->ctx, "vbx_resnet_input_ragged", n, T);
+    if (rc != VBX_OK) return rc;
+    if (!d_in) FAIL(net->ctx, VBX_ERR_INVALID, "vbx_resnet_input_ragged: d_in must not be NULL");
     size_t frames = 0;
     for (int b = 0; b < n; ++b) frames += (size_t)T[b];
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // (a smaller buffer may still be read by queued work)
-    const int rc = fb_reserve(ctx, &net->d_in, &net->cap_in, frames * RN_MEL);
-    if (rc != VBX_OK) return rc;
-    *d_in = net->d_in;
-    return VBX_OK;
+    return rn_input(net, frames * RN_MEL, d_in);
 }
 
 int vbx_resnet_run(vbx_resnet* net, int32_t n, int32_t T, const float* x, int x_on_device, float* out, int out_on_device) {
     if (!net) return VBX_ERR_INVALID;
     vbx_ctx* ctx = net->ctx;
     if (!x || !out || n <= 0 || T <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run: bad argument");
-    RnLevels g = rn_levels_uniform(n, T);
+    RnBatch g = rn_batch(n, RN_MEL, T, nullptr, RN_LEVELS);
     return rn_run(net, "vbx_resnet_run", g, x, x_on_device, out, out_on_device);
 }
 
@@ -544,7 +609,7 @@ int vbx_resnet_run_ragged(vbx_resnet* net, int32_t n, const int32_t* T, const fl
     const int rc = rn_check_lengths(ctx, "vbx_resnet_run_ragged", n, T);
     if (rc != VBX_OK) return rc;
     if (!x || !out) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_run_ragged: x and out must not be NULL");
-    RnLevels g = rn_levels_ragged(n, T);
+    RnBatch g = rn_batch(n, RN_MEL, 0, T, RN_LEVELS);
     return rn_run(net, "vbx_resnet_run_ragged", g, x, x_on_device, out, out_on_device);
 }
 
@@ -578,20 +643,6 @@ int vbx_resnet_conv_tile(int64_t M, int32_t Cout, int32_t* bn, int32_t* bm) {
     return VBX_OK;
 }
 
-// the tables of one ragged convolution step on host arrays: n windows of H rows and Wv[b] columns, stride s
-struct RnStepTables {
-    std::vector<long long> pos;                                // [2][n + 1]: the input's, the output's
-    std::vector<int> wid;                                      // [2][n]
-    RnStepTables(int n, int H, const int32_t* Wv, int s) : pos(2 * (size_t)(n + 1), 0), wid(2 * (size_t)n) {
-        for (int b = 0; b < n; ++b) {
-            wid[b] = Wv[b];
-            wid[n + b] = rn_out(Wv[b], s);
-            pos[b + 1] = pos[b] + (long long)H * wid[b];
-            pos[n + 1 + b + 1] = pos[n + 1 + b] + (long long)rn_out(H, s) * wid[n + b];
-        }
-    }
-};
-
 // vbx_resnet_conv, vbx_resnet_conv_gemm and vbx_resnet_conv_ragged: one convolution on host arrays in either mode; Wv: the
 // windows' widths of a ragged batch, or null (then all of them W wide)
 static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, int32_t n, int32_t H, int32_t W,
@@ -607,39 +658,25 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
     if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2))
         FAIL(ctx, VBX_ERR_INVALID, "%s: kernel size %d stride %d: built for 1 or 3 at stride 1 or 2", name, ks, stride);
     if (Cin % RN_BK != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cin = %d is not a multiple of %d", name, Cin, RN_BK);
-    RnCall c = rn_call(ks, stride, n, H, W, Cin, Cout, relu ? 1 : 0);
-    size_t nx = (size_t)n * H * W * Cin;
-    std::vector<long long> pos;                                // (outlive the copies, as wf and we below)
-    std::vector<int> wid;
-    if (Wv) {
-        RnStepTables t(n, H, Wv, stride);
-        pos.swap(t.pos);
-        wid.swap(t.wid);
-        c = rn_call_ragged(ks, stride, H, Cin, Cout, relu ? 1 : 0, RnRag{}, pos[2 * (size_t)n + 1]);
-        nx = (size_t)pos[n] * Cin;
-    }
+    RnBatch g = rn_batch(n, H, W, Wv, 2, stride);              // (outlives the copies, as wf and we below)
+    RnCall c = rn_call(RnConv{ks, stride, Cin, Cout}, relu ? 1 : 0, g, 0, 1);
+    const size_t nx = (size_t)g.M[0] * Cin;
     int BN = bn, BM = bm;
     if (bn == 0 && bm == 0) {
         if (Cout % 32 != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of 32", name, Cout);
-        rn_tile(c.M, Cout, &BN, &BM);
+        rn_tile(c.M(), Cout, &BN, &BM);
     } else {
         if (!rn_tile_built(bn, bm)) FAIL(ctx, VBX_ERR_INVALID, "%s: no BN x BM = %d x %d tile is built (RN_TILES)", name, bn, bm);
         if (Cout % bn != 0) FAIL(ctx, VBX_ERR_INVALID, "%s: Cout = %d is not a multiple of the tile's BN = %d", name, Cout, bn);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RnStep s(ctx);
-    const size_t ny = (size_t)c.M * Cout + 2 * (size_t)pad;
+    const size_t ny = (size_t)c.M() * Cout + 2 * (size_t)pad;
     float* dy;
     rc = s.up(x, nx, &c.x);
-    if (rc == VBX_OK && Wv) {
-        long long* dpos;
-        int* dwid;
-        rc = s.up_bytes(pos.data(), sizeof(long long) * pos.size(), &dpos);
-        if (rc == VBX_OK) rc = s.up_bytes(wid.data(), sizeof(int) * wid.size(), &dwid);
-        if (rc == VBX_OK) c.g = RnRag{dpos, dpos + n + 1, dwid, dwid + n, n};
-    }
+    if (rc == VBX_OK) rc = s.tables(g);
     if (rc == VBX_OK) rc = s.up(bias, (size_t)Cout, &c.b);
-    if (rc == VBX_OK) rc = s.up(res, (size_t)c.M * Cout, &c.res);
+    if (rc == VBX_OK) rc = s.up(res, (size_t)c.M() * Cout, &c.res);
     if (rc == VBX_OK) rc = s.up(y, ny, &dy);
     if (rc == VBX_OK && gemm == VBX_GEMM_EXACT) rc = s.up(w, (size_t)ks * ks * Cin * Cout, &c.w);
     if (rc != VBX_OK) return rc;
@@ -655,8 +692,7 @@ static int rn_conv_step(const char* name, vbx_ctx* ctx, int gemm, int32_t ks, in
         if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &dax);
         if (rc == VBX_OK) rc = s.up_bytes(nullptr, sizeof(unsigned) * n, &c.ay);
         if (rc != VBX_OK) return rc;
-        if (Wv) rn_amax_ragged(ctx->stream, c.x, n, c.g.pos_in, pos[n], Cin, dax);
-        else rn_amax(ctx->stream, c.x, n, (long long)H * W * Cin, dax);
+        rn_amax(ctx->stream, g, 0, Cin, c.x, dax);
         c.ax = dax;
     }
     if (!rn_launch(ctx->stream, c, BN, BM, gemm)) FAIL(ctx, VBX_ERR_INVALID, "%s: no kernel for this convolution", name);
@@ -689,85 +725,20 @@ int vbx_resnet_conv_ragged(vbx_ctx* ctx, int gemm, int32_t ks, int32_t stride, i
 }
 
 int vbx_resnet_stem(vbx_ctx* ctx, int32_t n, int32_t T, const float* x, const float* w, const float* bias, float* y, int64_t pad) {
-    if (!ctx) return VBX_ERR_INVALID;
-    if (!x || !w || !bias || !y || n <= 0 || T <= 0 || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_stem: bad argument");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RnStep s(ctx);
-    const long long total = (long long)n * RN_MEL * T * 32;
-    const size_t ny = (size_t)total + 2 * (size_t)pad;
-    float *dx, *dw, *db, *dy;
-    int rc = s.up(x, (size_t)n * RN_MEL * T, &dx);
-    if (rc == VBX_OK) rc = s.up(w, 9 * 32, &dw);
-    if (rc == VBX_OK) rc = s.up(bias, 32, &db);
-    if (rc == VBX_OK) rc = s.up(y, ny, &dy);
-    if (rc != VBX_OK) return rc;
-    hipLaunchKernelGGL(resnet_stem_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dw, db, dy + pad, T,
-                       total);
-    return s.down("vbx_resnet_stem", y, dy, ny);
+    return rn_stem_step("vbx_resnet_stem", ctx, false, n, T, nullptr, x, w, bias, y, pad);
 }
 
 int vbx_resnet_stem_ragged(vbx_ctx* ctx, int32_t n, const int32_t* T, const float* x, const float* w, const float* bias, float* y,
                            int64_t pad) {
-    if (!ctx) return VBX_ERR_INVALID;
-    int rc = rn_check_lengths(ctx, "vbx_resnet_stem_ragged", n, T);
-    if (rc != VBX_OK) return rc;
-    if (!x || !w || !bias || !y || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_stem_ragged: x, w, bias and y must not be NULL, pad not negative");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RnStep s(ctx);
-    const RnStepTables t(n, RN_MEL, T, 1);
-    const long long total = t.pos[n] * 32;
-    const size_t ny = (size_t)total + 2 * (size_t)pad;
-    float *dx, *dw, *db, *dy;
-    long long* dpos;
-    int* dwid;
-    rc = s.up(x, (size_t)t.pos[n], &dx);
-    if (rc == VBX_OK) rc = s.up(w, 9 * 32, &dw);
-    if (rc == VBX_OK) rc = s.up(bias, 32, &db);
-    if (rc == VBX_OK) rc = s.up(y, ny, &dy);
-    if (rc == VBX_OK) rc = s.up_bytes(t.pos.data(), sizeof(long long) * (n + 1), &dpos);
-    if (rc == VBX_OK) rc = s.up_bytes(t.wid.data(), sizeof(int) * n, &dwid);
-    if (rc != VBX_OK) return rc;
-    hipLaunchKernelGGL(resnet_stem_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dw, db,
-                       dy + pad, dpos, dwid, n, total);
-    return s.down("vbx_resnet_stem_ragged", y, dy, ny);
-}
-
-int vbx_resnet_pool_ragged(vbx_ctx* ctx, int32_t n, const int32_t* W4, const float* x, float* out, int64_t pad) {
-    if (!ctx) return VBX_ERR_INVALID;
-    int rc = rn_check_lengths(ctx, "vbx_resnet_pool_ragged", n, W4);
-    if (rc != VBX_OK) return rc;
-    if (!x || !out || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_pool_ragged: x and out must not be NULL, pad not negative");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RnStep s(ctx);
-    const RnStepTables t(n, RN_H4, W4, 1);
-    const long long total = (long long)n * RN_H4 * RN_C4;
-    const size_t ny = (size_t)n * RN_POOL + 2 * (size_t)pad;
-    float *dx, *dy;
-    long long* dpos;
-    int* dwid;
-    rc = s.up(x, (size_t)t.pos[n] * RN_C4, &dx);
-    if (rc == VBX_OK) rc = s.up(out, ny, &dy);
-    if (rc == VBX_OK) rc = s.up_bytes(t.pos.data(), sizeof(long long) * (n + 1), &dpos);
-    if (rc == VBX_OK) rc = s.up_bytes(t.wid.data(), sizeof(int) * n, &dwid);
-    if (rc != VBX_OK) return rc;
-    hipLaunchKernelGGL(resnet_pool_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dy + pad, dpos,
-                       dwid, total);
-    return s.down("vbx_resnet_pool_ragged", out, dy, ny);
+    return rn_stem_step("vbx_resnet_stem_ragged", ctx, true, n, 0, T, x, w, bias, y, pad);
 }
 
 int vbx_resnet_pool(vbx_ctx* ctx, int32_t n, int32_t W4, const float* x, float* out, int64_t pad) {
-    if (!ctx) return VBX_ERR_INVALID;
-    if (!x || !out || n <= 0 || W4 <= 0 || pad < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_resnet_pool: bad argument");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RnStep s(ctx);
-    const long long total = (long long)n * RN_H4 * RN_C4;
-    const size_t ny = (size_t)n * RN_POOL + 2 * (size_t)pad;
-    float *dx, *dy;
-    int rc = s.up(x, (size_t)total * W4, &dx);
-    if (rc == VBX_OK) rc = s.up(out, ny, &dy);
-    if (rc != VBX_OK) return rc;
-    hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx, dy + pad, W4, total);
-    return s.down("vbx_resnet_pool", out, dy, ny);
+    return rn_pool_step("vbx_resnet_pool", ctx, false, n, W4, nullptr, x, out, pad);
+}
+
+int vbx_resnet_pool_ragged(vbx_ctx* ctx, int32_t n, const int32_t* W4, const float* x, float* out, int64_t pad) {
+    return rn_pool_step("vbx_resnet_pool_ragged", ctx, true, n, 0, W4, x, out, pad);
 }
 
 }  // extern "C"

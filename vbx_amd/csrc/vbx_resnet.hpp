@@ -16,10 +16,14 @@
 // F.relu does (a NaN window must reach the embedding: predict.py skips it).
 //
 // Ragged batches (windows of mixed lengths in one run): at spatial level l (H_l = 64, 32, 16, 8) an activation tensor is the
-// concatenation of the windows' [H_l][W_{b,l}][C] blocks, window b starting at position pos_l[b] (RnRag).  The *_ragged
-// kernels are the same code with one change: a row m finds its window by a search of pos (rn_window) and takes its widths
-// and its input base from the tables, where the uniform kernels divide by Ho Wo (rn_row).  Taps, k order and zeros are the
-// same, so every window has the bits it has when it is run alone.
+// concatenation of the windows' [H_l][W_{b,l}][C] blocks, window b starting at position pos_l[b].  Every kernel is one
+// body with a compile-time RAG and takes the batch's geometry as its last argument, by value: nothing or one width in
+// the uniform instantiation, the level's tables in the ragged one (RnGeom for the convolutions, RnLevel for the rest).  One
+// if constexpr helper each is all that differs: a row m finds its window by a search of pos (rn_window) and takes its
+// widths and its input base from the tables, where the uniform instantiation divides by Ho Wo (rn_row; rn_locate and rn_span
+// for the stem, the pooling and resnet_amax_kernel).  Taps, k order and zeros are the same, so every window has the bits it
+// has when it is run alone.  In a profile the kernels carry their instantiation: resnet_stem_kernel<false> is the uniform
+// stem, resnet_stem_kernel<true> the ragged one, and so for resnet_pool_kernel and resnet_amax_kernel.
 #pragma once
 #include "vbx_device.hpp"
 
@@ -209,18 +213,58 @@ __global__ __launch_bounds__(256) void resnet_conv_kernel(const float* __restric
     }
 }
 
-// x [B][64][W] (the front end's window layout, one input channel), w [9][32] (tap r 3 + s), y [B][64][W][32] NHWC
+// One level of a batch as the stem, the pooling and resnet_amax_kernel take it, their last argument: every window W
+// positions wide, or (RAG) the level's tables: window b starts at position pos[b] ([n + 1], pos[n] = M) and is wid[b] wide.
+template <bool RAG> struct RnLevel {
+    int W;
+};
+template <> struct RnLevel<true> {
+    const long long* pos;
+    const int* wid;
+    int n;
+};
+
+// window b of a level of H rows: the position it starts at, how many it has, its width
+struct RnSpan {
+    long long start, count;
+    int W;
+};
+template <bool RAG> __device__ __forceinline__ RnSpan rn_span(const RnLevel<RAG>& g, long long b, int H) {
+    if constexpr (RAG) return RnSpan{g.pos[b], g.pos[b + 1] - g.pos[b], g.wid[b]};
+    else return RnSpan{b * H * (long long)g.W, (long long)H * g.W, g.W};
+}
+
+// position m of a level of RN_MEL rows -> its window's span, its row h and its column wo there: two divisions by W, or a
+// search of pos and one division
+template <bool RAG> __device__ __forceinline__ RnSpan rn_locate(const RnLevel<RAG>& g, long long m, int& h, int& wo) {
+    long long b;
+    if constexpr (RAG) {
+        b = rn_window(g.pos, g.n, m);
+        const int W = g.wid[b], rem = (int)(m - g.pos[b]);
+        h = rem / W;
+        wo = rem - h * W;
+    } else {
+        wo = (int)(m % g.W);
+        const long long t = m / g.W;
+        h = (int)(t % RN_MEL);
+        b = t / RN_MEL;
+    }
+    return rn_span(g, b, RN_MEL);
+}
+
+// x: the windows' [64][T_b] blocks end to end (the front end's window layout, one input channel), w [9][32] (tap r 3 + s),
+// y: their [64][T_b][32] NHWC blocks; total = 32 M
+template <bool RAG>
 __global__ __launch_bounds__(256) void resnet_stem_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                          const float* __restrict__ bias, float* __restrict__ y, int W,
-                                                          long long total) {
+                                                          const float* __restrict__ bias, float* __restrict__ y,
+                                                          long long total, RnLevel<RAG> g) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int c = (int)(idx & 31);
-    const long long pos = idx >> 5;
-    const int wo = (int)(pos % W);
-    const long long t = pos / W;
-    const int h = (int)(t % RN_MEL);
-    const float* __restrict__ xb = x + (t / RN_MEL) * RN_MEL * (long long)W;
+    int h, wo;
+    const RnSpan win = rn_locate(g, idx >> 5, h, wo);
+    const int W = win.W;
+    const float* __restrict__ xb = x + win.start;
     float acc = 0.0f;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -235,68 +279,21 @@ __global__ __launch_bounds__(256) void resnet_stem_kernel(const float* __restric
     y[idx] = rn_relu(acc + bias[c]);
 }
 
-// the stem over a ragged batch: x the concatenation of the windows' [64][T_b] blocks, y of their [64][T_b][32] blocks; window
-// b starts at position pos[b] of both (pos [n + 1] = 64 times the running sum of T, wid[b] = T_b); total = 32 pos[n]
-__global__ __launch_bounds__(256) void resnet_stem_ragged_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                 const float* __restrict__ bias, float* __restrict__ y,
-                                                                 const long long* __restrict__ pos, const int* __restrict__ wid,
-                                                                 int n, long long total) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int c = (int)(idx & 31);
-    const long long m = idx >> 5;
-    const int b = rn_window(pos, n, m), W = wid[b], rem = (int)(m - pos[b]), h = rem / W, wo = rem - h * W;
-    const float* __restrict__ xb = x + pos[b];
-    float acc = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int hi = h + r - 1;
-        if (hi < 0 || hi >= RN_MEL) continue;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            const int wi = wo + s - 1;
-            if (wi >= 0 && wi < W) acc = fmaf(xb[(long long)hi * W + wi], w[(r * 3 + s) * 32 + c], acc);
-        }
-    }
-    y[idx] = rn_relu(acc + bias[c]);
-}
-
-// x [B][8][W4][1024] -> out [B][16384]: [h 1024 + c] = mean over time, [8192 + h 1024 + c] = sqrt(mean(x^2) - mean^2 + 1e-10)
-// (resnet.py:138-140, summed in f64).  The embedding matrix's columns are permuted on the host to this order.
-__global__ __launch_bounds__(256) void resnet_pool_kernel(const float* __restrict__ x, float* __restrict__ out, int W4,
-                                                          long long total) {
+// x: the windows' [8][W4_b][1024] blocks end to end -> out [B][16384]: [h 1024 + c] = mean over time, [8192 + h 1024 + c] =
+// sqrt(mean(x^2) - mean^2 + 1e-10) (resnet.py:138-140, summed in f64), every window over its own W4_b.  The embedding
+// matrix's columns are permuted on the host to this order.  total = 8192 B
+template <bool RAG>
+__global__ __launch_bounds__(256) void resnet_pool_kernel(const float* __restrict__ x, float* __restrict__ out, long long total,
+                                                          RnLevel<RAG> g) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int c = (int)(idx & (RN_C4 - 1));
     const long long bh = idx >> 10;
     const int h = (int)(bh & (RN_H4 - 1));
     const long long b = bh >> 3;
-    const float* __restrict__ p = x + bh * W4 * RN_C4 + c;
-    double s = 0.0, s2 = 0.0;
-    for (int t = 0; t < W4; ++t) {
-        const double v = p[(long long)t * RN_C4];
-        s += v;
-        s2 += v * v;
-    }
-    const double mean = s / W4;
-    float* __restrict__ o = out + b * RN_POOL + h * RN_C4 + c;
-    o[0] = (float)mean;
-    o[RN_POOL / 2] = (float)sqrt(s2 / W4 - mean * mean + 1e-10);
-}
-
-// the pooling over a ragged batch: x the concatenation of the windows' [8][W4_b][1024] blocks, window b at position pos[b],
-// wid[b] = W4_b frames wide: its own divisor
-__global__ __launch_bounds__(256) void resnet_pool_ragged_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                                 const long long* __restrict__ pos, const int* __restrict__ wid,
-                                                                 long long total) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int c = (int)(idx & (RN_C4 - 1));
-    const long long bh = idx >> 10;
-    const int h = (int)(bh & (RN_H4 - 1));
-    const long long b = bh >> 3;
-    const int W4 = wid[b];
-    const float* __restrict__ p = x + (pos[b] + (long long)h * W4) * RN_C4 + c;
+    const RnSpan win = rn_span(g, b, RN_H4);
+    const int W4 = win.W;
+    const float* __restrict__ p = x + (win.start + (long long)h * W4) * RN_C4 + c;
     double s = 0.0, s2 = 0.0;
     for (int t = 0; t < W4; ++t) {
         const double v = p[(long long)t * RN_C4];

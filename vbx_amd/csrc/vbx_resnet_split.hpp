@@ -25,36 +25,18 @@ namespace vbx {
 
 constexpr int RS_BK = 32;        // K per LDS stage: two k-steps of 16
 
-// max |x| over the finite elements of every window -> amax[window] (zeroed beforehand); per_window a multiple of 4;
-// grid = n * bpw blocks, bpw blocks share a window
-__global__ __launch_bounds__(256) void resnet_amax_kernel(const float* __restrict__ x, long long per_window, int bpw,
-                                                          unsigned* __restrict__ amax) {
+// max |x| over the finite elements of every window of a level of H rows and C channels (C a multiple of 4) -> amax[window]
+// (zeroed beforehand); grid = n * bpw blocks, bpw blocks share a window.  One body for uniform and ragged batches, as the
+// convolution below: g (vbx_resnet.hpp: RnLevel) says where window b lies
+template <bool RAG>
+__global__ __launch_bounds__(256) void resnet_amax_kernel(const float* __restrict__ x, int H, int C, int bpw,
+                                                          unsigned* __restrict__ amax, RnLevel<RAG> g) {
     using f4 = Vec<float>::v4;
     const long long b = blockIdx.x / bpw;
     const int part = blockIdx.x - (int)(b * bpw);
-    const f4* __restrict__ src = reinterpret_cast<const f4*>(x + b * per_window);
-    const long long n4 = per_window >> 2;
-    int m = 0;
-    for (long long q = (long long)part * 256 + threadIdx.x; q < n4; q += 256LL * bpw) {
-        const f4 v = src[q];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int a = __builtin_bit_cast(int, v[j]) & 0x7fffffff;
-            m = vmax(m, a < 0x7f800000 ? a : 0);
-        }
-    }
-    m = allreduce_max<64>(m);
-    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(amax + b, (unsigned)m);
-}
-
-// the same over a ragged batch of C-channel tensors (C a multiple of 4): window b is positions pos[b] .. pos[b + 1]
-__global__ __launch_bounds__(256) void resnet_amax_ragged_kernel(const float* __restrict__ x, const long long* __restrict__ pos,
-                                                                 int C, int bpw, unsigned* __restrict__ amax) {
-    using f4 = Vec<float>::v4;
-    const long long b = blockIdx.x / bpw;
-    const int part = blockIdx.x - (int)(b * bpw);
-    const f4* __restrict__ src = reinterpret_cast<const f4*>(x + pos[b] * C);
-    const long long n4 = (pos[b + 1] - pos[b]) * C >> 2;
+    const RnSpan win = rn_span(g, b, H);
+    const f4* __restrict__ src = reinterpret_cast<const f4*>(x + win.start * C);
+    const long long n4 = win.count * C >> 2;
     int m = 0;
     for (long long q = (long long)part * 256 + threadIdx.x; q < n4; q += 256LL * bpw) {
         const f4 v = src[q];

@@ -74,7 +74,7 @@ LEVELS = 4                                             # spatial levels of the n
 
 def ragged_layout(lengths):
     """The layout of a ragged batch -- windows of lengths[b] >= 1 frames, in any order -- as the device builds it
-    (vbx_host_resnet.hpp: rn_levels_ragged): -> (pos int64 [4][n + 1], wid int32 [4][n]).  At level l (64 >> l rows) window b
+    (vbx_host_resnet.hpp: rn_batch): -> (pos int64 [4][n + 1], wid int32 [4][n]).  At level l (64 >> l rows) window b
     is wid[l][b] wide (the stride-2 output size applied l times to lengths[b]) and its [H_l][wid[l][b]][C] block starts at
     position pos[l][b] of the concatenated activation tensor; pos[l][n] = M_l, all positions of the level."""
     lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
