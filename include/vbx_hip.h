@@ -378,7 +378,9 @@ int vbx_scores_destroy(vbx_scores* sc);
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then
  * cmvn_floating_kaldi(., LC, RC, norm_vars=False) cast to float32.  The four linear steps run as ONE f64 operator on the
- * matrix cores (vbx_fbank.hpp).  The dither is the caller's (numpy's generator: predict.py:169-170). */
+ * matrix cores (vbx_fbank.hpp).  The dither before it (predict.py:169-170, numpy's legacy generator) is either the
+ * caller's, who passes the dithered f64 signal to vbx_fbank_run, or the library's: vbx_fbank_run_raw takes the int16
+ * samples and draws the same MT19937 stream on the device, bit for bit. */
 typedef struct vbx_fbank vbx_fbank;
 /* window [winlen], mel [nfft/2 + 1][n_mel] f64 (features.mel_fbank_mx).  Geometries built: winlen / shift / nfft =
  * 400 / 160 / 512 (16 kHz) and 200 / 80 / 256 (8 kHz), n_mel = 64; others: VBX_ERR_UNSUPPORTED. */
@@ -390,6 +392,18 @@ int vbx_fbank_create(vbx_ctx* ctx, int32_t winlen, int32_t shift, int32_t nfft, 
  * rows each.  Returns once the host arrays may be reused. */
 int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_t n_seg, const int64_t* seg, int32_t cmn_lc,
                   int32_t cmn_rc, int64_t* n_frames);
+/* vbx_fbank_run from the raw int16 samples [n_samples] of n_rec recordings: rec [n_rec][2] = (first sample, samples) of
+ * each.  Recording r becomes x + levels[r] * (2 u - 1) in f64 with u = np.random.RandomState(seeds[r]).rand(samples), every
+ * sample of it in order (not only the segments), the stream restarting from its seed for every recording; the signal
+ * vbx_fbank_run would have been given, one quarter of the bytes uploaded.  Samples that belong to no recording are zero.
+ * Then the launch sequence of vbx_fbank_run; returns once the host arrays may be reused.  VBX_ERR_INVALID with a message:
+ * a NULL pointer, n_rec <= 0, a recording that runs past n_samples, two recordings that overlap. */
+int vbx_fbank_run_raw(vbx_fbank* fb, int64_t n_samples, const int16_t* samples, int32_t n_rec, const int64_t* rec,
+                      const uint32_t* seeds, const double* levels, int32_t n_seg, const int64_t* seg, int32_t cmn_lc,
+                      int32_t cmn_rc, int64_t* n_frames);
+/* samples [first, first + n) of the f64 signal of the last run (uploaded by vbx_fbank_run, written by vbx_fbank_run_raw).
+ * Synchronises before it returns. */
+int vbx_fbank_get_signal(vbx_fbank* fb, int64_t first, int64_t n, double* dst, int dst_on_device);
 /* rows [row0, row0 + nrows) of the last run: which = 0 the CMN features (f32), 1 the log-Mel rows before CMN (f64).
  * dst_on_device != 0: dst is device memory of the ctx's device (e.g. a torch tensor).  Synchronises before it returns. */
 int vbx_fbank_get(vbx_fbank* fb, int which, int64_t row0, int64_t nrows, void* dst, int dst_on_device);
@@ -403,6 +417,9 @@ int vbx_fbank_windows(vbx_fbank* fb, int32_t n, const int64_t* starts, int32_t l
 int vbx_fbank_windows_ragged(vbx_fbank* fb, int32_t n, const int64_t* starts, const int32_t* lens, float* dst, int dst_on_device);
 /* device milliseconds (HIP events) of the last run: ms[0] upload, [1] frame kernel, [2] CMN; ms[3] the last windows call. */
 int vbx_fbank_times(vbx_fbank* fb, float* ms);
+/* device milliseconds of the dither kernel of the last run (between its upload and its frame kernel); 0 if that run was
+ * no vbx_fbank_run_raw. */
+int vbx_fbank_dither_time(vbx_fbank* fb, float* ms);
 int vbx_fbank_destroy(vbx_fbank* fb);
 
 /* ---- x-vector network ------------------------------------------------------------------------------------------------

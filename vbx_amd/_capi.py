@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     'vbx_resnet_set_gemm', 'vbx_resnet_gemm_in_effect', 'vbx_resnet_conv_gemm', 'vbx_resnet_split_weights',
     'vbx_fbank_windows_ragged', 'vbx_resnet_run_ragged', 'vbx_resnet_input_ragged',
     'vbx_resnet_conv_ragged', 'vbx_resnet_stem_ragged', 'vbx_resnet_pool_ragged',
+    'vbx_fbank_run_raw', 'vbx_fbank_get_signal', 'vbx_fbank_dither_time',
 ]
 
 
@@ -155,6 +156,9 @@ def load():
     lib.vbx_resnet_conv_ragged.argtypes = [vp, C.c_int, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, C.c_int, i32, i32, vp, i64, vp]
     lib.vbx_resnet_stem_ragged.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64]
     lib.vbx_resnet_pool_ragged.argtypes = [vp, i32, vp, vp, vp, i64]
+    lib.vbx_fbank_run_raw.argtypes = [vp, i64, vp, i32, vp, vp, vp, i32, vp, i32, i32, C.POINTER(i64)]
+    lib.vbx_fbank_get_signal.argtypes = [vp, i64, i64, vp, C.c_int]
+    lib.vbx_fbank_dither_time.argtypes = [vp, C.POINTER(C.c_float)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -383,6 +387,39 @@ class FbankDevice:
                                                int(rc), C.byref(rows)), 'vbx_fbank_run')
         self.rows = rows.value
         return self.rows
+
+    def run_raw(self, samples, rec, seeds, levels, segs, lc=150, rc=149):
+        """samples int16 [n] of the recordings rec int64 [n_rec][2] (first sample, samples), dithered on the device with
+        np.random.RandomState(seeds[r])'s stream at levels[r] (vbx_fbank_run_raw); then as run()."""
+        samples = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
+        rec = np.ascontiguousarray(rec, dtype=np.int64).reshape(-1, 2)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        levels = _f64(levels).reshape(-1)
+        if not (rec.shape[0] == seeds.shape[0] == levels.shape[0]):
+            raise ValueError(f'run_raw: {rec.shape[0]} recordings, {seeds.shape[0]} seeds, {levels.shape[0]} levels')
+        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 2)
+        rows = C.c_int64()
+        self.ctx.check(self._lib.vbx_fbank_run_raw(self._h, samples.shape[0], _ptr(samples), rec.shape[0], _ptr(rec),
+                                                   _ptr(seeds), _ptr(levels), segs.shape[0], _ptr(segs), int(lc), int(rc),
+                                                   C.byref(rows)), 'vbx_fbank_run_raw')
+        self.rows = rows.value
+        return self.rows
+
+    def signal(self, first, n, dst_ptr=None):
+        """samples [first, first + n) of the f64 signal of the last run; into a host array, or into device memory."""
+        out = None
+        if dst_ptr is None:
+            out = np.empty(int(n), dtype=np.float64)
+            dst_ptr = out.ctypes.data
+        self.ctx.check(self._lib.vbx_fbank_get_signal(self._h, int(first), int(n), C.c_void_p(dst_ptr), int(out is None)),
+                       'vbx_fbank_get_signal')
+        return out
+
+    def dither_time(self):
+        """device ms of the dither kernel of the last run (0.0 after a run that was given the dithered signal)."""
+        ms = C.c_float()
+        self.ctx.check(self._lib.vbx_fbank_dither_time(self._h, C.byref(ms)), 'vbx_fbank_dither_time')
+        return float(ms.value)
 
     def get(self, which, row0, nrows, dst_ptr=None):
         """rows of the CMN features ('fea', f32) or the log-Mel rows ('logmel', f64); into a host array, or into device

@@ -13,6 +13,8 @@
 //   fbank_cmn_kernel     cmvn_floating_kaldi(fea, LC, RC, norm_vars=False) per segment, cast to f32
 //   fbank_gather_kernel  windows [n][64][len] (the model's [B, C, T] layout) from the CMN rows; fbank_gather_ragged_kernel:
 //                        windows of mixed lengths, their [64][len_w] blocks laid end to end
+//   fbank_dither_kernel  the dither before all of this (predict.py:169-170), for a caller that hands over the raw int16
+//                        samples: numpy's legacy MT19937 stream, word for word, one workgroup per recording
 #pragma once
 #include "vbx_device.hpp"
 
@@ -160,6 +162,110 @@ __global__ __launch_bounds__(256) void fbank_gather_ragged_kernel(const float* _
         }
         __syncthreads();
     }
+}
+
+// ---- dither: x + level (2 rand - 1) with rand = np.random.RandomState(seed).rand ------------------------------------
+// numpy's legacy generator is plain MT19937: 624 words of state, regenerated ("twisted") every 624 draws, each draw
+// tempered, and a double made of two draws, r = ((a >> 5) 2^26 + (b >> 6)) / 2^53.  A twist is sequential as written,
+//     new[i] = f(old[i], old[i + 1], i < 227 ? old[i + 397] : new[i - 227]),
+//     f(u, v, w) = w ^ (y >> 1) ^ (y & 1 ? 0x9908b0df : 0), y = (u & 0x80000000) | (v & 0x7fffffff),
+// but only through new[i - 227] and, for the last word, new[0]: words 0 .. 226 | 227 .. 453 | 454 .. 622 and 623 are
+// three data-parallel phases with the same result (623 reads new[0] and new[396], both there after the second).
+constexpr int MT_N = 624, MT_M = 397, MT_PAIRS = MT_N / 2;
+constexpr int MT_AHEAD = 8;    // twists whose samples are in flight together (even)
+
+struct FbRec {
+    long long first, n;        // the recording's samples in the concatenated signal
+    double level;
+};
+
+__device__ __forceinline__ unsigned mt_f(unsigned u, unsigned v, unsigned w) {
+    const unsigned y = (u & 0x80000000u) | (v & 0x7fffffffu);
+    return w ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+
+__device__ __forceinline__ unsigned mt_temper(unsigned y) {
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    return y ^ (y >> 18);
+}
+
+// x + level (2 r - 1) of one sample: 2 r - 1 is exact (a multiple of 2^-52 below 1 in magnitude); the product rounds
+// once for a level that is no power of two, and must then not be fused into the add, which numpy rounds separately
+__device__ __forceinline__ double mt_dither(double x, double level, uint2 w) {
+#pragma clang fp contract(off)
+    const double r = ((double)(mt_temper(w.x) >> 5) * 67108864.0 + (double)(mt_temper(w.y) >> 6)) * (1.0 / 9007199254740992.0);
+    const double d = level * (r * 2.0 - 1.0);
+    return x + d;
+}
+
+// MT_AHEAD twists of the state in LDS and their doubles: twist tw0 + k reads copy k & 1 and writes the other one
+// (MT_AHEAD is even), then the doubles of samples (tw0 + k) 312 + tid (and + 256 for the first 56 threads) are read from
+// the written copy while the next twist already writes the one just read.  s: those samples.  FULL: all MT_AHEAD twists
+// lie inside the n samples, nothing is masked (and the compiler can count the stores that follow a load).
+template <bool FULL>
+__device__ __forceinline__ void mt_group(unsigned (&mt)[2][MT_N], int tid, long long tw0, long long ntw, long long n,
+                                         const int (&s)[MT_AHEAD][2], double level, double* __restrict__ o) {
+    constexpr int P2 = MT_N - MT_M, P3 = 2 * P2;                // 227, 454: the first words of phases 2 and 3
+    const bool two = tid < MT_PAIRS - 256;
+#pragma unroll
+    for (int k = 0; k < MT_AHEAD; ++k) {
+        if (!FULL && tw0 + k >= ntw) break;                     // (the same for every thread, as the barriers need it)
+        const unsigned* old = mt[k & 1];
+        unsigned* nw = mt[(k & 1) ^ 1];
+        if (tid < P2) nw[tid] = mt_f(old[tid], old[tid + 1], old[tid + MT_M]);
+        __syncthreads();
+        if (tid < P2) nw[P2 + tid] = mt_f(old[P2 + tid], old[P2 + tid + 1], nw[tid]);
+        __syncthreads();
+        if (tid < MT_N - 1 - P3)
+            nw[P3 + tid] = mt_f(old[P3 + tid], old[P3 + tid + 1], nw[P2 + tid]);
+        else if (tid == 255)
+            nw[MT_N - 1] = mt_f(old[MT_N - 1], nw[0], nw[MT_M - 1]);
+        __syncthreads();
+        const uint2* pairs = reinterpret_cast<const uint2*>(nw);
+        const long long p0 = (tw0 + k) * MT_PAIRS + tid, p1 = p0 + 256;
+        if (FULL || p0 < n) o[p0] = mt_dither((double)s[k][0], level, pairs[tid]);
+        if (two && (FULL || p1 < n)) o[p1] = mt_dither((double)s[k][1], level, pairs[tid + 256]);
+    }
+}
+
+// sig[first + p] = raw[first + p] + level (2 rand_p - 1), p < n, for recording blockIdx.x: its stream restarts from
+// states[blockIdx.x] (the 624 words init_genrand leaves, position 624: the first draw twists).  The state lives in LDS in
+// two copies, a twist reads one and writes the other, so no thread overwrites a word a neighbour still reads.  Trip
+// counts and barriers depend on the recording only; a twist past the end of the recording only masks its stores.
+__global__ __launch_bounds__(256) void fbank_dither_kernel(const short* __restrict__ raw, const FbRec* __restrict__ recs,
+                                                           const unsigned* __restrict__ states, double* __restrict__ sig) {
+    __shared__ __attribute__((aligned(8))) unsigned mt[2][MT_N];
+    const FbRec rc = recs[blockIdx.x];
+    const int tid = threadIdx.x;
+    if (rc.n <= 0) return;
+    for (int i = tid; i < MT_N; i += 256) mt[0][i] = states[(long long)blockIdx.x * MT_N + i];
+    __syncthreads();
+    const short* __restrict__ x = raw + rc.first;
+    double* __restrict__ o = sig + rc.first;
+    const long long ntw = (rc.n + MT_PAIRS - 1) / MT_PAIRS;
+    const long long nfull = rc.n / (MT_PAIRS * MT_AHEAD) * MT_AHEAD;   // the twists of the groups with nothing to mask
+    // the samples of a group of twists are fetched together, a group ahead of the twists that use them: a twist is far
+    // shorter than a trip to memory (indices past the recording are clamped into it, their results never stored)
+    int sc[MT_AHEAD][2], sn[MT_AHEAD][2];                       // (a register each: packed halves would wait for their loads at once)
+    auto fetch = [&](long long tw0, int (&s)[MT_AHEAD][2]) {
+#pragma unroll
+        for (int k = 0; k < MT_AHEAD; ++k) {
+            const long long p0 = (tw0 + k) * MT_PAIRS + tid;
+            s[k][0] = x[min(p0, rc.n - 1)];
+            s[k][1] = x[min(tid < MT_PAIRS - 256 ? p0 + 256 : p0, rc.n - 1)];
+        }
+    };
+    fetch(0, sc);
+    long long tw0 = 0;
+    for (; tw0 < nfull; tw0 += MT_AHEAD) {
+        fetch(tw0 + MT_AHEAD, sn);
+        mt_group<true>(mt, tid, tw0, ntw, rc.n, sc, rc.level, o);
+#pragma unroll
+        for (int k = 0; k < MT_AHEAD; ++k) sc[k][0] = sn[k][0], sc[k][1] = sn[k][1];
+    }
+    if (tw0 < ntw) mt_group<false>(mt, tid, tw0, ntw, rc.n, sc, rc.level, o);   // (fewer than MT_AHEAD twists are left)
 }
 
 }  // namespace vbx

@@ -12,9 +12,26 @@ struct vbx_fbank {
     FbSeg* d_segs = nullptr;
     FbTile* d_tiles = nullptr;                                 // 64-frame blocks: the frame kernel's tiles and the CMN kernel's blocks
     long long* d_starts = nullptr;
-    size_t cap_sig = 0, cap_logmel = 0, cap_fea = 0, cap_segs = 0, cap_tiles = 0, cap_starts = 0;
+    // a raw run (vbx_fbank_run_raw): the int16 samples, the recording table and the generator states
+    short* d_raw = nullptr;
+    FbRec* d_recs = nullptr;
+    unsigned* d_mt = nullptr;
+    size_t cap_sig = 0, cap_logmel = 0, cap_fea = 0, cap_segs = 0, cap_tiles = 0, cap_starts = 0, cap_raw = 0, cap_recs = 0,
+           cap_mt = 0;
     long long rows = 0;                                        // feature rows of the last run
+    long long n_sig = 0;                                       // samples of the last run
+    bool raw = false;                                          // the last run was a raw one
     hipEvent_t ev[6] = {};                                     // upload | frame | cmn of a run; gather of a windows call
+    hipEvent_t evd[2] = {};                                    // the dither kernel of a raw run
+};
+
+// the recordings of a raw run: samples, their table [n_rec][2] = (first sample, samples), a seed and a level each
+struct FbRaw {
+    const int16_t* samples;
+    int n_rec;
+    const int64_t* rec;
+    const uint32_t* seeds;
+    const double* levels;
 };
 
 template <typename T> static int fb_reserve(vbx_ctx* ctx, T** p, size_t* cap, size_t count) {
@@ -35,9 +52,11 @@ int vbx_fbank_destroy(vbx_fbank* fb) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (void* p : {(void*)fb->d_MT, (void*)fb->d_melT, (void*)fb->d_melr, (void*)fb->d_sig, (void*)fb->d_logmel, (void*)fb->d_fea,
-                    (void*)fb->d_segs, (void*)fb->d_tiles, (void*)fb->d_starts})
+                    (void*)fb->d_segs, (void*)fb->d_tiles, (void*)fb->d_starts, (void*)fb->d_raw, (void*)fb->d_recs, (void*)fb->d_mt})
         ctx_free(ctx, p);
     for (auto& e : fb->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : fb->evd)
         if (e) (void)hipEventDestroy(e);
     delete fb;
     return VBX_OK;
@@ -118,6 +137,8 @@ int vbx_fbank_create(vbx_ctx* ctx, int32_t winlen, int32_t shift, int32_t nfft, 
         if (e == hipSuccess) e = hipMemcpy(fb->d_melr, melr.data(), sizeof(int2) * FB_MEL, hipMemcpyHostToDevice);
         for (auto& ev : fb->ev)
             if (e == hipSuccess) e = hipEventCreate(&ev);
+        for (auto& ev : fb->evd)
+            if (e == hipSuccess) e = hipEventCreate(&ev);
         if (e != hipSuccess) {
             ctx->err = std::string("vbx_fbank_create: ") + hipGetErrorString(e);
             rc = VBX_ERR_HIP;
@@ -131,12 +152,11 @@ int vbx_fbank_create(vbx_ctx* ctx, int32_t winlen, int32_t shift, int32_t nfft, 
     return VBX_OK;
 }
 
-int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_t n_seg, const int64_t* seg, int32_t cmn_lc,
-                  int32_t cmn_rc, int64_t* n_frames) {
-    if (!fb) return VBX_ERR_INVALID;
+// one run: the signal comes up as f64 (signal), or as int16 samples that the dither kernel turns into it (raw); the tables
+// and the frame and CMN launches are the same
+static int fb_run(vbx_fbank* fb, const char* fn, int64_t n_samples, const double* signal, const FbRaw* raw, int32_t n_seg,
+                  const int64_t* seg, int32_t cmn_lc, int32_t cmn_rc, int64_t* n_frames) {
     vbx_ctx* ctx = fb->ctx;
-    if (!signal || !seg || n_samples <= 0 || n_seg <= 0 || cmn_lc < 0 || cmn_rc < 0)
-        FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<FbSeg> segs(n_seg);
     std::vector<FbTile> tiles;
@@ -145,16 +165,50 @@ int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_
         const long long a = seg[2 * s], n = seg[2 * s + 1];
         // a segment needs one full frame and its leading mirror: predict.py only passes segments of more than 0.01 s
         if (a < 0 || n <= fb->pre || n > (1LL << 30) || a + n > n_samples)
-            FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run: segment %d (start %lld, %lld samples) outside the signal or shorter "
-                 "than %d samples", s, a, n, fb->pre + 1);
+            FAIL(ctx, VBX_ERR_INVALID, "%s: segment %d (start %lld, %lld samples) outside the signal or shorter "
+                 "than %d samples", fn, s, a, n, fb->pre + 1);
         const long long padlen = fb->pre + n + std::min<long long>(fb->post_cap, n);
-        if (padlen < fb->L) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run: segment %d is shorter than one frame", s);
+        if (padlen < fb->L) FAIL(ctx, VBX_ERR_INVALID, "%s: segment %d is shorter than one frame", fn, s);
         const int nf = (int)((padlen - fb->L) / fb->shift + 1);
         segs[s] = FbSeg{a, rows, (int)n, nf};
         for (int f0 = 0; f0 < nf; f0 += FB_TILE) tiles.push_back(FbTile{s, f0});
         rows += nf;
     }
+    // a raw run: the recordings lie inside the samples and apart from each other, and each gets init_genrand(seed):
+    // mt[0] = seed, mt[i] = 1812433253 (mt[i - 1] ^ (mt[i - 1] >> 30)) + i
+    std::vector<FbRec> recs;
+    std::vector<uint32_t> states;
+    long long covered = 0;
+    if (raw) {
+        recs.resize(raw->n_rec);
+        std::vector<int> order(raw->n_rec);
+        for (int r = 0; r < raw->n_rec; ++r) {
+            const long long a = raw->rec[2 * r], n = raw->rec[2 * r + 1];
+            if (a < 0 || n < 0 || a > n_samples || n > n_samples - a)
+                FAIL(ctx, VBX_ERR_INVALID, "%s: recording %d (start %lld, %lld samples) outside the %lld samples", fn, r, a, n,
+                     (long long)n_samples);
+            recs[r] = FbRec{a, n, raw->levels[r]};
+            order[r] = r;
+            covered += n;
+        }
+        std::sort(order.begin(), order.end(), [&](int p, int q) { return recs[p].first < recs[q].first; });
+        for (int k = 1; k < raw->n_rec; ++k) {
+            const FbRec &p = recs[order[k - 1]], &q = recs[order[k]];
+            if (p.n > 0 && q.n > 0 && p.first + p.n > q.first)
+                FAIL(ctx, VBX_ERR_INVALID, "%s: recordings %d (start %lld, %lld samples) and %d (start %lld) overlap", fn,
+                     order[k - 1], p.first, p.n, order[k], q.first);
+        }
+        states.resize((size_t)raw->n_rec * MT_N);
+        for (int r = 0; r < raw->n_rec; ++r) {
+            uint32_t* mt = &states[(size_t)r * MT_N];
+            mt[0] = raw->seeds[r];
+            for (int i = 1; i < MT_N; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+        }
+    }
     int rc = fb_reserve(ctx, &fb->d_sig, &fb->cap_sig, (size_t)n_samples);
+    if (rc == VBX_OK && raw) rc = fb_reserve(ctx, &fb->d_raw, &fb->cap_raw, (size_t)n_samples);
+    if (rc == VBX_OK && raw) rc = fb_reserve(ctx, &fb->d_recs, &fb->cap_recs, recs.size());
+    if (rc == VBX_OK && raw) rc = fb_reserve(ctx, &fb->d_mt, &fb->cap_mt, states.size());
     if (rc == VBX_OK) rc = fb_reserve(ctx, &fb->d_segs, &fb->cap_segs, segs.size());
     if (rc == VBX_OK) rc = fb_reserve(ctx, &fb->d_tiles, &fb->cap_tiles, tiles.size());
     if (rc == VBX_OK) rc = fb_reserve(ctx, &fb->d_logmel, &fb->cap_logmel, (size_t)rows * FB_MEL);
@@ -162,9 +216,25 @@ int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_
     if (rc != VBX_OK) return rc;
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, hipEventRecord(fb->ev[0], st));
-    HIPCHK(ctx, hipMemcpyAsync(fb->d_sig, signal, sizeof(double) * (size_t)n_samples, hipMemcpyHostToDevice, st));
+    if (raw) {
+        HIPCHK(ctx, hipMemcpyAsync(fb->d_raw, raw->samples, sizeof(short) * (size_t)n_samples, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(fb->d_recs, recs.data(), sizeof(FbRec) * recs.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(fb->d_mt, states.data(), sizeof(uint32_t) * states.size(), hipMemcpyHostToDevice, st));
+    } else {
+        HIPCHK(ctx, hipMemcpyAsync(fb->d_sig, signal, sizeof(double) * (size_t)n_samples, hipMemcpyHostToDevice, st));
+    }
     HIPCHK(ctx, hipMemcpyAsync(fb->d_segs, segs.data(), sizeof(FbSeg) * segs.size(), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(fb->d_tiles, tiles.data(), sizeof(FbTile) * tiles.size(), hipMemcpyHostToDevice, st));
+    if (raw) {
+        // samples that belong to no recording carry no dither and are zero
+        if (covered < n_samples) HIPCHK(ctx, hipMemsetAsync(fb->d_sig, 0, sizeof(double) * (size_t)n_samples, st));
+        HIPCHK(ctx, hipEventRecord(fb->evd[0], st));
+        hipLaunchKernelGGL(fbank_dither_kernel, dim3((unsigned)raw->n_rec), dim3(256), 0, st, fb->d_raw, fb->d_recs, fb->d_mt,
+                           fb->d_sig);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(fb->evd[1], st));
+    }
+    fb->raw = raw != nullptr;
     HIPCHK(ctx, hipEventRecord(fb->ev[1], st));
     if (fb->L == 400)
         hipLaunchKernelGGL((fbank_frame_kernel<400, 160, 272>), dim3((unsigned)tiles.size()), dim3(256), 0, st, fb->d_sig,
@@ -179,9 +249,46 @@ int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(fb->ev[3], st));
     fb->rows = rows;
+    fb->n_sig = n_samples;
     if (n_frames) *n_frames = rows;
     // the host arrays above go out of scope: the copies from them must have landed
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return VBX_OK;
+}
+
+int vbx_fbank_run(vbx_fbank* fb, int64_t n_samples, const double* signal, int32_t n_seg, const int64_t* seg, int32_t cmn_lc,
+                  int32_t cmn_rc, int64_t* n_frames) {
+    if (!fb) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = fb->ctx;
+    if (!signal || !seg || n_samples <= 0 || n_seg <= 0 || cmn_lc < 0 || cmn_rc < 0)
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run: bad argument");
+    return fb_run(fb, "vbx_fbank_run", n_samples, signal, nullptr, n_seg, seg, cmn_lc, cmn_rc, n_frames);
+}
+
+int vbx_fbank_run_raw(vbx_fbank* fb, int64_t n_samples, const int16_t* samples, int32_t n_rec, const int64_t* rec,
+                      const uint32_t* seeds, const double* levels, int32_t n_seg, const int64_t* seg, int32_t cmn_lc,
+                      int32_t cmn_rc, int64_t* n_frames) {
+    if (!fb) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = fb->ctx;
+    if (!samples || !rec || !seeds || !levels || !seg)
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run_raw: samples, rec, seeds, levels and seg must not be NULL");
+    if (n_rec <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run_raw: n_rec = %d recordings, need at least one", n_rec);
+    if (n_samples <= 0 || n_seg <= 0 || cmn_lc < 0 || cmn_rc < 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_run_raw: bad argument");
+    const FbRaw raw{samples, n_rec, rec, seeds, levels};
+    return fb_run(fb, "vbx_fbank_run_raw", n_samples, nullptr, &raw, n_seg, seg, cmn_lc, cmn_rc, n_frames);
+}
+
+int vbx_fbank_get_signal(vbx_fbank* fb, int64_t first, int64_t n, double* dst, int dst_on_device) {
+    if (!fb) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = fb->ctx;
+    if (!dst) FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_get_signal: dst must not be NULL");
+    if (first < 0 || n < 0 || first > fb->n_sig || n > fb->n_sig - first)
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_fbank_get_signal: samples %lld + %lld past the %lld of the last run", (long long)first,
+             (long long)n, fb->n_sig);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(dst, fb->d_sig + first, sizeof(double) * (size_t)n,
+                               dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return VBX_OK;
 }
 
@@ -281,10 +388,19 @@ int vbx_fbank_times(vbx_fbank* fb, float* ms) {
     if (!fb || !ms) return VBX_ERR_INVALID;
     vbx_ctx* ctx = fb->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipEventElapsedTime(&ms[0], fb->ev[0], fb->ev[1]));
+    HIPCHK(ctx, hipEventElapsedTime(&ms[0], fb->ev[0], fb->raw ? fb->evd[0] : fb->ev[1]));   // (a raw run: up to its dither kernel)
     HIPCHK(ctx, hipEventElapsedTime(&ms[1], fb->ev[1], fb->ev[2]));
     HIPCHK(ctx, hipEventElapsedTime(&ms[2], fb->ev[2], fb->ev[3]));
     if (hipEventElapsedTime(&ms[3], fb->ev[4], fb->ev[5]) != hipSuccess) ms[3] = 0.0f;   // (no windows call yet)
+    return VBX_OK;
+}
+
+int vbx_fbank_dither_time(vbx_fbank* fb, float* ms) {
+    if (!fb || !ms) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = fb->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    *ms = 0.0f;                                                 // (the last run was no raw one)
+    if (fb->raw) HIPCHK(ctx, hipEventElapsedTime(ms, fb->evd[0], fb->evd[1]));
     return VBX_OK;
 }
 

@@ -2,6 +2,8 @@
 
     read_wav / read_lab        predict.py:149-151 (16-bit PCM through the standard library; soundfile is not needed)
     dither                     predict.py:169-170, numpy's legacy generator on the host (bit-exact)
+    mt19937_seed_state,        the same dither drawn on the device (FrontEnd.run_raw, dither_on='device'): the state
+    raw_samples                np.random.seed leaves, and the int16 samples that go up instead of the f64 signal
     povey_window, mel_matrix   features.py:povey_window / mel_fbank_mx(htk_bug=False) for the two supported rates
     segments, window_plan      predict.py:171-204: which VAD segments are processed, the 144-frame windows every 24
                                frames, their ark keys and segments-file lines
@@ -36,16 +38,17 @@ def geometry(sr: int) -> dict:
 
 
 # ---- input ---------------------------------------------------------------------------------------------------------
-def read_wav(path: str):
+def read_wav(path: str, raw: bool = False):
     """(samples as int64, sample rate) of a mono 16-bit PCM WAV at 8 or 16 kHz: (sf.read(path)[0] * 2**15).astype(int) of
-    predict.py:149,170 is exactly the int16 sample values for such a file.  Anything else is refused."""
+    predict.py:149,170 is exactly the int16 sample values for such a file.  Anything else is refused.  raw: the samples
+    stay int16, as the device dither takes them."""
     with wave.open(path, 'rb') as w:
         ch, width, sr, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
         if ch != 1 or width != 2:
             raise ValueError(f'{path}: {ch} channel(s) of {8 * width}-bit samples; only mono 16-bit PCM is supported')
         geometry(sr)
         data = w.readframes(n)
-    return np.frombuffer(data, dtype='<i2').astype(np.int64), sr
+    return np.frombuffer(data, dtype='<i2').astype(np.int16 if raw else np.int64), sr
 
 
 def write_wav(path: str, samples, sr: int):
@@ -64,6 +67,36 @@ def read_lab(path: str, sr: int) -> np.ndarray:
 def dither(x, seed: int = DITHER_SEED, level: int = DITHER_LEVEL) -> np.ndarray:
     """features.add_dither after np.random.seed(seed) (predict.py:169-170), without touching the global generator."""
     return x + level * (np.random.RandomState(seed).rand(*np.shape(x)) * 2 - 1)
+
+
+def mt19937_seed_state(seed: int) -> np.ndarray:
+    """The 624 words np.random.RandomState(seed) starts from (init_genrand of an int seed): mt[0] = seed,
+    mt[i] = 1812433253 (mt[i - 1] ^ (mt[i - 1] >> 30)) + i mod 2^32.  The device does the same for run_raw."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f'Seed must be between 0 and 2**32 - 1, got {seed}')
+    mt = np.empty(624, dtype=np.uint32)
+    w = seed
+    mt[0] = w
+    for i in range(1, 624):
+        w = (1812433253 * (w ^ (w >> 30)) + i) & 0xffffffff
+        mt[i] = w
+    return mt
+
+
+def raw_samples(x) -> np.ndarray:
+    """The samples of a recording as int16, the type the device dithers: an integer array (what read_wav returns) whose
+    values fit; anything else is refused, never wrapped."""
+    x = np.asarray(x)
+    if x.dtype.kind not in 'iu':
+        raise ValueError(f'raw samples must be integers, got dtype {x.dtype}')
+    x = x.reshape(-1)
+    if x.dtype == np.int16 or x.size == 0:
+        return x.astype(np.int16, copy=False)
+    if x.min() < -32768 or x.max() > 32767:
+        bad = int(np.flatnonzero((x < -32768) | (x > 32767))[0])
+        raise ValueError(f'sample {bad} is {int(x[bad])}: outside int16 [-32768, 32767]')
+    return x.astype(np.int16)
 
 
 # ---- filterbank definition -----------------------------------------------------------------------------------------
@@ -193,7 +226,8 @@ def window_plan(fn: str, segs, sr: int, seg_len: int = 144, seg_jump: int = 24) 
 class FrontEnd:
     """Filterbank + CMN of one sample rate on one device.  run() takes one or more recordings (dithered f64 signals with
     their segment lists), lays them end to end and computes all their features in one launch sequence; the features
-    stay on the device until get() / windows() copy them out."""
+    stay on the device until get() / windows() copy them out.  run_raw() takes the undithered integer samples instead
+    and draws the dither on the device, to the same bits."""
 
     def __init__(self, sr: int, device: int = 0):
         g = geometry(sr)
@@ -232,6 +266,37 @@ class FrontEnd:
         self.seg_rows, self.rows = seg_rows, rows
         return seg_rows
 
+    def run_raw(self, recordings, seed: int = DITHER_SEED, level=DITHER_LEVEL) -> list:
+        """recordings: [(int samples, [Segment])].  run() on dither(samples, seed, level) of every recording, with the
+        dither drawn on the device (one workgroup per recording follows numpy's MT19937 stream from the seed) and the
+        int16 samples uploaded instead of the f64 signal.  Returns what run() returns."""
+        mt19937_seed_state(seed)                 # (refuses what numpy refuses)
+        raws, recs, table, rows, off, seg_rows = [], [], [], 0, 0, []
+        for x, segs in recordings:
+            r = []
+            for s in segs:
+                table.append((off + s.start, s.n))
+                r.append(rows)
+                rows += s.nframes
+            seg_rows.append(r)
+            raws.append(raw_samples(x))
+            recs.append((off, len(raws[-1])))
+            off += len(raws[-1])
+        if not table:
+            self.seg_rows, self.rows = seg_rows, 0
+            return seg_rows
+        got = self.dev.run_raw(np.concatenate(raws), np.array(recs, dtype=np.int64).reshape(-1, 2),
+                               np.full(len(recs), int(seed), dtype=np.uint32), np.full(len(recs), float(level)),
+                               np.array(table, dtype=np.int64).reshape(-1, 2), CMN_LC, CMN_RC)
+        assert got == rows, (got, rows)
+        self.seg_rows, self.rows = seg_rows, rows
+        return seg_rows
+
+    def signal(self, first: int, n: int) -> np.ndarray:
+        """Samples [first, first + n) of the f64 signal of the last run, recordings end to end: what run() was given, or
+        what run_raw() dithered."""
+        return self.dev.signal(first, n)
+
     def _torch_empty(self, shape, dtype):
         import torch
         if not torch.cuda.is_available():
@@ -266,6 +331,10 @@ class FrontEnd:
     def times(self) -> dict:
         return self.dev.times()
 
+    def dither_time(self) -> float:
+        """Device ms of the dither kernel of the last run_raw."""
+        return self.dev.dither_time()
+
 
 _front_ends = {}
 
@@ -283,22 +352,36 @@ def prepare(samples, labs, sr: int, dither_signal: bool = True):
     return x, segments(labs, len(samples), sr)
 
 
-def features(recordings, sr: int, device: int = 0, dither_signal: bool = True, out: str = 'numpy') -> list:
-    """recordings: [(int samples, labels in samples)] of one sample rate.  Per recording, the list of its processed
-    segments' CMN features ([nframes][64] f32) as predict.py:175-177 computes them."""
-    fe = front_end(sr, device)
+def _run(fe, recordings, sr: int, dither_signal: bool, dither_on: str):
+    """One FrontEnd run over [(int samples, labels in samples)]: (first rows per recording, segments per recording)."""
+    if dither_on not in ('host', 'device'):
+        raise ValueError(f"dither_on must be 'host' or 'device', got {dither_on!r}")
+    if dither_on == 'device':
+        if not dither_signal:
+            raise ValueError("dither_on='device' draws the dither: it cannot go with dither_signal=False")
+        prep = [(x, segments(labs, len(x), sr)) for x, labs in recordings]
+        return fe.run_raw(prep), [segs for _, segs in prep]
     prep = [prepare(x, labs, sr, dither_signal) for x, labs in recordings]
-    seg_rows = fe.run(prep)
-    return [[fe.get(r0, s.nframes, out=out) for r0, s in zip(rows, segs)] for rows, (_, segs) in zip(seg_rows, prep)]
+    return fe.run(prep), [segs for _, segs in prep]
+
+
+def features(recordings, sr: int, device: int = 0, dither_signal: bool = True, out: str = 'numpy',
+             dither_on: str = 'host') -> list:
+    """recordings: [(int samples, labels in samples)] of one sample rate.  Per recording, the list of its processed
+    segments' CMN features ([nframes][64] f32) as predict.py:175-177 computes them.  dither_on: 'host' draws the dither with
+    numpy and uploads the f64 signal, 'device' uploads the int16 samples and draws it there; the features are the same."""
+    fe = front_end(sr, device)
+    seg_rows, seg_lists = _run(fe, recordings, sr, dither_signal, dither_on)
+    return [[fe.get(r0, s.nframes, out=out) for r0, s in zip(rows, segs)] for rows, segs in zip(seg_rows, seg_lists)]
 
 
 def windows(samples, labs, sr: int, fn: str, device: int = 0, seg_len: int = 144, seg_jump: int = 24,
-            dither_signal: bool = True, out: str = 'numpy'):
+            dither_signal: bool = True, out: str = 'numpy', dither_on: str = 'host'):
     """The windows of one recording: (plan, full windows [B][64][seg_len], {length: (plan indices, [n][64][length])}
-    for the tails), in the order of window_plan()."""
+    for the tails), in the order of window_plan().  dither_on as for features()."""
     fe = front_end(sr, device)
-    sig, segs = prepare(samples, labs, sr, dither_signal)
-    rows = fe.run([(sig, segs)])[0]
+    seg_rows, seg_lists = _run(fe, [(samples, labs)], sr, dither_signal, dither_on)
+    rows, segs = seg_rows[0], seg_lists[0]
     plan = window_plan(fn, segs, sr, seg_len, seg_jump)
     full = [i for i, w in enumerate(plan) if w.end - w.start == seg_len]
     full_t = fe.windows([rows[plan[i].seg] + plan[i].start for i in full], seg_len, out=out)

@@ -8,7 +8,8 @@ device.  Full windows go ``--batch-size`` at a time.  The other windows of a fil
 segment -- go through the ``--checkpoint`` network together, as ragged batches of at most ``--batch-size`` x ``--seg-len``
 frames (every embedding has the bits its window gives alone); a ``--model-file`` module takes them grouped by length.
 The ark file and the segments file are the ones predict.py writes, in its order.  The dither of the next file is drawn on the host while the
-device works on the current one.
+device works on the current one; with ``--dither device`` the device draws it (the same MT19937 stream, the same bits), the
+int16 samples go up instead of the f64 signal, and the host only reads the files ahead.
 
 Not supported: ``--backend onnx`` and ``--model/--weights`` (pass the ResNet101 weights with ``--checkpoint``).
 """
@@ -52,7 +53,12 @@ def parse_args(argv=None):
     p.add_argument('--backend', default='pytorch', choices=['pytorch', 'onnx'], help='only pytorch is supported')
     p.add_argument('--batch-size', type=int, default=128, help='full windows per model call')
     p.add_argument('--no-dither', action='store_true', help='skip the dither (the reference always adds it)')
+    p.add_argument('--dither', default='host', choices=['host', 'device'],
+                   help="where the dither is drawn: by numpy on the host (default), or by the front end's MT19937 kernel on "
+                        'the device, to the same bits')
     args = p.parse_args(argv)
+    if args.no_dither and args.dither == 'device':
+        p.error('--no-dither and --dither device exclude each other')
     if args.backend == 'onnx':
         p.error('--backend onnx is not supported: export the model to TorchScript and pass --model-file')
     if args.model is not None or (args.model_file is None and args.checkpoint is None):
@@ -78,8 +84,10 @@ def _ark_entry(key: str, vec: np.ndarray) -> bytes:
 
 
 def _load(args, fn):
-    samples, sr = fbank.read_wav(os.path.join(args.in_wav_dir, fn) + '.wav')
+    samples, sr = fbank.read_wav(os.path.join(args.in_wav_dir, fn) + '.wav', raw=args.dither == 'device')
     labs = fbank.read_lab(os.path.join(args.in_lab_dir, fn) + '.lab', sr)
+    if args.dither == 'device':                  # the samples as read: embed_file has the device dither them
+        return sr, samples, fbank.segments(labs, len(samples), sr)
     sig, segs = fbank.prepare(samples, labs, sr, dither_signal=not args.no_dither)
     return sr, sig, segs
 
@@ -103,8 +111,8 @@ def embed_file(embed, fe, fn, sig, segs, sr, args, embed_ragged=None):
     """(key, segments line, embedding) of every window of one file, in predict.py's order.  embed(fe, starts, length):
     the embeddings [n][E] (numpy) of the windows of `length` frames from feature rows `starts`.  embed_ragged(fe, starts,
     lengths), if given, takes the windows that are not full ones, of whatever lengths, in one call; without it they are
-    grouped by length."""
-    rows = fe.run([(sig, segs)])[0]
+    grouped by length.  sig is the dithered f64 signal, or with --dither device the integer samples."""
+    rows = (fe.run_raw if getattr(args, 'dither', 'host') == 'device' else fe.run)([(sig, segs)])[0]
     plan = fbank.window_plan(fn, segs, sr, args.seg_len, args.seg_jump)
     emb = [None] * len(plan)
     start = lambda i: rows[plan[i].seg] + plan[i].start
