@@ -193,6 +193,29 @@ int vbx_batch_run(vbx_batch* batch, int max_iters, double epsilon);
 int vbx_batch_get_result(vbx_batch* batch, int b, double* gamma, double* pi, double* Li, int li_cap,
                          int* n_iters, int* warned, double* alpha, double* invL);
 
+/* Reference labels of recording b (VBx.py:27 "ref", the diagnostic mode of VBx.py:107-110): ref [T] in [0, n_ref), n_ref <= 64,
+ * else VBX_ERR_INVALID.  Call it after the recording has been set and before a run; ref = NULL clears the labels.  While any
+ * recording of the batch has labels, every iteration of vbx_batch_run is followed on the device -- no synchronize, no
+ * download -- by the two score kernels (vbx_score.hpp), which leave in slot n_iters - 1 of the recording's history the
+ * confusion block C [2][n_ref][S] f64 of that iteration's responsibilities:
+ *   C[0][r][s] = sum_{t: ref_t = r} gamma[t][s]          C[1][r][s] = sum_{t: ref_t = r} -log(gamma[t][s] + 4.94e-324)
+ * i.e. -err_mx of VBx.py:139 with and without xentropy; the assignment of VBx.py:140 stays with the caller.  A label without
+ * frames keeps its all-zero row.  The sums are taken per recording in a fixed order: equal responsibilities give the same bits
+ * alone, in any batch and on any number of streams.  (The responsibilities themselves are those of the batch: the forward-
+ * backward algorithm follows the longest recording of a sub-batch, VBX_OPT_FB_ALGO, so a short recording gets another last bit
+ * of gamma -- and with it of its blocks -- alone than beside a long one unless the option pins the algorithm.)  gamma, pi and
+ * the ELBO do not depend on the labels, bit for bit.  Works for recordings set with _shared and _resident.  The labels belong to
+ * slot b (whose T is fixed) and stay until they are set again or cleared, also when another recording is uploaded into the
+ * slot: a caller that replaces the recording replaces its labels.  Setting or clearing labels discards the history of the
+ * recordings that share the stream (sub-batch) of b; the history is kept across runs otherwise.  A batch without labels launches and allocates
+ * nothing of this.  The launches are timed under VBX_K_POST. */
+int vbx_batch_set_reference(vbx_batch* batch, int b, const int32_t* ref, int32_t n_ref);
+/* The history of recording b: conf [n_iters][2][n_ref][S] f64, unpadded, at most cap_iters blocks of it (conf may be NULL);
+ * n_iters = blocks that are valid = iterations the recording has run (at most the batch's max_iters; the iteration a
+ * recording stopped at has its block, as VBx.py:105-125 appends before it tests).  Iterations that ran before the labels
+ * were set hold zeros.  VBX_ERR_STATE: the recording has no labels. */
+int vbx_batch_get_scores(vbx_batch* batch, int b, double* conf, int cap_iters, int* n_iters);
+
 /* Wait for the uploads enqueued under VBX_OPT_ASYNC_UPLOAD (vbx_batch_run does the same when it begins).  ABI 7. */
 int vbx_batch_sync_uploads(vbx_batch* batch);
 
@@ -297,6 +320,12 @@ int vbx_mstep(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, co
 /* per-frame log-likelihoods (VBx.py:97): X, Phi, alpha, invL -> log_p [T][S] (G included). */
 int vbx_loglik(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, const double* Phi,
                const double* alpha, const double* invL, double Fa, int precision, double* log_p);
+
+/* the confusion block of vbx_batch_set_reference for responsibilities on the host: gamma [T][S] f64 (rounded to f32 first for
+ * VBX_PREC_FP32, as a batch of that precision holds them), ref [T] in [0, n_ref), n_ref <= 64 -> conf [2][n_ref][S] f64.
+ * The same two kernels as in the iteration loop. */
+int vbx_score_posteriors(vbx_ctx* ctx, int64_t T, int32_t S, const double* gamma, const int32_t* ref, int32_t n_ref,
+                         int precision, double* conf);
 
 /* ---- the steps of the driver either side of VBx(), for all x-vectors of an archive at once -------------------------
  * vbhmm.py:125-129  xproj = l2_norm( l2_norm(x - mean1) lda - mean2 )       [n][Dl]       input of cos_similarity

@@ -11,6 +11,11 @@ initialisation) and replays the reference's observable host behaviour (the WARNI
 ``Li`` as a list of lists, DER bookkeeping when ``ref`` is given).  There is no CPU fallback:
 without the library or a gfx950 device the call raises ``vbx_amd._capi.VbxError``.
 
+``ref`` (the reference's diagnostic mode, VBx.py:107-110): the confusion block of every iteration's responsibilities
+against the labels is accumulated on the device inside the one run (vbx_batch_set_reference) and the rows ``[ELBO, DER,
+cross-entropy]`` are built from that history; only the Hungarian assignment runs on the host.  ``plot=True``, more than
+64 labels or ``VBX_AMD_REF_SCORING=host`` take the responsibilities to the host after every iteration instead.
+
 Two extra keyword-only arguments (the reference call sites never pass them):
   precision  'fp64' | 'fp32' | None.  None -> $VBX_AMD_PRECISION or "auto": float32 ``X``
              selects the fp32 device path, anything else the fp64 path (the reference always
@@ -26,7 +31,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ['VBx', 'forward_backward', 'DER']
+__all__ = ['VBx', 'forward_backward', 'DER', 'speaker_confusion', 'der_from_confusion']
 
 _EPS_TR = 1e-8          # VBx.py:158
 
@@ -65,10 +70,17 @@ def VBx(X, Phi, loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, maxIters=10,
     try:
         batch.set_recording(0, X, Phi, pi, gamma, loopProb, Fa, Fb, alpha0=alpha, invL0=invL)
         Li = []
+        labels = None if ref is None else _device_labels(ref, T, plot)
         if ref is None:
             batch.run(int(maxIters), epsilon)
             res = batch.result(0, want_model=return_model)
             Li = [[np.float64(e)] for e in res['Li']]
+        elif labels is not None:
+            # one run; every iteration's confusion block is left in the recording's history on the device
+            batch.set_reference(0, labels)
+            batch.run(int(maxIters), epsilon)
+            res = batch.result(0, want_model=return_model)
+            Li = score_rows(res['Li'], batch.scores(0), T)
         else:
             # DER / cross-entropy per iteration need gamma on the host every iteration (VBx.py:108-120)
             batch.set_option(_capi.OPT_CHECK_EVERY, 1)
@@ -92,6 +104,50 @@ def VBx(X, Phi, loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, maxIters=10,
     if return_model:
         out = out + (res['alpha'], res['invL'])
     return out
+
+
+def _device_labels(ref, T, plot=False):
+    """``ref`` as the int32 labels the device scores against, or None where VBx() keeps the per-iteration host path: a plot is
+    asked for, VBX_AMD_REF_SCORING=host, more than _capi.MAX_REF_LABELS labels, or labels the device path does not take."""
+    if plot or os.environ.get('VBX_AMD_REF_SCORING', 'device') == 'host':
+        return None
+    ref = np.asarray(ref)
+    if ref.shape != (T,) or ref.dtype.kind not in 'iu' or ref.min() < 0 or ref.max() >= _capi.MAX_REF_LABELS:
+        return None
+    return ref.astype(np.int32)
+
+
+def score_rows(elbo, conf, n_frames):
+    """The reference's ``Li`` rows [ELBO, DER, cross-entropy] (VBx.py:105-109) from an ELBO history and the confusion blocks."""
+    assert len(conf) == len(elbo), (len(conf), len(elbo))
+    return [[np.float64(e), der_from_confusion(c, n_frames), der_from_confusion(c, n_frames, xentropy=True)]
+            for e, c in zip(elbo, conf)]
+
+
+def speaker_confusion(q, ref, *, precision='fp64', device=None):
+    """Confusion block ``C[2][R][S]`` of posteriors ``q[T,S]`` against labels ``ref[T]``, R = max(ref) + 1, on the device:
+    ``C[0] = ref_mx^T q`` and ``C[1] = ref_mx^T -log(q + nextafter(0, 1))`` -- all DER() (VBx.py:134-143) needs of q
+    (der_from_confusion).  ``precision='fp32'`` rounds q to float32 first, as an fp32 batch holds it."""
+    q = np.asarray(q, dtype=np.float64)
+    ref = np.asarray(ref)
+    if q.ndim != 2 or ref.shape != (q.shape[0],):
+        raise ValueError(f'speaker_confusion: q [T][S] and ref [T] expected, got {q.shape} and {ref.shape}')
+    if ref.min() < 0 or ref.max() >= _capi.MAX_REF_LABELS:
+        raise ValueError(f'speaker_confusion: labels must lie in [0, {_capi.MAX_REF_LABELS})')
+    return _capi.default_context(device).score_posteriors(q, ref, precision=precision)
+
+
+def der_from_confusion(C, n_frames, xentropy=False):
+    """DER(q, ref) (VBx.py:134-143, ``expected=True``) from the confusion block of q and ref: the Hungarian assignment on
+    ``-C[0]`` (or on ``C[1]`` for the cross-entropy) and the reference's normalisation.  Host code."""
+    from scipy.optimize import linear_sum_assignment
+    C = np.asarray(C, dtype=np.float64)
+    per_pair = C[1] if xentropy else -C[0]
+    rows, cols = linear_sum_assignment(per_pair)
+    best = per_pair[rows, cols].sum()
+    if xentropy:
+        return best / float(n_frames)
+    return (n_frames + best) / float(n_frames)
 
 
 def _plot_iteration(gamma, ref, ii, maxIters):            # VBx.py:111-120

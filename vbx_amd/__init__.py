@@ -2,10 +2,11 @@
 
 Public surface (mirrors /root/reference/VBx/VBx.py):
     from vbx_amd import VBx, forward_backward, DER
-plus ``vbx_amd.batch.VBx_batch`` for many independent recordings per GPU / per node.
+plus ``speaker_confusion`` / ``der_from_confusion`` (what DER() needs of the posteriors, summed on the device) and
+``vbx_amd.batch.VBx_batch`` for many independent recordings per GPU / per node.
 The compute path is libvbx_hip.so (vbx_amd/csrc, C ABI in include/vbx_hip.h).
 """
-from .VBx import VBx, forward_backward, DER  # noqa: F401
+from .VBx import VBx, forward_backward, DER, speaker_confusion, der_from_confusion  # noqa: F401
 
-__all__ = ['VBx', 'forward_backward', 'DER']
+__all__ = ['VBx', 'forward_backward', 'DER', 'speaker_confusion', 'der_from_confusion']
 __version__ = '0.1.0'

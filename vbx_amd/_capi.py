@@ -25,6 +25,7 @@ STREAM_LOADS_NAMES = {'auto': STREAM_LOADS_AUTO, 'on': STREAM_LOADS_ON, 'off': S
 K_NAMES = ['prep', 'mstep_acc', 'mstep_fin', 'loglik', 'fb', 'fb_aux', 'post', 'iter_fin', 'chunk_loglik',
            'chunk_post']
 MAX_SPEAKERS = 16384
+MAX_REF_LABELS = 64          # labels a recording can be scored against on the device (vbx_batch_set_reference)
 
 ABI_SYMBOLS = [
     'vbx_abi_version', 'vbx_create', 'vbx_destroy', 'vbx_last_error', 'vbx_device_info',
@@ -46,6 +47,7 @@ ABI_SYMBOLS = [
     'vbx_fbank_windows_ragged', 'vbx_resnet_run_ragged', 'vbx_resnet_input_ragged',
     'vbx_resnet_conv_ragged', 'vbx_resnet_stem_ragged', 'vbx_resnet_pool_ragged',
     'vbx_fbank_run_raw', 'vbx_fbank_get_signal', 'vbx_fbank_dither_time',
+    'vbx_batch_set_reference', 'vbx_batch_get_scores', 'vbx_score_posteriors',
 ]
 
 
@@ -159,6 +161,9 @@ def load():
     lib.vbx_fbank_run_raw.argtypes = [vp, i64, vp, i32, vp, vp, vp, i32, vp, i32, i32, C.POINTER(i64)]
     lib.vbx_fbank_get_signal.argtypes = [vp, i64, i64, vp, C.c_int]
     lib.vbx_fbank_dither_time.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.vbx_batch_set_reference.argtypes = [vp, C.c_int, vp, i32]
+    lib.vbx_batch_get_scores.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
+    lib.vbx_score_posteriors.argtypes = [vp, i64, i32, vp, vp, i32, C.c_int, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -320,6 +325,20 @@ class Context:
         self.check(self._lib.vbx_loglik(self._h, T, S, D, _ptr(X), _ptr(Phi), _ptr(alpha), _ptr(invL), float(Fa),
                                         precision_code(precision), _ptr(out)), 'vbx_loglik')
         return out
+
+
+    def score_posteriors(self, gamma, ref, n_ref=None, precision='fp64'):
+        """Confusion block C[2][n_ref][S] of responsibilities ``gamma[T,S]`` against labels ``ref[T]`` (vbx_score_posteriors):
+        C[0] = ref_mx^T gamma, C[1] = ref_mx^T -log(gamma + nextafter(0, 1)); ``n_ref`` defaults to max(ref) + 1."""
+        gamma = _f64(gamma)
+        ref = np.ascontiguousarray(ref, dtype=np.int32)
+        T, S = gamma.shape
+        assert ref.shape == (T,)
+        n_ref = int(ref.max()) + 1 if n_ref is None else int(n_ref)
+        conf = np.empty((2, max(n_ref, 0), S))
+        self.check(self._lib.vbx_score_posteriors(self._h, T, S, _ptr(gamma), _ptr(ref), n_ref, precision_code(precision),
+                                                  _ptr(conf)), 'vbx_score_posteriors')
+        return conf
 
 
 class XVectors:
@@ -839,6 +858,7 @@ class Batch:
                                                      int(streams or 0), C.byref(h)), 'vbx_batch_create_streams')
         self._h = h
         self._held = []                                    # arrays an asynchronous upload still reads (set_async_upload)
+        self._n_ref = {}                                   # recording -> label count it is scored against (set_reference)
         self._async = False
         def choice(var, value, table):
             if value not in table:
@@ -936,6 +956,28 @@ class Batch:
         second = np.empty(self.T[b], dtype=np.int32)
         self.ctx.check(self._lib.vbx_batch_get_labels(self._h, int(b), _ptr(first), _ptr(second)), 'vbx_batch_get_labels')
         return first.astype(np.int64), (second.astype(np.int64) if self.S[b] > 1 else None)
+
+    def set_reference(self, b, ref, n_ref=None):
+        """Reference labels of recording b (after it has been set, before a run): every iteration of run() then leaves the
+        confusion block of its responsibilities in the recording's history (scores()).  ``ref=None`` clears them; ``n_ref``
+        defaults to max(ref) + 1 (at most MAX_REF_LABELS)."""
+        if ref is None:
+            self.ctx.check(self._lib.vbx_batch_set_reference(self._h, int(b), None, 0), 'vbx_batch_set_reference')
+            self._n_ref.pop(int(b), None)
+            return
+        ref = np.ascontiguousarray(ref, dtype=np.int32)
+        assert ref.shape == (self.T[b],)
+        n_ref = int(ref.max()) + 1 if n_ref is None else int(n_ref)
+        self.ctx.check(self._lib.vbx_batch_set_reference(self._h, int(b), _ptr(ref), n_ref), 'vbx_batch_set_reference')
+        self._n_ref[int(b)] = n_ref
+
+    def scores(self, b):
+        """The confusion blocks of recording b, one per iteration it has run: [n_iters][2][n_ref][S] (vbx_batch_get_scores)."""
+        n_ref = self._n_ref.get(int(b), 1)                 # (no labels: the library says so)
+        conf = np.zeros((max(self.max_iters, 1), 2, n_ref, self.S[b]))
+        n = C.c_int()
+        self.ctx.check(self._lib.vbx_batch_get_scores(self._h, int(b), _ptr(conf), len(conf), C.byref(n)), 'vbx_batch_get_scores')
+        return conf[:min(n.value, len(conf))].copy()
 
     def n_iters(self, b):
         n, w = C.c_int(), C.c_int()

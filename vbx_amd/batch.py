@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+from ._capi import MAX_REF_LABELS      # labels a recording of a batch can be scored against (vbx_batch_set_reference)
+
 __all__ = ['shard_recordings', 'VBx_batch', 'VBx_sweep', 'VBx_batch_distributed']
 
 
@@ -34,13 +36,28 @@ def shard_recordings(costs, world_size: int):
 # VBx() keyword arguments that mean something per recording, and the ones that only exist per batch / per call: the
 # latter are accepted in a recording's dict (a dict built for VBx(**kw) can be passed as it is) and ignored with a warning
 # when they differ from what the batch runs with
-PER_RECORDING = ('loopProb', 'Fa', 'Fb', 'pi', 'gamma', 'alphaQInit', 'alpha', 'invL')
-PER_BATCH = ('maxIters', 'epsilon', 'return_model', 'ref', 'plot', 'precision', 'device')
+PER_RECORDING = ('loopProb', 'Fa', 'Fb', 'pi', 'gamma', 'alphaQInit', 'alpha', 'invL', 'ref')
+PER_BATCH = ('maxIters', 'epsilon', 'return_model', 'plot', 'precision', 'device')
+
+
+def _check_ref(ref, T):
+    """Reference labels of a recording of T frames as int32, or a ValueError that says what the batch path does not take."""
+    ref = np.asarray(ref)
+    if ref.shape != (T,):
+        raise ValueError(f'VBx_batch: ref has shape {ref.shape}, the recording has {T} frames')
+    if ref.dtype.kind not in 'iu':
+        raise ValueError(f'VBx_batch: ref must hold integer labels, got {ref.dtype}')
+    if T and ref.min() < 0:
+        raise ValueError('VBx_batch: ref holds negative labels')
+    if T and ref.max() >= MAX_REF_LABELS:
+        raise ValueError(f'VBx_batch: ref has {int(ref.max()) + 1} labels; a batch scores against at most {MAX_REF_LABELS} '
+                         '(VBx() takes more, on the host)')
+    return ref.astype(np.int32)
 
 
 def _normalise(rec, defaults):
     """rec: dict with X, Phi and optional VBx() keyword arguments -> full argument dict."""
-    kw = dict(loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, alphaQInit=1.0, alpha=None, invL=None)
+    kw = dict(loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, alphaQInit=1.0, alpha=None, invL=None, ref=None)
     for where in (defaults, rec):
         bad = set(where) - set(PER_RECORDING) - set(PER_BATCH) - {'X', 'Phi'}
         if bad:            # a typo would otherwise be ignored silently
@@ -63,8 +80,9 @@ def _normalise(rec, defaults):
         gamma = np.random.gamma(kw['alphaQInit'], size=(X.shape[0], len(pi)))
         gamma = gamma / gamma.sum(1, keepdims=True)
     assert gamma.shape[1] == len(pi) and gamma.shape[0] == X.shape[0]     # VBx.py:85
+    ref = None if kw['ref'] is None else _check_ref(kw['ref'], X.shape[0])
     return dict(X=X, Phi=np.asarray(rec['Phi']), pi=pi, gamma=gamma, loopProb=kw['loopProb'], Fa=kw['Fa'],
-                Fb=kw['Fb'], alpha=kw['alpha'], invL=kw['invL'])
+                Fb=kw['Fb'], alpha=kw['alpha'], invL=kw['invL'], ref=ref)
 
 
 def _shape_of(rec, defaults):
@@ -89,6 +107,8 @@ def _shape_of(rec, defaults):
         raise ValueError(f'VBx_batch: Phi has shape {np.shape(rec["Phi"])}, X has {xs[1]} dimensions')
     if kw.get('gamma') is not None:
         assert np.shape(kw['gamma']) == (T, S), (np.shape(kw['gamma']), (T, S))     # VBx.py:85
+    if kw.get('ref') is not None and np.shape(kw['ref']) != (T,):
+        raise ValueError(f'VBx_batch: ref has shape {np.shape(kw["ref"])}, the recording has {T} frames')
     for name in ('alpha', 'invL'):
         if kw.get(name) is not None and np.shape(kw[name]) != (S, xs[1]):
             raise ValueError(f'VBx_batch: {name} has shape {np.shape(kw[name])}, expected {(S, xs[1])}')
@@ -133,6 +153,8 @@ def _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results, gates=N
                 it = items[k]
                 batch.set_recording(j, it['X'], it['Phi'], it['pi'], it['gamma'], it['loopProb'], it['Fa'],
                                     it['Fb'], alpha0=it['alpha'], invL0=it['invL'])
+                if it.get('ref') is not None:
+                    batch.set_reference(j, it['ref'])
         by_stream = {}
         for j, k in enumerate(idx):
             by_stream.setdefault(batch.stream_of(j), []).append((j, k))
@@ -151,7 +173,9 @@ def _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results, gates=N
         with run:
             batch.run(maxIters, epsilon)
         with fetch:
-            for k, res in zip(idx, batch.results()):
+            for j, (k, res) in enumerate(zip(idx, batch.results())):
+                if items[k].get('ref') is not None:       # the confusion block of every iteration (_as_tuple: DER, cross-entropy)
+                    res['conf'] = batch.scores(j)
                 results[k] = res
     finally:
         batch.close()
@@ -208,8 +232,11 @@ def VBx_batch(recordings, maxIters=10, epsilon=1e-4, precision=None, device=None
     Each recording is a dict with ``X`` and ``Phi`` plus the per-recording keyword arguments of VBx(): ``loopProb``,
     ``Fa``, ``Fb``, ``pi``, ``gamma``, ``alphaQInit``, ``alpha``, ``invL``; ``defaults`` supplies shared values of the
     same.  ``maxIters``, ``epsilon``, ``return_model``, ``precision`` and ``device`` apply to the whole batch: given in a
-    recording's dict they are ignored with a warning (``ref`` / ``plot`` need the responsibilities on the host every
-    iteration and are a VBx() feature only); any other key is a TypeError.  ``precision`` follows VBx(): fp64 kernels
+    recording's dict they are ignored with a warning (``plot`` needs the responsibilities on the host every
+    iteration and is a VBx() feature only); any other key is a TypeError.  ``ref`` (reference labels, per recording): that
+    recording's ``Li`` rows are ``[ELBO, DER, cross-entropy]`` as VBx(ref=...) returns them, scored on the device inside the
+    one run (vbx_batch_set_reference); the recordings without labels keep one-column rows.  ValueError for labels that are
+    not T non-negative integers below 64.  ``precision`` follows VBx(): fp64 kernels
     unless every X is float32 (or VBX_AMD_PRECISION / the argument says otherwise) -- NB before round 2 the default was
     fp32 whatever the input type -- so the numerics and iteration counts are those of one VBx() call per recording.  Returns a list of ``(gamma, pi, Li[,
     alpha, invL])`` tuples in input order (same types as the reference returns, VBx.py:126)."""
@@ -252,22 +279,32 @@ def run_sweep_hip(X, Phi, items, maxIters, epsilon, precision=None, device=None)
             else:
                 batch.set_recording_shared(j, 0, it['pi'], it['gamma'], it['loopProb'], it['Fa'], it['Fb'],
                                            alpha0=it['alpha'], invL0=it['invL'])
+            if it.get('ref') is not None:
+                batch.set_reference(j, it['ref'])
         batch.run(maxIters, epsilon)
-        return [batch.result(j) for j in range(len(items))]
+        out = [batch.result(j) for j in range(len(items))]
+        for j, it in enumerate(items):
+            if it.get('ref') is not None:
+                out[j]['conf'] = batch.scores(j)
+        return out
     finally:
         batch.close()
 
 
-def VBx_sweep(X, Phi, points, maxIters=10, epsilon=1e-4, precision=None, device=None, return_model=False, **defaults):
+def VBx_sweep(X, Phi, points, maxIters=10, epsilon=1e-4, precision=None, device=None, return_model=False, ref=None,
+              **defaults):
     """``[VBx(X, Phi, **defaults, **p, maxIters=..., epsilon=...) for p in points]`` -- a hyper-parameter sweep over ONE
     recording, the grids of the reference's recipes (DIHARD2_run.sh:42-47, AMI_run.sh:44-49, CALLHOME_run.sh:42-47:
     Fa x Fb x loopP around one x-vector sequence) -- as one batch on one GPU with ONE rho = X * sqrt(Phi) (VBx.py:89) in
     HBM: the per-chunk kernels run the chunks of all points that read the same rows of it side by side, so HBM delivers
     the x-vectors once per kernel and not once per point.  ``points``: dicts of the per-recording keyword arguments of
     VBx() (``Fa``, ``Fb``, ``loopProb``, ``pi``, ``gamma``, ``alphaQInit``, ``alpha``, ``invL``).  ``gamma=None`` draws the
-    initialisation from the global RNG per point, in list order, exactly as successive VBx() calls would.  Returns the
-    list of ``(gamma, pi, Li[, alpha, invL])`` tuples."""
+    initialisation from the global RNG per point, in list order, exactly as successive VBx() calls would.  ``ref``: reference
+    labels of the recording, one array for all points -- every point's ``Li`` rows are then ``[ELBO, DER, cross-entropy]``
+    (what a grid is scored by), accumulated on the device.  Returns the list of ``(gamma, pi, Li[, alpha, invL])`` tuples."""
     X = np.asarray(X)
+    if ref is not None:
+        defaults = dict(defaults, ref=ref)
     items = [_normalise(dict(p, X=X, Phi=Phi), defaults) for p in points]
     if maxIters <= 0:
         return [(it['gamma'], it['pi'], []) + ((it['alpha'], it['invL']) if return_model else ()) for it in items]
@@ -280,7 +317,12 @@ def VBx_sweep(X, Phi, points, maxIters=10, epsilon=1e-4, precision=None, device=
 def _as_tuple(res, return_model, warn=True):
     if res['warned'] and warn:
         print('WARNING: Value of auxiliary function has decreased!')       # VBx.py:123-124
-    out = (res['gamma'], res['pi'], [[np.float64(e)] for e in res['Li']])
+    if res.get('conf') is not None:                       # a recording with reference labels: [ELBO, DER, cross-entropy] rows
+        from .VBx import score_rows
+        Li = score_rows(res['Li'], res['conf'], res['gamma'].shape[0])
+    else:
+        Li = [[np.float64(e)] for e in res['Li']]
+    out = (res['gamma'], res['pi'], Li)
     if return_model:
         out = out + (res['alpha'], res['invL'])
     return out

@@ -71,7 +71,8 @@ static int leaf_destroy(vbx_batch* b) {
                     b->d_opexp, b->d_tllpart, b->d_sfw, b->d_dump, b->d_sop, b->d_sopexp, b->d_sup_rec, b->d_sup_idx,
                     b->d_sop2, b->d_sopexp2, b->d_sup2_rec, b->d_sup2_idx,
                     b->d_gamma0, b->d_pi_prev, b->d_oph, b->d_ophexp, b->d_cop, b->d_lppow, b->d_tile_order,
-                    b->d_rho_a, b->d_rho_b, b->d_alpha_frag, b->d_rho_e, b->d_rho_amax, b->d_alpha_e};
+                    b->d_rho_a, b->d_rho_b, b->d_alpha_frag, b->d_rho_e, b->d_rho_amax, b->d_alpha_e,
+                    b->d_score_lab, b->d_score_rec, b->d_score_items, b->d_score_part, b->d_score_hist};
     (void)hipStreamSynchronize(b->ctx->stream);               // nothing of this batch may still be running when its
     for (void* p : ptrs) ctx_free(b->ctx, p);                 // blocks go back to the spare list
     if (b->d_fetch) ctx_free(b->ctx, b->d_fetch);
@@ -740,6 +741,113 @@ static int prepare_split(vbx_batch* b) {
     return VBX_OK;
 }
 
+// Reference labels (vbx_batch_set_reference): the tables of the score kernels (vbx_score.hpp).  The partial blocks and the history
+// are laid out per recording with that recording's own label count, so they are (re)built -- and the history zeroed -- by the
+// first run after any recording's labels have changed; the label rows themselves are allocated when the first labels are set.
+static int score_prepare(vbx_batch* b) {
+    if (!b->score_dirty) return VBX_OK;
+    vbx_ctx* ctx = b->ctx;
+    std::vector<int2> items;
+    b->h_score_rec.assign(b->n_rec, ScoreRec{0, 0, 0, 0});
+    long long part = 0, hist = 0;
+    b->score_rmax = 0;
+    for (int i = 0; i < b->n_rec; ++i) {
+        ScoreRec& sr = b->h_score_rec[i];
+        sr.n_ref = b->ref_n[i];
+        if (!sr.n_ref) continue;
+        sr.ngroups = (b->recs[i].ntiles + kScoreGroupTiles - 1) / kScoreGroupTiles;
+        sr.part_off = part;
+        sr.hist_off = hist;
+        const long long block = 2ll * sr.n_ref * b->Sp;
+        part += block * sr.ngroups;
+        hist += block * std::max(b->max_iters, 1);
+        for (int g = 0; g < sr.ngroups; ++g) items.push_back(make_int2(i, g));
+        b->score_rmax = std::max(b->score_rmax, sr.n_ref);
+    }
+    for (void* p : {(void*)b->d_score_items, (void*)b->d_score_part, (void*)b->d_score_hist}) ctx_free(ctx, p);
+    b->d_score_items = nullptr; b->d_score_part = nullptr; b->d_score_hist = nullptr;
+    b->score_items = (int)items.size();
+    int rc = b->d_score_rec ? VBX_OK : dmalloc(ctx, &b->d_score_rec, (size_t)b->n_rec);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &b->d_score_items, items.size());
+    if (rc == VBX_OK) rc = dmalloc(ctx, &b->d_score_part, (size_t)part);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &b->d_score_hist, (size_t)hist);
+    if (rc != VBX_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(b->d_score_rec, b->h_score_rec.data(), sizeof(ScoreRec) * b->n_rec, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b->d_score_items, items.data(), sizeof(int2) * items.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(b->d_score_hist, 0, sizeof(double) * (size_t)hist, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    b->score_dirty = false;
+    return VBX_OK;
+}
+
+extern "C++" {
+namespace {
+// the two score kernels on `st`: every item's partial block, then every labelled recording's partials into one history slot
+template <typename R>
+void score_launch(hipStream_t st, const R* gamma, int Sp, int n_rec, int max_iters, const RecDesc* recs, const ScoreRec* srec,
+                  const int* lab, const int2* items, int n_items, int rmax, const RecState* state, int slot, double* part,
+                  double* hist) {
+    if (n_items <= 0) return;
+    hipLaunchKernelGGL((score_acc_kernel<R>), dim3(n_items, (Sp + kScoreCols - 1) / kScoreCols), dim3(256), 0, st, gamma, Sp, recs,
+                       srec, lab, items, part);
+    const long long block = 2ll * rmax * Sp;
+    hipLaunchKernelGGL(score_fin_kernel, dim3(n_rec, (unsigned)((block + 255) / 256)), dim3(256), 0, st, Sp, max_iters, srec, state,
+                       slot, (const double*)part, hist);
+}
+}  // namespace
+}  // extern "C++"
+
+static int leaf_set_reference(vbx_batch* b, int rec, const int32_t* ref, int32_t n_ref) {
+    if (!b) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = b->ctx;
+    if (rec < 0 || rec >= b->n_rec) FAIL(ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
+    if (b->ref_n.empty()) b->ref_n.assign(b->n_rec, 0);
+    if (ref) {
+        if (!b->is_set[rec]) FAIL(ctx, VBX_ERR_STATE, "vbx_batch_set_reference: recording %d has not been set", rec);
+        if (n_ref < 1 || n_ref > kScoreMaxRef)
+            FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_reference: n_ref=%d outside [1, %d]", n_ref, kScoreMaxRef);
+        const RecDesc& rd = b->recs[rec];
+        for (int t = 0; t < rd.T; ++t)
+            if (ref[t] < 0 || ref[t] >= n_ref) FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_reference: label %d of frame %d outside [0, %d)", ref[t], t, n_ref);
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        if (!b->d_score_lab)
+            if (int rc = dmalloc(ctx, &b->d_score_lab, (size_t)b->sum_T); rc != VBX_OK) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(b->d_score_lab + rd.row0, ref, sizeof(int32_t) * (size_t)rd.T, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // (the caller's array is free when this returns)
+        b->ref_n[rec] = n_ref;
+    } else {
+        b->ref_n[rec] = 0;
+    }
+    b->score_any = false;
+    for (int n : b->ref_n) b->score_any = b->score_any || n > 0;
+    b->score_dirty = true;
+    return VBX_OK;
+}
+
+static int fetch_mirrors(vbx_batch* b);
+
+static int leaf_get_scores(vbx_batch* b, int rec, double* conf, int cap_iters, int* n_iters) {
+    if (!b) return VBX_ERR_INVALID;
+    vbx_ctx* ctx = b->ctx;
+    if (rec < 0 || rec >= b->n_rec) FAIL(ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
+    if (b->ref_n.empty() || !b->ref_n[rec]) FAIL(ctx, VBX_ERR_STATE, "vbx_batch_get_scores: recording %d has no reference labels", rec);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_mirrors(b); rc != VBX_OK) return rc;
+    // (labels changed since the last run: its history went with the old layout)
+    int n = (b->score_dirty || !b->d_score_hist) ? 0 : std::min(b->h_state[rec].n_iters, b->max_iters);
+    if (n_iters) *n_iters = n;
+    n = std::min(n, cap_iters);
+    if (!conf || n <= 0) return VBX_OK;
+    const ScoreRec& sr = b->h_score_rec[rec];
+    const int S = b->recs[rec].S, Sp = b->Sp;
+    const size_t rows = (size_t)n * 2 * sr.n_ref;
+    std::vector<double> padded(rows * Sp);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(padded.data(), b->d_score_hist + sr.hist_off, sizeof(double) * padded.size(), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) std::memcpy(conf + r * S, padded.data() + r * Sp, sizeof(double) * S);
+    return VBX_OK;
+}
+
 // One run = begin (checks, tables, start event) -> max_iters x { launch one iteration; now and then look at the
 // convergence flags } -> end (stop event, wait, timings).  Split so that a stream group can interleave its kids.
 static int run_begin(vbx_batch* b, int max_iters) {
@@ -759,6 +867,7 @@ static int run_begin(vbx_batch* b, int max_iters) {
     std::fill(b->k_launches, b->k_launches + VBX_K_COUNT, 0);
     b->ev_used = 0;
     b->iters_launched = 0;
+    if (b->score_any && (rc = score_prepare(b)) != VBX_OK) return rc;
     HIPCHK(ctx, hipEventRecord(b->ev_start, ctx->stream));
     // (inside the timed run and under VBX_K_PREP: the first run after an upload pays two more passes over rho in split mode)
     return prepare_split(b);
@@ -810,8 +919,9 @@ template <typename R> void launch_gamma_replay(vbx_batch* b) {
 }  // namespace
 }  // extern "C++"
 
-static int run_end(vbx_batch* b) {
-    vbx_ctx* ctx = b->ctx;
+// what closes the iterations launched so far, without waiting for it: the finishing role of the last one, then gamma where the
+// fused kernels kept it on the chip
+static void run_close_launches(vbx_batch* b) {
     if (b->fin_pending) {                     // the last iteration launched: ELBO, pi, history, convergence
         if (b->precision == VBX_PREC_FP64) launch_fin<double>(b, b->run_epsilon, 2);
         else launch_fin<float>(b, b->run_epsilon, 2);
@@ -822,6 +932,26 @@ static int run_end(vbx_batch* b) {
         else launch_gamma_replay<float>(b);
         b->gamma_stale = false;
     }
+}
+
+// Reference labels: every iteration is closed as a run of one iteration would close it (the sequence run(1) repeated goes
+// through, bit for bit that of one long run: tests/test_gpu_parity.py) and its gamma scored into slot n_iters - 1 -- no
+// synchronise, no download; the next iteration starts with fin mode 1.
+static void run_score(vbx_batch* b) {
+    run_close_launches(b);
+    LaunchScope ls(b, VBX_K_POST);
+    const RecState* st = b->d_state + (size_t)b->state_cur * b->n_rec;
+    if (b->precision == VBX_PREC_FP64)
+        score_launch<double>(b->ctx->stream, (const double*)b->d_gamma, b->Sp, b->n_rec, b->max_iters, b->d_recs, b->d_score_rec, b->d_score_lab,
+                             b->d_score_items, b->score_items, b->score_rmax, st, 0, b->d_score_part, b->d_score_hist);
+    else
+        score_launch<float>(b->ctx->stream, (const float*)b->d_gamma, b->Sp, b->n_rec, b->max_iters, b->d_recs, b->d_score_rec, b->d_score_lab,
+                            b->d_score_items, b->score_items, b->score_rmax, st, 0, b->d_score_part, b->d_score_hist);
+}
+
+static int run_end(vbx_batch* b) {
+    vbx_ctx* ctx = b->ctx;
+    run_close_launches(b);
     HIPCHK(ctx, hipEventRecord(b->ev_stop, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipGetLastError());
@@ -842,6 +972,7 @@ static int leaf_run(vbx_batch* b, int max_iters, double epsilon) {
     const bool can_stop = epsilon > -1e299;
     for (int it = 0; it < max_iters; ++it) {
         run_launch(b, epsilon);
+        if (b->score_any) run_score(b);
         if (can_stop && ((it + 1) % b->check_every == 0) && it + 1 < max_iters) {
             bool all_done = false;
             if ((rc = run_all_done(b, &all_done)) != VBX_OK) return rc;

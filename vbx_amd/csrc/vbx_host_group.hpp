@@ -352,6 +352,22 @@ int vbx_batch_get_result(vbx_batch* b, int rec, double* gamma, double* pi, doubl
     return kid_fail(b, k, leaf_get_result(b->kids[k], b->local_of[rec], gamma, pi, Li, li_cap, n_iters, warned, alpha, invL));
 }
 
+int vbx_batch_set_reference(vbx_batch* b, int rec, const int32_t* ref, int32_t n_ref) {
+    if (!b) return VBX_ERR_INVALID;
+    if (b->kids.empty()) return leaf_set_reference(b, rec, ref, n_ref);
+    if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
+    const int k = b->kid_of[rec];                             // (labels, partials and history live in the arena of its sub-batch)
+    return kid_fail(b, k, leaf_set_reference(b->kids[k], b->local_of[rec], ref, n_ref));
+}
+
+int vbx_batch_get_scores(vbx_batch* b, int rec, double* conf, int cap_iters, int* n_iters) {
+    if (!b) return VBX_ERR_INVALID;
+    if (b->kids.empty()) return leaf_get_scores(b, rec, conf, cap_iters, n_iters);
+    if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
+    const int k = b->kid_of[rec];
+    return kid_fail(b, k, leaf_get_scores(b->kids[k], b->local_of[rec], conf, cap_iters, n_iters));
+}
+
 int vbx_batch_sync_uploads(vbx_batch* b) {
     if (!b) return VBX_ERR_INVALID;
     if (b->kids.empty()) return sync_uploads(b);

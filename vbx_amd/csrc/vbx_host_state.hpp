@@ -198,6 +198,18 @@ struct vbx_batch {
     int *d_sopexp2 = nullptr, *d_sup2_rec = nullptr, *d_sup2_idx = nullptr;
     void* d_xstage = nullptr;
     size_t xstage_bytes = 0;
+    // reference labels (vbx_batch_set_reference, vbx_score.hpp): nothing here is allocated, and no kernel launched, until a
+    // recording of the batch has labels
+    std::vector<int> ref_n;                       // recording -> labels it is scored against (0: none); empty until the first set
+    bool score_any = false;                       // a recording has labels: every iteration of a run is scored
+    bool score_dirty = false;                     // labels have changed since the tables below were built (score_prepare)
+    int* d_score_lab = nullptr;                   // [sum_T] label of every frame row (rows of unlabelled recordings: never read)
+    vbx::ScoreRec* d_score_rec = nullptr;         // [n_rec]
+    int2* d_score_items = nullptr;                // [score_items] {recording, group of kScoreGroupTiles tiles}
+    double* d_score_part = nullptr;               // per recording [groups][2][n_ref][Sp]
+    double* d_score_hist = nullptr;               // per recording [max_iters][2][n_ref][Sp]
+    std::vector<vbx::ScoreRec> h_score_rec;
+    int score_items = 0, score_rmax = 0;
     // timing
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     double last_ms = 0.0;

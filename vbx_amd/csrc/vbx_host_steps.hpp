@@ -301,4 +301,74 @@ int vbx_loglik(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, c
     return rc;
 }
 
+extern "C++" {
+namespace {
+template <typename R>
+int score_posteriors_impl(vbx_ctx* ctx, int64_t T, int32_t S, const double* gamma, const int32_t* ref, int32_t n_ref, double* conf) {
+    int Sp = 16;
+    while (Sp < S) Sp *= 2;
+    RecDesc rd;
+    std::memset(&rd, 0, sizeof rd);
+    rd.T = (int)T;
+    rd.S = S;
+    rd.ntiles = (rd.T + kTileFrames - 1) / kTileFrames;
+    const ScoreRec sr{0, 0, n_ref, (rd.ntiles + kScoreGroupTiles - 1) / kScoreGroupTiles};
+    std::vector<int2> items;
+    for (int g = 0; g < sr.ngroups; ++g) items.push_back(make_int2(0, g));
+    std::vector<R> gp;
+    pack_matrix<R, double>(gp, gamma, T, S, Sp, (R)0);        // (fp32: rounded here, as a batch holds it)
+    const size_t block = (size_t)2 * n_ref * Sp;
+    R* d_gamma = nullptr;
+    RecDesc* d_rd = nullptr;
+    ScoreRec* d_sr = nullptr;
+    int* d_lab = nullptr;
+    int2* d_items = nullptr;
+    double *d_part = nullptr, *d_hist = nullptr;
+    int rc = dmalloc(ctx, &d_gamma, gp.size());
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rd, 1);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_sr, 1);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_lab, (size_t)T);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_items, items.size());
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, block * sr.ngroups);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_hist, block);
+    std::vector<double> padded(block);
+    hipError_t e = hipSuccess;
+    if (rc == VBX_OK) {
+        hipStream_t st = ctx->stream;
+        e = hipMemcpyAsync(d_gamma, gp.data(), sizeof(R) * gp.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rd, &rd, sizeof rd, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_sr, &sr, sizeof sr, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_lab, ref, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_items, items.data(), sizeof(int2) * items.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            score_launch<R>(st, d_gamma, Sp, 1, 1, d_rd, d_sr, d_lab, d_items, (int)items.size(), n_ref, nullptr, 0, d_part, d_hist);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(padded.data(), d_hist, sizeof(double) * block, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    for (void* p : {(void*)d_gamma, (void*)d_rd, (void*)d_sr, (void*)d_lab, (void*)d_items, (void*)d_part, (void*)d_hist}) ctx_free(ctx, p);
+    if (rc != VBX_OK) return rc;
+    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "score kernels failed: %s", hipGetErrorString(e));
+    for (size_t r = 0; r < (size_t)2 * n_ref; ++r) std::memcpy(conf + r * S, padded.data() + r * Sp, sizeof(double) * S);
+    return VBX_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int vbx_score_posteriors(vbx_ctx* ctx, int64_t T, int32_t S, const double* gamma, const int32_t* ref, int32_t n_ref, int precision,
+                         double* conf) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!gamma || !ref || !conf) FAIL(ctx, VBX_ERR_INVALID, "vbx_score_posteriors: NULL argument");
+    if (T <= 0 || T > 0x7fffffffLL / 512 || S <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_score_posteriors: T=%lld, S=%d out of range", (long long)T, S);
+    if (S > VBX_MAX_SPEAKERS) FAIL(ctx, VBX_ERR_UNSUPPORTED, "S=%d exceeds VBX_MAX_SPEAKERS=%d", S, VBX_MAX_SPEAKERS);
+    if (n_ref < 1 || n_ref > kScoreMaxRef) FAIL(ctx, VBX_ERR_INVALID, "vbx_score_posteriors: n_ref=%d outside [1, %d]", n_ref, kScoreMaxRef);
+    if (precision != VBX_PREC_FP32 && precision != VBX_PREC_FP64) FAIL(ctx, VBX_ERR_INVALID, "unknown precision %d", precision);
+    for (int64_t t = 0; t < T; ++t)
+        if (ref[t] < 0 || ref[t] >= n_ref) FAIL(ctx, VBX_ERR_INVALID, "vbx_score_posteriors: label %d of frame %lld outside [0, %d)", ref[t], (long long)t, n_ref);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return precision == VBX_PREC_FP64 ? score_posteriors_impl<double>(ctx, T, S, gamma, ref, n_ref, conf)
+                                      : score_posteriors_impl<float>(ctx, T, S, gamma, ref, n_ref, conf);
+}
+
 }  // extern "C"

@@ -732,7 +732,8 @@ __global__ __launch_bounds__(256) void post_kernel(BatchView<R> bt) {
     constexpr int W = SP < 64 ? SP : 64;
     constexpr int FPW = 64 / W;        // frames per wavefront pass
     constexpr int NREG = SP / W;
-    __shared__ double ent_lds[SP];
+    constexpr int NCON = 256 / W;      // threads that hold a share of one state's "entered" statistic: (wavefront, frame slot)
+    __shared__ double ent_lds[NCON][SP];
     const int tile = blockIdx.x;
     const int rec = bt.tile_rec[tile];
     if (bt.state[rec].done) return;
@@ -745,8 +746,6 @@ __global__ __launch_bounds__(256) void post_kernel(BatchView<R> bt) {
     const R* __restrict__ A = bt.ahat + rd.row0 * SP;
     const R* __restrict__ Bh = bt.bhat + rd.row0 * SP;
     R* __restrict__ G = bt.gamma + rd.row0 * SP;
-    for (int j = threadIdx.x; j < SP; j += 256) ent_lds[j] = 0.0;
-    __syncthreads();
     R c[NREG];
     double ent[NREG];
 #pragma unroll
@@ -795,10 +794,17 @@ __global__ __launch_bounds__(256) void post_kernel(BatchView<R> bt) {
             }
         }
     }
+    // the shares of a state in a fixed order (LDS atomics took them in whatever order the wavefronts arrived: the priors, and
+    // with them gamma, of two runs of one recording differed in the last bits on this path)
 #pragma unroll
-    for (int r = 0; r < NREG; ++r) atomicAdd(&ent_lds[jl + W * r], ent[r]);
+    for (int r = 0; r < NREG; ++r) ent_lds[wave * FPW + sub][jl + W * r] = ent[r];
     __syncthreads();
-    for (int j = threadIdx.x; j < SP; j += 256) bt.epart[(long long)tile * SP + j] = ent_lds[j];
+    for (int j = threadIdx.x; j < SP; j += 256) {
+        double e = 0.0;
+#pragma unroll
+        for (int q = 0; q < NCON; ++q) e += ent_lds[q][j];
+        bt.epart[(long long)tile * SP + j] = e;
+    }
     if (bt.tllpart) {      // chunked scan: this tile's share of the total log-likelihood (VBx.py:173)
         __shared__ double tl_lds[16];
         double part = 0.0;
