@@ -10,6 +10,7 @@
 # Summaries land in gpurun_out/prof_<round>_*/ and are copied into profiles/<round>_* on the box and into
 # gpurun_out/profiles_<round>/ (what comes back: copy that directory's files into profiles/; the files bench.py reads carry the
 # hash of the kernel sources: a later change of the kernels retires them).
+set -o pipefail
 r=$1; shift
 want="$*"
 export SQ2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_BUSY_CYCLES"
@@ -17,7 +18,8 @@ export SQ_EXTRA="SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_INSTS_LDS"
 run() {  # tag, NO_BENCH flag, args...
   tag=$1; nb=$2; shift 2
   if [ -n "$want" ] && ! echo " $want " | grep -q " $tag "; then return; fi
-  NO_BENCH=$nb bash tools/profile_bench.sh ${r}_$tag "$@" > /dev/null 2>&1
+  # (a workload whose pass failed -- profile_bench.sh hands its status on -- is the last one: nothing more runs on that GPU)
+  NO_BENCH=$nb bash tools/profile_bench.sh ${r}_$tag "$@" > /dev/null 2>&1 || { rc=$?; echo "== $tag: FAILED with status $rc, stopping"; exit $rc; }
   d=gpurun_out/prof_${r}_$tag
   mkdir -p gpurun_out/profiles_$r
   for f in kernel_stats.txt pmc_traffic.json sq_counters.txt sq2_counters.txt sq_issue.json bench_py_kernel_stats.txt bench_py_line.json; do

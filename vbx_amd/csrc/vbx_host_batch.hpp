@@ -136,6 +136,7 @@ static int leaf_create(vbx_ctx* ctx, int n_rec, const int64_t* T, const int32_t*
         }
         row += rd.T;
         maxT = std::max<long long>(maxT, rd.T);
+        b->maxtiles = std::max(b->maxtiles, rd.ntiles);
     }
     b->sum_T = row;
     b->ntiles_total = b->nblocks_chunk = (int)tile_rec.size();
@@ -531,8 +532,7 @@ static int leaf_set_recording_resident(vbx_batch* b, int rec, const vbx_xvectors
     // softmax(smoothing * onehot) row (vbhmm.py:152, scipy.special.softmax: exp(x - max) / sum)
     const double z = std::exp(-init_smoothing), den = 1.0 + (rd.S - 1) * z;
     const double hi = 1.0 / den, lo = z / den;
-    int rc = b->precision == VBX_PREC_FP64 ? set_recording_resident_impl<double>(b, rec, d_fea, labels, hi, lo, Phi)
-                                            : set_recording_resident_impl<float>(b, rec, d_fea, labels, hi, lo, Phi);
+    int rc = with_precision(b->precision, [&](auto r) { return set_recording_resident_impl<decltype(r)>(b, rec, d_fea, labels, hi, lo, Phi); });
     if (rc != VBX_OK) return rc;
     b->is_set[rec] = 1;
     b->recs_dirty = true;
@@ -544,8 +544,7 @@ static int leaf_get_labels(vbx_batch* b, int rec, int32_t* first, int32_t* secon
     if (!b) return VBX_ERR_INVALID;
     if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
     HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
-    return b->precision == VBX_PREC_FP64 ? get_labels_impl<double>(b, rec, first, second)
-                                         : get_labels_impl<float>(b, rec, first, second);
+    return with_precision(b->precision, [&](auto r) { return get_labels_impl<decltype(r)>(b, rec, first, second); });
 }
 
 // `rec` gets (back) a rho of its own: recordings that read its rows so far are unset, and it leaves the group it was in
@@ -585,9 +584,7 @@ static int leaf_set_recording(vbx_batch* b, int rec, const void* X, int x_dtype,
     rd.Fa = Fa;
     rd.Fb = Fb;
     own_rho(b, rec);
-    int rc = b->precision == VBX_PREC_FP64
-                 ? set_recording_impl<double>(b, rec, X, x_dtype, Phi, pi0, gamma0, g_dtype, alpha0, invL0)
-                 : set_recording_impl<float>(b, rec, X, x_dtype, Phi, pi0, gamma0, g_dtype, alpha0, invL0);
+    int rc = with_precision(b->precision, [&](auto r) { return set_recording_impl<decltype(r)>(b, rec, X, x_dtype, Phi, pi0, gamma0, g_dtype, alpha0, invL0); });
     if (rc != VBX_OK) return rc;
     b->is_set[rec] = 1;
     b->recs_dirty = true;
@@ -631,9 +628,7 @@ static int leaf_set_recording_shared(vbx_batch* b, int rec, int src, const doubl
     // tile (finite values that meet gamma = 0, vbx_chunk_post.hpp), so they must not hold whatever the block held before
     HIPCHK(ctx, hipMemsetAsync((char*)b->d_rho + (size_t)rd.row0 * b->Dp * b->rsize, 0,
                                (size_t)std::min(rd.T, kTileFrames) * b->Dp * b->rsize, ctx->stream));
-    int rc = b->precision == VBX_PREC_FP64
-                 ? set_recording_impl<double>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0)
-                 : set_recording_impl<float>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0);
+    int rc = with_precision(b->precision, [&](auto r) { return set_recording_impl<decltype(r)>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0); });
     if (rc != VBX_OK) return rc;
     b->is_set[rec] = 1;
     b->recs_dirty = true;
@@ -675,9 +670,7 @@ static int leaf_set_recording_cloned(vbx_batch* b, int rec, vbx_batch* from, int
                                (size_t)rd.T * b->Dp * b->rsize, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * b->Dp, from->d_phi + (size_t)src * b->Dp, sizeof(double) * b->Dp, hipMemcpyDeviceToDevice, ctx->stream));
     rd.gsum = from->recs[src].gsum;
-    int rc = b->precision == VBX_PREC_FP64
-                 ? set_recording_impl<double>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0)
-                 : set_recording_impl<float>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0);
+    int rc = with_precision(b->precision, [&](auto r) { return set_recording_impl<decltype(r)>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0); });
     if (rc != VBX_OK) return rc;
     b->is_set[rec] = 1;
     b->recs_dirty = true;
@@ -870,13 +863,14 @@ static int run_begin(vbx_batch* b, int max_iters) {
     if (b->score_any && (rc = score_prepare(b)) != VBX_OK) return rc;
     HIPCHK(ctx, hipEventRecord(b->ev_start, ctx->stream));
     // (inside the timed run and under VBX_K_PREP: the first run after an upload pays two more passes over rho in split mode)
-    return prepare_split(b);
+    if ((rc = prepare_split(b)) != VBX_OK) return rc;
+    plan_iteration(b);
+    return VBX_OK;
 }
 
 static void run_launch(vbx_batch* b, double epsilon) {
     b->run_epsilon = epsilon;
-    if (b->precision == VBX_PREC_FP64) launch_iteration<double>(b, epsilon);
-    else launch_iteration<float>(b, epsilon);
+    with_precision(b->precision, [&](auto r) { launch_iteration<decltype(r)>(b, epsilon); });
     ++b->iters_launched;
 }
 
@@ -906,15 +900,9 @@ static int run_all_done(vbx_batch* b, bool* all_done) {
 extern "C++" {
 namespace {
 template <typename R> void launch_gamma_replay(vbx_batch* b) {
-    b->fused_now = true;
     auto v = b->view<R>(0.0);
     LaunchScope ls(b, VBX_K_POST);
-    switch (b->Sp) {
-        case 16: launch_chunk_post<R, 16, true>(b, v); break;
-        case 32: launch_chunk_post<R, 32, true>(b, v); break;
-        case 64: launch_chunk_post<R, 64, true>(b, v); break;
-        default: break;
-    }
+    for_fused_sp(b->Sp, [&](auto sp) { launch_chunk_post<R, decltype(sp)::value, true>(b, v); });
 }
 }  // namespace
 }  // extern "C++"
@@ -923,13 +911,11 @@ template <typename R> void launch_gamma_replay(vbx_batch* b) {
 // fused kernels kept it on the chip
 static void run_close_launches(vbx_batch* b) {
     if (b->fin_pending) {                     // the last iteration launched: ELBO, pi, history, convergence
-        if (b->precision == VBX_PREC_FP64) launch_fin<double>(b, b->run_epsilon, 2);
-        else launch_fin<float>(b, b->run_epsilon, 2);
+        with_precision(b->precision, [&](auto r) { launch_fin<decltype(r)>(b, b->run_epsilon, 2); });
         b->fin_pending = false;
     }
     if (b->gamma_stale) {
-        if (b->precision == VBX_PREC_FP64) launch_gamma_replay<double>(b);
-        else launch_gamma_replay<float>(b);
+        with_precision(b->precision, [&](auto r) { launch_gamma_replay<decltype(r)>(b); });
         b->gamma_stale = false;
     }
 }
@@ -941,12 +927,10 @@ static void run_score(vbx_batch* b) {
     run_close_launches(b);
     LaunchScope ls(b, VBX_K_POST);
     const RecState* st = b->d_state + (size_t)b->state_cur * b->n_rec;
-    if (b->precision == VBX_PREC_FP64)
-        score_launch<double>(b->ctx->stream, (const double*)b->d_gamma, b->Sp, b->n_rec, b->max_iters, b->d_recs, b->d_score_rec, b->d_score_lab,
-                             b->d_score_items, b->score_items, b->score_rmax, st, 0, b->d_score_part, b->d_score_hist);
-    else
-        score_launch<float>(b->ctx->stream, (const float*)b->d_gamma, b->Sp, b->n_rec, b->max_iters, b->d_recs, b->d_score_rec, b->d_score_lab,
-                            b->d_score_items, b->score_items, b->score_rmax, st, 0, b->d_score_part, b->d_score_hist);
+    with_precision(b->precision, [&](auto r) {
+        score_launch(b->ctx->stream, (const decltype(r)*)b->d_gamma, b->Sp, b->n_rec, b->max_iters, b->d_recs, b->d_score_rec, b->d_score_lab,
+                     b->d_score_items, b->score_items, b->score_rmax, st, 0, b->d_score_part, b->d_score_hist);
+    });
 }
 
 static int run_end(vbx_batch* b) {
@@ -1103,9 +1087,7 @@ static int leaf_fetch_enqueue(vbx_batch* b, int rec, double* gamma, double* pi, 
     if (!b) return VBX_ERR_INVALID;
     if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
     HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
-    return b->precision == VBX_PREC_FP64
-               ? fetch_enqueue_impl<double>(b, rec, gamma, pi, Li, li_cap, n_iters, warned, alpha, invL)
-               : fetch_enqueue_impl<float>(b, rec, gamma, pi, Li, li_cap, n_iters, warned, alpha, invL);
+    return with_precision(b->precision, [&](auto r) { return fetch_enqueue_impl<decltype(r)>(b, rec, gamma, pi, Li, li_cap, n_iters, warned, alpha, invL); });
 }
 
 static int leaf_fetch_finish(vbx_batch* b) {

@@ -489,9 +489,9 @@ int vbx_batch_stream_of(const vbx_batch* b, int rec) {
 
 int vbx_batch_stream_loads_in_effect(const vbx_batch* b) {
     if (!b) return 0;
-    if (b->kids.empty()) return b->stream_now ? 1 : 0;
+    if (b->kids.empty()) return b->plan.stream ? 1 : 0;
     for (const vbx_batch* k : b->kids)
-        if (!k->stream_now) return 0;
+        if (!k->plan.stream) return 0;
     return 1;
 }
 
@@ -499,10 +499,10 @@ int vbx_stream_loads_auto(int64_t rho_bytes) { return stream_loads_auto((long lo
 
 int vbx_batch_gemm_in_effect(const vbx_batch* b) {
     if (!b) return VBX_GEMM_EXACT;
-    if (b->kids.empty()) return b->split_now ? VBX_GEMM_SPLIT : VBX_GEMM_EXACT;
+    if (b->kids.empty()) return b->plan.split ? VBX_GEMM_SPLIT : VBX_GEMM_EXACT;
     // a stream group: the range guard of the split mode (prepare_split) acts per sub-batch; "split" = every one of them
     for (const vbx_batch* k : b->kids)
-        if (!k->split_now) return VBX_GEMM_EXACT;
+        if (!k->plan.split) return VBX_GEMM_EXACT;
     return VBX_GEMM_SPLIT;
 }
 

@@ -25,38 +25,26 @@ struct LaunchScope {   // brackets one kernel launch with events when profiling 
     }
 };
 
-#define NT_SWITCH(nt_, BODY)                                   \
-    switch (nt_) {                                             \
-        case 1: { constexpr int kNT = 1; BODY } break;         \
-        case 2: { constexpr int kNT = 2; BODY } break;         \
-        case 4: { constexpr int kNT = 4; BODY } break;         \
-        case 8: { constexpr int kNT = 8; BODY } break;         \
-        case 16: { constexpr int kNT = 16; BODY } break;       \
-        default: b->launch_rc = VBX_ERR_UNSUPPORTED; break;    \
-    }
+// The padded widths each kernel family is instantiated for: Sp of the fused per-chunk kernels and the scan in LDS, of the wide
+// scan, of post_kernel; tiles of 16 speakers per block (also fb_seq_kernel's states per lane / 4); Sp / 1024 beyond 1024 states
+template <typename F> bool for_fused_sp(int sp, F&& f) { return dispatch_int<16, 32, 64>(sp, f); }
+template <typename F> bool for_wide_sp(int sp, F&& f) { return dispatch_int<128, 256>(sp, f); }
+template <typename F> bool for_post_sp(int sp, F&& f) { return dispatch_int<16, 32, 64, 128, 256, 512, 1024>(sp, f); }
+template <typename F> bool for_nt(int nt, F&& f) { return dispatch_int<1, 2, 4, 8, 16>(nt, f); }
+template <typename F> bool for_big_nr(int sp, F&& f) { return dispatch_int<2, 4, 8, 16>(sp >> 10, f); }
 
 template <typename R> void launch_mstep_acc(vbx_batch* b, double eps) {
     auto v = b->view<R>(eps);
     LaunchScope ls(b, VBX_K_MSTEP_ACC);
     const int nt = std::min(b->NT, 16);                       // (more than 256 speakers: blocks of 16 tiles along grid z)
     dim3 grid(b->ntiles_total, b->Dp / 32, b->NT / nt);
-    NT_SWITCH(nt, hipLaunchKernelGGL((mstep_acc_kernel<R, kNT>), grid, dim3(64), 0, b->ctx->stream, v);)
+    if (!for_nt(nt, [&](auto n) { hipLaunchKernelGGL((mstep_acc_kernel<R, decltype(n)::value>), grid, dim3(64), 0, b->ctx->stream, v); }))
+        b->launch_rc = VBX_ERR_UNSUPPORTED;
 }
-
-static int small_kernel_threads(const vbx_batch* b, int from_tiles);
 
 // fin_kernel (vbx_kernels.hpp): mode 1 = start an iteration (M-step), 2 = finish one (ELBO, pi, convergence), 3 = finish
 // the previous one and start the next in the same launch.  A launch with a finishing role writes the other state copy.
-// More than 1024 states (vbx_big.hpp): switch over NR = Sp / 1024
-#define BIG_SWITCH(sp, BODY)                                   \
-    switch ((sp) >> 10) {                                      \
-        case 2: { constexpr int kNR = 2; BODY } break;         \
-        case 4: { constexpr int kNR = 4; BODY } break;         \
-        case 8: { constexpr int kNR = 8; BODY } break;         \
-        case 16: { constexpr int kNR = 16; BODY } break;       \
-        default: break;                                        \
-    }
-
+// More than 1024 states (vbx_big.hpp): NR = Sp / 1024
 template <typename R> void launch_fin(vbx_batch* b, double eps, int mode) {
     if (b->Sp > 1024) {
         // the finishing role has a kernel of its own there (a thread per speaker does not reach); it runs first and the host
@@ -64,7 +52,7 @@ template <typename R> void launch_fin(vbx_batch* b, double eps, int mode) {
         if (mode & 2) {
             auto v = b->view<R>(eps);
             LaunchScope ls(b, VBX_K_ITER_FIN);
-            BIG_SWITCH(b->Sp, hipLaunchKernelGGL((iter_fin_big_kernel<R, kNR>), dim3(b->n_rec), dim3(1024), 0, b->ctx->stream, v);)
+            for_big_nr(b->Sp, [&](auto nr) { hipLaunchKernelGGL((iter_fin_big_kernel<R, decltype(nr)::value>), dim3(b->n_rec), dim3(1024), 0, b->ctx->stream, v); });
             b->state_cur ^= 1;
         }
         if (mode & 1) {
@@ -76,7 +64,7 @@ template <typename R> void launch_fin(vbx_batch* b, double eps, int mode) {
     }
     auto v = b->view<R>(eps);
     LaunchScope ls(b, mode == 2 ? VBX_K_ITER_FIN : VBX_K_MSTEP_FIN);
-    hipLaunchKernelGGL((fin_kernel<R>), dim3(b->n_rec, b->Sp + 1), dim3(small_kernel_threads(b, 80)), 0, b->ctx->stream, v, mode);
+    hipLaunchKernelGGL((fin_kernel<R>), dim3(b->n_rec, b->Sp + 1), dim3(b->plan.fin_threads), 0, b->ctx->stream, v, mode);
     if (mode & 2) b->state_cur ^= 1;
 }
 
@@ -90,8 +78,10 @@ template <typename R> void launch_loglik(vbx_batch* b, double eps, bool raw) {
     LaunchScope ls(b, VBX_K_LOGLIK);
     R* lraw = raw ? (R*)b->d_lraw : nullptr;
     const int nt = std::min(b->NT, 16);
-    NT_SWITCH(nt, hipLaunchKernelGGL((loglik_kernel<R, kNT>), dim3(b->ntiles_total, b->NT / nt), dim3(256), 0,
-                                     b->ctx->stream, v, lraw);)
+    if (!for_nt(nt, [&](auto n) {
+            hipLaunchKernelGGL((loglik_kernel<R, decltype(n)::value>), dim3(b->ntiles_total, b->NT / nt), dim3(256), 0, b->ctx->stream, v, lraw);
+        }))
+        b->launch_rc = VBX_ERR_UNSUPPORTED;
     if (b->NT > nt)          // the row maximum spans several speaker blocks
         hipLaunchKernelGGL((rownorm_kernel<R>), dim3(b->ntiles_total), dim3(256), 0, b->ctx->stream, v);
 }
@@ -99,22 +89,16 @@ template <typename R> void launch_loglik(vbx_batch* b, double eps, bool raw) {
 // Block size of the per-recording reductions over tiles (fin_kernel): more threads once a recording has more partials than
 // the smaller block fetches in a few rounds (one recording of T = 200 000, rounds 2-3: mstep_fin 42 -> 30 us, iter_fin 33 -> 23 us
 // with 1024 threads instead of 256).
-static int small_kernel_threads(const vbx_batch* b, int from_tiles) {
-    int maxtiles = 0;
-    for (auto& rd : b->recs) maxtiles = std::max(maxtiles, rd.ntiles);
+static int fin_threads_wanted(const vbx_batch* b) {
     // (round 6, one recording, split, us per iteration with 256 / 512 / 1024 threads: T = 12 000 48.7 / 48.0 / 51.3, 20 000 52.9 /
     //  53.6 / 56.1, 50 000 74.0 / 73.4 / 75.9, 100 000 102.8 / 98.0 / 100.2; four of T = 20 000: 65.5 / 65.0 / 68.8 -- the barriers
     //  of a block of sixteen waves cost more than its shorter rounds save until a recording has about a thousand partials)
     if (b->Sp > 256) return 1024;                                      // (iter_fin: a thread per speaker)
     // (T = 150 000 / 200 000 alone: 126.1 / 149.7 with 512 against 125.0 / 148.6 with 1024; the nine-point sweep over T = 200 000
     //  on three streams: 1.390 against 1.407 ms -- the lighter block fits beside the other streams' kernels)
-    return (maxtiles > 1200 && b->n_rec == 1) ? 1024 : maxtiles > from_tiles ? 512 : 256;
+    return (b->maxtiles > 1200 && b->n_rec == 1) ? 1024 : b->maxtiles > 80 ? 512 : 256;
 }
 
-// chunk_post over the tiles of the batch; REPLAY: the instance that only writes the responsibilities
-// Does chunk_post walk the last level of the boundary walk itself (FOLD, vbx_chunk_post.hpp)?  Where an iteration is its launches:
-// a grouped walk, the group's operators fit the free LDS region, and the batch does not fill the chip (beyond that the extra
-// mat-vecs per workgroup cost more than the launch they replace).
 // A batch that does not fill the chip: the small-batch instances of the chunk kernels (FOLD / LAT).
 static bool small_batch_wanted(const vbx_batch* b) { return b->ntiles_total <= 2048; }
 // Non-temporal loads of rho in the per-chunk kernels (VBX_OPT_STREAM_LOADS)?  Each launch reads every line of its rho copy once.
@@ -130,67 +114,62 @@ static bool stream_loads_wanted(const vbx_batch* b) {
         if (b->share_src[i] == i) own += b->recs[i].T * (long long)b->Dp * (long long)b->rsize;
     return stream_loads_auto(b->group_rho_bytes > 0 ? b->group_rho_bytes : own);
 }
-template <int SP> bool fold_walk_wanted(const vbx_batch* b) {
-    if (SP > 32 || b->sgroup <= 1 || b->sgroup - 1 > kTileFrames / SP) return false;
-    return small_batch_wanted(b) && !b->stream_now;       // (no streaming FOLD instance: the last level is a launch of its own then)
+// Does chunk_post walk the last level of the boundary walk itself (FOLD, vbx_chunk_post.hpp)?  Where an iteration is its launches:
+// a grouped walk and a batch that does not fill the chip (beyond that the extra mat-vecs per workgroup cost more than the launch
+// they replace) -- in groups whose operators fit the free LDS region: at most fold_max_group chunks.  choose_fb_algo caps the
+// automatic group size with this, plan_iteration decides with it.
+static bool fold_wanted(const vbx_batch* b, bool fused_post, int group) {
+    return fused_post && b->Sp <= 32 && group > 1 && small_batch_wanted(b);
+}
+static int fold_max_group(const vbx_batch* b) { return kTileFrames / std::max(b->Sp, 1) + 1; }
+
+// The instance of chunk_post for this plan; REPLAY: the one that only writes the responsibilities (never split)
+template <typename R, int SP, bool REPLAY> auto chunk_post_instance(const IterPlan& p) -> void (*)(BatchView<R>) {
+    constexpr bool kCanFold = SP <= 32;                      // (a group has at least four chunks: three operators in r1)
+    if constexpr (std::is_same<R, float>::value && !REPLAY) {
+        if (p.split) {                                       // gamma^T rho on the f16 matrix cores (vbx_split.hpp)
+            if constexpr (kCanFold)
+                if (p.fold) return chunk_post_kernel<R, SP, false, true, true>;
+            if (p.stream) return chunk_post_kernel<R, SP, false, true, false, StreamLoads>;
+            return chunk_post_kernel<R, SP, false, true>;
+        }
+    }
+    if constexpr (kCanFold)
+        if (p.fold) return chunk_post_kernel<R, SP, REPLAY, false, true>;
+    return chunk_post_kernel<R, SP, REPLAY>;
+}
+
+// The instance of chunk_loglik for this plan
+template <typename R, int SP> auto chunk_loglik_instance(const IterPlan& p) -> void (*)(BatchView<R>) {
+    if constexpr (std::is_same<R, float>::value) {
+        if (p.split) {                                       // rho alpha^T on the f16 matrix cores (vbx_split.hpp)
+            if constexpr (SP <= 32)
+                if (p.lat) {
+                    if (p.stream) return chunk_loglik_kernel<R, SP, true, true, StreamLoads>;
+                    return chunk_loglik_kernel<R, SP, true, true>;
+                }
+            if (p.stream) return chunk_loglik_kernel<R, SP, true, false, StreamLoads>;
+            return chunk_loglik_kernel<R, SP, true>;
+        }
+    }
+    // (exact f32 and fp64: LAT measured slower -- 8 recordings 70.9 -> 79.9 / 117.6 -> 120.8 us per iteration together
+    //  with chunk_post's counterpart: the extra registers cost the occupancy these batches need; split only)
+    return chunk_loglik_kernel<R, SP>;
 }
 
 template <typename R, int SP, bool REPLAY> void launch_chunk_post(vbx_batch* b, const BatchView<R>& v) {
-    if constexpr (ChunkPostCfg<R, SP>::kFits) {
-        constexpr bool kCanFold = SP <= 32;                  // (a group has at least four chunks: three operators in r1)
-        const bool fold = kCanFold && b->fold_now;
-        if constexpr (std::is_same<R, float>::value && !REPLAY) {
-            if (v.rho_b) {                                   // gamma^T rho on the f16 matrix cores (vbx_split.hpp)
-                if constexpr (kCanFold) {
-                    if (fold) {
-                        hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true, true>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
-                        return;
-                    }
-                }
-                if (b->stream_now) hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true, false, StreamLoads>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
-                else hipLaunchKernelGGL((chunk_post_kernel<R, SP, false, true>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
-                return;
-            }
-        }
-        if constexpr (kCanFold) {
-            if (fold) {
-                hipLaunchKernelGGL((chunk_post_kernel<R, SP, REPLAY, false, true>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((chunk_post_kernel<R, SP, REPLAY>), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
-    }
+    if constexpr (ChunkPostCfg<R, SP>::kFits)
+        hipLaunchKernelGGL((chunk_post_instance<R, SP, REPLAY>(b->plan)), dim3(b->nblocks_chunk), dim3(256), 0, b->ctx->stream, v);
 }
 
-template <typename R, int SP> void launch_scan(vbx_batch* b, const BatchView<R>& v, bool fused_post, bool fused_loglik) {
+template <typename R, int SP> void launch_scan(vbx_batch* b, const BatchView<R>& v) {
+    const IterPlan& p = b->plan;
     hipStream_t st = b->ctx->stream;
     bool have_op = false;
     if constexpr (ChunkLoglikCfg<R, SP>::kFits) {
-        if (fused_loglik) {      // log-likelihoods and the chunk operators in one pass over rho
+        if (p.fused_loglik) {      // log-likelihoods and the chunk operators in one pass over rho
             LaunchScope ls(b, VBX_K_CHUNK_LOGLIK);
-            bool launched = false;
-            // LAT: the whole rho slab of a workgroup in flight before the first product (vbx_chunk_loglik.hpp): batches that do
-            // not fill the chip, feature dimensions that fit the registers
-            const bool lat = SP <= 32 && b->Dp <= 128 && small_batch_wanted(b);
-            if constexpr (std::is_same<R, float>::value) {
-                if (v.rho_a) {                               // rho alpha^T on the f16 matrix cores (vbx_split.hpp)
-                    if constexpr (SP <= 32) {
-                        if (lat) {
-                            if (b->stream_now) hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, true, StreamLoads>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
-                            else hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
-                            launched = true;
-                        }
-                    }
-                    if (!launched) {
-                        if (b->stream_now) hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true, false, StreamLoads>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
-                        else hipLaunchKernelGGL((chunk_loglik_kernel<R, SP, true>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
-                    }
-                    launched = true;
-                }
-            }
-            // (exact f32 and fp64: LAT measured slower -- 8 recordings 70.9 -> 79.9 / 117.6 -> 120.8 us per iteration together
-            //  with chunk_post's counterpart: the extra registers cost the occupancy these batches need; split only)
-            if (!launched) hipLaunchKernelGGL((chunk_loglik_kernel<R, SP>), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
+            hipLaunchKernelGGL((chunk_loglik_instance<R, SP>(p)), dim3(b->nblocks_chunk), dim3(256), 0, st, v);
             have_op = true;
         }
     }
@@ -198,27 +177,24 @@ template <typename R, int SP> void launch_scan(vbx_batch* b, const BatchView<R>&
         LaunchScope ls(b, VBX_K_FB);
         hipLaunchKernelGGL((scan1_kernel<R, SP>), dim3(b->ntiles_total), dim3(SP * SP / 4), 0, st, v);
     }
-    bool fold = false;
-    if constexpr (ChunkPostCfg<R, SP>::kFits) fold = fused_post && fold_walk_wanted<SP>(b);
-    b->fold_now = fold;                          // (the gamma write-out after the run replays with the same choice)
     {
         LaunchScope ls(b, VBX_K_FB_AUX);
-        if (b->sgroup > 1 && b->sgroup2 > 1) {   // very long recordings: groups of groups on top
+        if (p.walk_levels == 3) {                // very long recordings: groups of groups on top
             hipLaunchKernelGGL((scan_compose_kernel<R, SP>), dim3(b->nsup_total), dim3(256), 0, st, v, 1);
             hipLaunchKernelGGL((scan_compose_kernel<R, SP>), dim3(b->nsup2_total), dim3(256), 0, st, v, 2);
             hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->n_rec, 2), dim3(256), 0, st, v, 4);
             hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->nsup2_total, 2), dim3(256), 0, st, v, 5);
-            if (!fold) hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->nsup_total, 2), dim3(256), 0, st, v, 3);
-        } else if (b->sgroup > 1) {     // long recordings: group operators, boundaries at the group edges, then inside the groups
+        } else if (p.walk_levels == 2) {         // long recordings: group operators, boundaries at the group edges, then inside the groups
             hipLaunchKernelGGL((scan_compose_kernel<R, SP>), dim3(b->nsup_total), dim3(256), 0, st, v, 1);
             hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->n_rec, 2), dim3(256), 0, st, v, 2);
-            if (!fold) hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->nsup_total, 2), dim3(256), 0, st, v, 3);
         } else {
             hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->n_rec, 2), dim3(256), 0, st, v, 0);
         }
+        // the last level, inside the groups: a launch of its own unless chunk_post walks it (FOLD)
+        if (p.walk_levels > 1 && !p.fold) hipLaunchKernelGGL((scan2_kernel<R, SP>), dim3(b->nsup_total, 2), dim3(256), 0, st, v, 3);
     }
     if constexpr (ChunkPostCfg<R, SP>::kFits) {
-        if (fused_post) {
+        if (p.fused_post) {
             LaunchScope ls(b, VBX_K_CHUNK_POST);
             launch_chunk_post<R, SP, false>(b, v);
             return;
@@ -256,105 +232,86 @@ template <typename R, int SP> void launch_scan_wide(vbx_batch* b, const BatchVie
     }
 }
 
-template <typename R> bool fused_loglik_available(const vbx_batch* b) {
-    if (!b->use_chunked || b->fuse < 2) return false;
-    switch (b->Sp) {
-        case 16: return ChunkLoglikCfg<R, 16>::kFits;
-        case 32: return ChunkLoglikCfg<R, 32>::kFits;
-        case 64: return ChunkLoglikCfg<R, 64>::kFits;
-        default: return false;
-    }
+// Can this batch run the fused per-chunk kernels?  (chunked scan + the lattices fit in LDS): chunk_post from fuse = 1,
+// chunk_loglik as well at fuse = 2
+template <typename R> bool fused_available(const vbx_batch* b, bool loglik = false) {
+    if (!b->use_chunked || b->fuse < (loglik ? 2 : 1)) return false;
+    bool fits = false;
+    for_fused_sp(b->Sp, [&](auto sp) {
+        constexpr int SP = decltype(sp)::value;
+        fits = loglik ? ChunkLoglikCfg<R, SP>::kFits : ChunkPostCfg<R, SP>::kFits;
+    });
+    return fits;
 }
 
-// Can this batch run the fused per-chunk kernels?  (chunked scan + the lattices fit in LDS)
-template <typename R> bool fused_available(const vbx_batch* b) {
-    if (!b->use_chunked || !b->fuse) return false;
-    switch (b->Sp) {
-        case 16: return ChunkPostCfg<R, 16>::kFits;
-        case 32: return ChunkPostCfg<R, 32>::kFits;
-        case 64: return ChunkPostCfg<R, 64>::kFits;
-        default: return false;
-    }
-}
-
-template <typename R> void launch_fb(vbx_batch* b, double eps, bool fused_post = false, bool fused_loglik = false) {
+template <typename R> void launch_fb(vbx_batch* b, double eps) {
     auto v = b->view<R>(eps);
     if (b->use_chunked) {
-        switch (b->Sp) {
-            case 16: launch_scan<R, 16>(b, v, fused_post, fused_loglik); return;
-            case 32: launch_scan<R, 32>(b, v, fused_post, fused_loglik); return;
-            case 64: launch_scan<R, 64>(b, v, fused_post, fused_loglik); return;
-            case 128: launch_scan_wide<R, 128>(b, v); return;
-            case 256: launch_scan_wide<R, 256>(b, v); return;
-            default: break;
-        }
+        if (for_fused_sp(b->Sp, [&](auto sp) { launch_scan<R, decltype(sp)::value>(b, v); })) return;
+        if (for_wide_sp(b->Sp, [&](auto sp) { launch_scan_wide<R, decltype(sp)::value>(b, v); })) return;
     }
     LaunchScope ls(b, VBX_K_FB);
-    const int nreg = std::max(1, b->Sp / 64);
-    switch (nreg) {
-        case 1: hipLaunchKernelGGL((fb_seq_kernel<R, 1>), dim3(b->n_rec), dim3(128), 0, b->ctx->stream, v); break;
-        case 2: hipLaunchKernelGGL((fb_seq_kernel<R, 2>), dim3(b->n_rec), dim3(128), 0, b->ctx->stream, v); break;
-        case 4: hipLaunchKernelGGL((fb_seq_kernel<R, 4>), dim3(b->n_rec), dim3(128), 0, b->ctx->stream, v); break;
-        case 8: hipLaunchKernelGGL((fb_seq_kernel<R, 8>), dim3(b->n_rec), dim3(128), 0, b->ctx->stream, v); break;
-        case 16: hipLaunchKernelGGL((fb_seq_kernel<R, 16>), dim3(b->n_rec), dim3(128), 0, b->ctx->stream, v); break;
-        default: BIG_SWITCH(b->Sp, hipLaunchKernelGGL((fb_big_kernel<R, kNR>), dim3(b->n_rec, 2), dim3(1024), 0, b->ctx->stream, v);) break;
-    }
+    if (!for_nt(std::max(1, b->Sp / 64), [&](auto nreg) {
+            hipLaunchKernelGGL((fb_seq_kernel<R, decltype(nreg)::value>), dim3(b->n_rec), dim3(128), 0, b->ctx->stream, v);
+        }))
+        for_big_nr(b->Sp, [&](auto nr) { hipLaunchKernelGGL((fb_big_kernel<R, decltype(nr)::value>), dim3(b->n_rec, 2), dim3(1024), 0, b->ctx->stream, v); });
 }
 
 template <typename R> void launch_post(vbx_batch* b, double eps) {
     auto v = b->view<R>(eps);
     LaunchScope ls(b, VBX_K_POST);
     dim3 grid(b->ntiles_total), block(256);
-    switch (b->Sp) {
-        case 16: hipLaunchKernelGGL((post_kernel<R, 16>), grid, block, 0, b->ctx->stream, v); break;
-        case 32: hipLaunchKernelGGL((post_kernel<R, 32>), grid, block, 0, b->ctx->stream, v); break;
-        case 64: hipLaunchKernelGGL((post_kernel<R, 64>), grid, block, 0, b->ctx->stream, v); break;
-        case 128: hipLaunchKernelGGL((post_kernel<R, 128>), grid, block, 0, b->ctx->stream, v); break;
-        case 256: hipLaunchKernelGGL((post_kernel<R, 256>), grid, block, 0, b->ctx->stream, v); break;
-        case 512: hipLaunchKernelGGL((post_kernel<R, 512>), grid, block, 0, b->ctx->stream, v); break;
-        case 1024: hipLaunchKernelGGL((post_kernel<R, 1024>), grid, block, 0, b->ctx->stream, v); break;
-        default: hipLaunchKernelGGL((post_big_kernel<R>), grid, block, 0, b->ctx->stream, v); break;     // > 1024 states (vbx_big.hpp)
-    }
+    if (!for_post_sp(b->Sp, [&](auto sp) { hipLaunchKernelGGL((post_kernel<R, decltype(sp)::value>), grid, block, 0, b->ctx->stream, v); }))
+        hipLaunchKernelGGL((post_big_kernel<R>), grid, block, 0, b->ctx->stream, v);     // > 1024 states (vbx_big.hpp)
 }
 
 // Can this batch multiply with f16 operand pairs (VBX_OPT_GEMM = split)?  fp32, both fused per-chunk kernels -- and
 // (split_available) x-vectors whose dynamic range one power-of-two scale per recording covers (prepare_split).
 static bool split_wanted(const vbx_batch* b) {
     return b->gemm == VBX_GEMM_SPLIT && b->precision == VBX_PREC_FP32 && b->Dp <= kSplitMaxDp &&
-           fused_available<float>(b) && fused_loglik_available<float>(b);
+           fused_available<float>(b) && fused_available<float>(b, true);
 }
 static bool split_available(const vbx_batch* b) { return split_wanted(b) && !b->split_declined; }
 
+// The launch plan of a run: which instances its iterations -- and the gamma write-out after them -- launch.  Called when a run
+// begins, after choose_fb_algo (use_chunked, the group sizes) and prepare_split (d_rho_a, split_declined); every input is
+// constant from there to the end of the run.
+static void plan_iteration(vbx_batch* b) {
+    IterPlan p;
+    p.fused_post = with_precision(b->precision, [&](auto r) { return fused_available<decltype(r)>(b); });
+    p.fused_loglik = p.fused_post && with_precision(b->precision, [&](auto r) { return fused_available<decltype(r)>(b, true); });
+    // half-tile re-runs: most where the chains' latency is exposed (one recording 65 -> 58 us per iteration, fp64
+    // batches -13 %), a few percent with thousands of f32 tiles in flight (there the operator build is
+    // VALU-throughput bound and chunk_loglik pays 5 % for what chunk_post gains) -- never a loss, so on unless asked
+    p.half_ops = p.fused_loglik && b->split_tiles != 2;
+    p.split = p.fused_post && b->d_rho_a != nullptr && split_available(b);
+    p.stream = p.split && stream_loads_wanted(b);
+    p.small = small_batch_wanted(b);
+    // LAT: the whole rho slab of a workgroup in flight before the first product (vbx_chunk_loglik.hpp): batches that do
+    // not fill the chip, feature dimensions that fit the registers
+    p.lat = b->Sp <= 32 && b->Dp <= 128 && p.small;
+    // (no streaming FOLD instance: the last level is a launch of its own then)
+    p.fold = fold_wanted(b, p.fused_post, b->sgroup) && b->sgroup <= fold_max_group(b) && !p.stream;
+    p.walk_levels = b->sgroup > 1 ? (b->sgroup2 > 1 ? 3 : 2) : 1;
+    p.fin_threads = fin_threads_wanted(b);
+    b->plan = p;
+}
+
 template <typename R> void launch_iteration(vbx_batch* b, double eps) {
-    b->fused_now = fused_available<R>(b);
-    b->split_now = b->d_rho_a != nullptr && split_available(b);
-    b->stream_now = b->split_now && b->fused_now && stream_loads_wanted(b);
+    const IterPlan& p = b->plan;
     // the previous iteration of this run (if any) is finished by the launch that starts this one; the last one of a run
     // by run_end
     const int fin_mode = b->fin_pending ? 3 : 1;
     b->fin_pending = true;
-    if (b->fused_now) {
-        // chunk_post leaves gamma^T rho of the gamma it has just written in mpart/npart, so only the
-        // first iteration after an upload needs the stand-alone accumulation
-        if (!b->mpart_valid) launch_mstep_acc<R>(b, eps);
-        launch_fin<R>(b, eps, fin_mode);
-        const bool fl = fused_loglik_available<R>(b);
-        // half-tile re-runs: most where the chains' latency is exposed (one recording 65 -> 58 us per iteration, fp64
-        // batches -13 %), a few percent with thousands of f32 tiles in flight (there the operator build is
-        // VALU-throughput bound and chunk_loglik pays 5 % for what chunk_post gains) -- never a loss, so on unless asked
-        b->half_ops_now = fl && b->split_tiles != 2;
-        if (!fl) launch_loglik<R>(b, eps, false);
-        launch_fb<R>(b, eps, true, fl);
-        b->mpart_valid = true;
-        b->gamma_stale = true;
-        return;
-    }
-    launch_mstep_acc<R>(b, eps);
+    // chunk_post leaves gamma^T rho of the gamma it has just written in mpart/npart, so only the
+    // first iteration after an upload needs the stand-alone accumulation
+    if (!p.fused_post || !b->mpart_valid) launch_mstep_acc<R>(b, eps);
     launch_fin<R>(b, eps, fin_mode);
-    launch_loglik<R>(b, eps, false);
+    if (!p.fused_loglik) launch_loglik<R>(b, eps, false);
     launch_fb<R>(b, eps);
-    launch_post<R>(b, eps);
-    b->mpart_valid = false;
+    if (!p.fused_post) launch_post<R>(b, eps);
+    b->mpart_valid = p.fused_post;
+    if (p.fused_post) b->gamma_stale = true;
 }
 
 template <typename R, typename XT>
@@ -429,8 +386,7 @@ int dmalloc_bytes(vbx_ctx* ctx, void** p, size_t bytes) { return ctx_alloc(ctx, 
 
 // Decide between the sequential walk and the chunked scan, allocating the scan buffers on first use.
 int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
-    int maxtiles = 0;
-    for (auto& rd : b->recs) maxtiles = std::max(maxtiles, rd.ntiles);
+    const int maxtiles = b->maxtiles;
     bool chunked = b->fb_algo == VBX_FB_CHUNKED || (b->fb_algo == VBX_FB_AUTO && maxtiles >= 3);
     if (step_api_logs) chunked = false;      // lfw/lbw reconstruction uses the sequential kernel's scales
     // More than 256 states: an S x S transfer operator per chunk is 1 - 4 MB and its build S^2 operations per frame -- the
@@ -450,7 +406,7 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
     }
     b->use_chunked = chunked;
     // the forward / backward lattices live in HBM only on the paths that do not keep them in LDS
-    const bool fused1 = b->precision == VBX_PREC_FP64 ? fused_available<double>(b) : fused_available<float>(b);
+    const bool fused1 = with_precision(b->precision, [&](auto r) { return fused_available<decltype(r)>(b); });
     if (fused1 && chunked && !b->d_oph) {
         const size_t nt = (size_t)b->ntiles_total, sp = (size_t)b->Sp;
         int rc = dmalloc_bytes(b->ctx, &b->d_oph, 2 * nt * sp * sp * b->rsize);
@@ -501,8 +457,8 @@ int choose_fb_algo(vbx_batch* b, bool step_api_logs) {
     // Round 6: where chunk_post walks the last level itself (FOLD: groups of at most kTileFrames / Sp + 1 chunks) that level
     // costs no launch, so the automatic group size stops there: one recording of T = 20 000 / 30 000 (g = 6 / 7 before, last
     // level a launch of its own) 57.5 -> 54.9 / 64.0 -> 62.0 us per iteration.
-    const int fold_max = kTileFrames / std::max(b->Sp, 1) + 1;
-    const bool may_fold = group > 1 && fused1 && b->Sp <= 32 && small_batch_wanted(b) && b->scan_group == 0;
+    const int fold_max = fold_max_group(b);
+    const bool may_fold = fold_wanted(b, fused1, group) && b->scan_group == 0;
     if (may_fold) group = std::min(group, fold_max);
     // Third level: with products worth ~4 walk steps the chain 4 (g - 1) + 4 (g2 - 1) + K / (g g2) + g2 + g is shortest
     // near g = g2 = (K / 8)^(1/3) rounded up: K = 1563 (T = 200 000): 7 x 7 -> 94 step equivalents against 173 on two

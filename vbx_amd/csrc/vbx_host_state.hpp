@@ -15,6 +15,17 @@ inline const char* experiment_env(const char* name) {
     return (on && on[0] == '1') ? std::getenv(name) : nullptr;
 }
 
+// One dispatch over a run-time integer and one over the precision.  `f` is a generic lambda: it gets the value as a
+// std::integral_constant<int, V> (the working precision as a value of its type), and its body is instantiated for the listed
+// values and no others.  dispatch_int says whether the list held `v`.
+template <int... V, typename F> bool dispatch_int(int v, F&& f) {
+    return ((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
+template <typename F> decltype(auto) with_precision(int precision, F&& f) {
+    if (precision == VBX_PREC_FP64) return f(double{});
+    return f(float{});
+}
+
 }  // namespace
 
 // A process gets four hardware compute queues by default; a fifth HIP stream shares one with another, and two busy
@@ -89,6 +100,22 @@ struct GroupThreads {
     std::vector<std::thread> workers;
 };
 
+// Which kernel instances the iterations of a run launch (plan_iteration, vbx_host_launch.hpp): decided once when a run begins
+// -- everything it depends on is constant until the run ends -- and only read by view(), the launch helpers, the gamma
+// write-out after the run and the *_in_effect getters.  A batch that has never run has the all-false plan.
+struct IterPlan {
+    bool fused_post = false;                      // the fused per-chunk kernels: chunk_post keeps gamma on the chip
+    bool fused_loglik = false;                    // ... and chunk_loglik builds the chunk operators in its pass over rho
+    bool half_ops = false;                        // ... and the half-tile operators chunk_post splits its re-run with
+    bool split = false;                           // f16 operand pairs (VBX_OPT_GEMM = split)
+    bool stream = false;                          // ... in the streaming instances (VBX_OPT_STREAM_LOADS)
+    bool small = false;                           // a batch that does not fill the chip: the small-batch instances (FOLD / LAT)
+    bool lat = false;                             // the split chunk_loglik has its whole rho slab in flight (LAT)
+    bool fold = false;                            // chunk_post walks the last level of the boundary walk itself (FOLD)
+    int walk_levels = 1;                          // the boundary walk: flat chain, groups, groups of groups
+    int fin_threads = 256;                        // block size of fin_kernel
+};
+
 struct vbx_batch {
     vbx_ctx* ctx = nullptr;
     // Stream groups (VBX_OPT_STREAMS): a batch of many recordings is a parent that owns no device memory but K
@@ -126,7 +153,7 @@ struct vbx_batch {
     int n_rec = 0, D = 0, Dp = 0, Sp = 0, NT = 0, precision = 0, max_iters = 0;
     size_t rsize = 4;
     long long sum_T = 0;
-    int ntiles_total = 0;
+    int ntiles_total = 0, maxtiles = 0;           // tiles of all recordings / of the longest one
     std::vector<RecDesc> recs;
     std::vector<char> is_set;
     bool recs_dirty = true;
@@ -134,10 +161,8 @@ struct vbx_batch {
     int fb_algo = VBX_FB_AUTO, check_every = 4, chunk_frames = 0, fuse = 2;
     int split_tiles = 0;                          // option: 0 auto, 1 on, 2 off (VBX_OPT_SPLIT_TILES)
     int gemm = VBX_GEMM_EXACT;                    // option VBX_OPT_GEMM: how the fp32 path multiplies (vbx_split.hpp)
-    bool split_now = false;                       // in effect for the launches being issued: f16 operand pairs
     int stream_loads = VBX_STREAM_LOADS_AUTO;     // option VBX_OPT_STREAM_LOADS: non-temporal loads of rho in the per-chunk kernels
     long long group_rho_bytes = 0;                // a sub-batch of a stream group: one copy of the rho of the WHOLE group (vbx_batch_run)
-    bool stream_now = false;                      // in effect for the launches being issued: the streaming instances
     std::vector<char> split_dirty;                // recording -> its rho has changed since its f16 copies were made
     std::vector<char> split_bad;                  // recording -> its rho spans more than kSplitRangeBits between frames (rho_absmax_kernel)
     bool split_declined = false;                  // ... for any recording: the batch multiplies exactly (vbx_batch_gemm_in_effect says so)
@@ -146,9 +171,7 @@ struct vbx_batch {
     int64_t profile = 0;                          // bit k: bracket launches of kernel class k with HIP events
     bool mpart_valid = false;                     // mpart/npart hold gamma^T rho of the current gamma (fused path)
     bool gamma_stale = false;                     // fused iterations have run since gamma was last written (run_end replays)
-    bool fused_now = false;                       // in effect for the launches being issued: the fused per-chunk kernels
-    bool fold_now = false;                        // ... and chunk_post walks the last level of the boundary walk itself (FOLD)
-    bool half_ops_now = false;                    // ... and chunk_loglik builds the half-tile operators chunk_post splits its re-run with
+    IterPlan plan;                                // in effect for the launches of this run
     void* d_gamma0 = nullptr;
     double* d_pi_prev = nullptr;
     // device memory
@@ -233,16 +256,16 @@ struct vbx_batch {
         v.bias = (R*)d_bias; v.bias_lo = (R*)d_bias + (size_t)2 * n_rec * Sp; v.emodel = d_emodel; v.pi = d_pi; v.mpart = (R*)d_mpart;
         v.npart = (R*)d_npart; v.epart = d_epart; v.Li = d_Li; v.epsilon = epsilon;
         v.ip = d_ip ? d_ip : d_pi; v.fw_scale = (R*)d_fw_scale; v.bw_scale = (R*)d_bw_scale;
-        v.oph = fused_now && half_ops_now ? (R*)d_oph : nullptr; v.ophexp = d_ophexp;
-        v.cop = fused_now ? (R*)d_cop : nullptr; v.lppow = d_lppow;
+        v.oph = plan.half_ops ? (R*)d_oph : nullptr; v.ophexp = d_ophexp;
+        v.cop = plan.fused_post ? (R*)d_cop : nullptr; v.lppow = d_lppow;
         v.op = (R*)d_op; v.opexp = d_opexp; v.fbound = (R*)d_fbound; v.gbound = (R*)d_gbound;
         v.tllpart = use_chunked ? d_tllpart : nullptr; v.sfw = (R*)d_sfw; v.dump = (R*)d_dump;
         v.sop = (R*)d_sop; v.sopexp = d_sopexp; v.sup_rec = d_sup_rec; v.sup_idx = d_sup_idx;
         v.sgroup = sgroup; v.nsup_total = nsup_total;
         v.sop2 = (R*)d_sop2; v.sopexp2 = d_sopexp2; v.sup2_rec = d_sup2_rec; v.sup2_idx = d_sup2_idx;
         v.sgroup2 = sgroup2; v.nsup2_total = nsup2_total;
-        v.gamma0 = fused_now ? (R*)d_gamma0 : nullptr; v.pi_prev = d_pi_prev;
-        const bool sp = split_now && fused_now;
+        v.gamma0 = plan.fused_post ? (R*)d_gamma0 : nullptr; v.pi_prev = d_pi_prev;
+        const bool sp = plan.split;
         v.rho_a = sp ? (const _Float16*)d_rho_a : nullptr; v.rho_b = sp ? (const _Float16*)d_rho_b : nullptr;
         v.rho_e = sp ? d_rho_e : nullptr; v.alpha_frag = sp ? (_Float16*)d_alpha_frag : nullptr; v.alpha_e = sp ? d_alpha_e : nullptr;
         return v;

@@ -32,6 +32,7 @@ int fb_step_impl(vbx_batch* b, int64_t T, int32_t S, const double* lls, double* 
     b->fuse = 0;                                  // stand-alone scan kernels: one operator per tile
     int rc = choose_fb_algo(b, want_logs);
     if (rc != VBX_OK) return rc;
+    plan_iteration(b);
     rc = upload_recs(b);
     if (rc != VBX_OK) return rc;
     launch_fb<R>(b, 0.0);
@@ -118,8 +119,7 @@ int vbx_forward_backward(vbx_ctx* ctx, int64_t T, int32_t S, const double* lls, 
         b->recs_dirty = true;
     }
     if (rc == VBX_OK)
-        rc = precision == VBX_PREC_FP64 ? fb_step_impl<double>(b, T, S, lls, gamma, tll, entered, lfw, lbw)
-                                        : fb_step_impl<float>(b, T, S, lls, gamma, tll, entered, lfw, lbw);
+        rc = with_precision(precision, [&](auto r) { return fb_step_impl<decltype(r)>(b, T, S, lls, gamma, tll, entered, lfw, lbw); });
     vbx_batch_destroy(b);
     return rc;
 }
@@ -226,8 +226,7 @@ int vbx_forward_backward_dense(vbx_ctx* ctx, int64_t T, int32_t S, const double*
     if (S > vbx::kFbDenseBigMax) FAIL(ctx, VBX_ERR_UNSUPPORTED, "forward_backward (dense): S=%d exceeds %d states", S, vbx::kFbDenseBigMax);
     if (precision != VBX_PREC_FP32 && precision != VBX_PREC_FP64) FAIL(ctx, VBX_ERR_INVALID, "unknown precision %d", precision);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return precision == VBX_PREC_FP64 ? fb_dense_impl<double>(ctx, T, S, lls, tr, ip, gamma, tll, lfw, lbw)
-                                      : fb_dense_impl<float>(ctx, T, S, lls, tr, ip, gamma, tll, lfw, lbw);
+    return with_precision(precision, [&](auto r) { return fb_dense_impl<decltype(r)>(ctx, T, S, lls, tr, ip, gamma, tll, lfw, lbw); });
 }
 
 int vbx_mstep(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, const double* Phi, const double* gamma,
@@ -241,7 +240,8 @@ int vbx_mstep(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, co
     rc = vbx_batch_set_recording(b, 0, X, VBX_F64, Phi, pi.data(), gamma, VBX_F64, nullptr, nullptr, 0.9, Fa, Fb);
     if (rc == VBX_OK) rc = upload_recs(b);
     if (rc == VBX_OK) {
-        if (precision == VBX_PREC_FP64) launch_mstep<double>(b, 0.0); else launch_mstep<float>(b, 0.0);
+        plan_iteration(b);
+        with_precision(precision, [&](auto r) { launch_mstep<decltype(r)>(b, 0.0); });
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) {
@@ -267,13 +267,11 @@ int vbx_loglik(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, c
     const size_t cells = (size_t)T * b->Sp;
     if (rc == VBX_OK) rc = dmalloc_bytes(ctx, &b->d_lraw, cells * b->rsize);
     if (rc == VBX_OK) {
-        auto go = [&](auto tag) {
-            using R = decltype(tag);
-            auto v = b->view<R>(0.0);
-            launch_fin<R>(b, 0.0, 1);
-            launch_loglik<R>(b, 0.0, true);
-        };
-        if (precision == VBX_PREC_FP64) go(double{}); else go(float{});
+        plan_iteration(b);
+        with_precision(precision, [&](auto r) {
+            launch_fin<decltype(r)>(b, 0.0, 1);
+            launch_loglik<decltype(r)>(b, 0.0, true);
+        });
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) {
@@ -283,8 +281,8 @@ int vbx_loglik(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, c
     }
     if (rc == VBX_OK) {
         // add the per-frame constant Fa*G_t of VBx.py:87,97 on the host (f64)
-        auto fetch = [&](auto tag) -> int {
-            using R = decltype(tag);
+        rc = with_precision(precision, [&](auto r) -> int {
+            using R = decltype(r);
             std::vector<R> raw(cells);
             HIPCHK(ctx, hipMemcpy(raw.data(), b->d_lraw, sizeof(R) * cells, hipMemcpyDeviceToHost));
             for (int64_t t = 0; t < T; ++t) {
@@ -294,8 +292,7 @@ int vbx_loglik(vbx_ctx* ctx, int64_t T, int32_t S, int32_t D, const double* X, c
                 for (int s = 0; s < S; ++s) log_p[(size_t)t * S + s] = (double)raw[(size_t)t * b->Sp + s] + Fa * G;
             }
             return VBX_OK;
-        };
-        rc = precision == VBX_PREC_FP64 ? fetch(double{}) : fetch(float{});
+        });
     }
     vbx_batch_destroy(b);
     return rc;
@@ -367,8 +364,7 @@ int vbx_score_posteriors(vbx_ctx* ctx, int64_t T, int32_t S, const double* gamma
     for (int64_t t = 0; t < T; ++t)
         if (ref[t] < 0 || ref[t] >= n_ref) FAIL(ctx, VBX_ERR_INVALID, "vbx_score_posteriors: label %d of frame %lld outside [0, %d)", ref[t], (long long)t, n_ref);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return precision == VBX_PREC_FP64 ? score_posteriors_impl<double>(ctx, T, S, gamma, ref, n_ref, conf)
-                                      : score_posteriors_impl<float>(ctx, T, S, gamma, ref, n_ref, conf);
+    return with_precision(precision, [&](auto r) { return score_posteriors_impl<decltype(r)>(ctx, T, S, gamma, ref, n_ref, conf); });
 }
 
 }  // extern "C"
