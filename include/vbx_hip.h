@@ -403,6 +403,28 @@ int vbx_gather_rows(const void* buf, int64_t len, const int64_t* offsets, int64_
 int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, double* llr);
 int vbx_scores_destroy(vbx_scores* sc);
 
+/* ---- the Kaldi-recipe PLDA similarity, the alternative to cos_similarity for the AHC stage (vbx_plda_score.hpp) -------
+ * kaldi_ivector_plda_scoring_dense   diarization_lib.py:59-93
+ * PLDA_scoring_in_LDA_space          diarization_lib.py:34-56
+ * The D x D eigen-decompositions of the reference stay with the caller; these entry points do what is O(T) and O(T^2).
+ *
+ * Covariance np.cov(x.T, bias=True) of the rows x [T][D] (D <= 1024): mean [D], cov [D][D] to the host.  Summed over
+ * fixed chunks of rows in a fixed order: the same rows give the same bits on every run and from either entry point. */
+int vbx_plda_covariance(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, double* mean, double* cov);
+/* ... of the resident rows [row0, row0 + T) of xproj (D = Dl). */
+int vbx_plda_covariance_resident(vbx_ctx* ctx, vbx_xvectors* xv, int64_t row0, int64_t T, double* mean, double* cov);
+/* Dense T x T PLDA scores of the rows x [T][D] as a vbx_scores, everything calibration and linkage take:
+ *   y = (x - mu) proj,  y *= sqrt(d / sum_k y_k^2 / (acvar_k + 1)),  S = PLDA_scoring_in_LDA_space(y, y, acvar)
+ * mu [D], proj [D][d] (the reference's PCA . wccn), acvar [d] >= 0, 1 <= d <= 256.  S is symmetric to the last bit. */
+int vbx_plda_scores(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, int32_t d, const double* mu, const double* proj,
+                    const double* acvar, vbx_scores** out);
+/* ... of the resident rows [row0, row0 + T) of xproj (D = Dl): nothing but the model is uploaded. */
+int vbx_plda_scores_resident(vbx_ctx* ctx, vbx_xvectors* xv, int64_t row0, int64_t T, int32_t d, const double* mu,
+                             const double* proj, const double* acvar, vbx_scores** out);
+/* PLDA_scoring_in_LDA_space(Fe, Ft, diagAC): Fe [N][D], Ft [M][D], diagAC [D] -> out [N][M] on the host. */
+int vbx_plda_score_lda(vbx_ctx* ctx, int64_t N, int64_t M, int32_t D, const double* Fe, const double* Ft,
+                       const double* diagAC, double* out);
+
 /* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then

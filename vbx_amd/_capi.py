@@ -25,6 +25,8 @@ STREAM_LOADS_NAMES = {'auto': STREAM_LOADS_AUTO, 'on': STREAM_LOADS_ON, 'off': S
 K_NAMES = ['prep', 'mstep_acc', 'mstep_fin', 'loglik', 'fb', 'fb_aux', 'post', 'iter_fin', 'chunk_loglik',
            'chunk_post']
 MAX_SPEAKERS = 16384
+PLDA_COV_CHUNK = 512         # rows of one partial of the PLDA covariance (vbx_plda_score.hpp: kCovChunk)
+PLDA_MAX_DIM = 256           # dimensions the PLDA projection kernel keeps (vbx_plda_score.hpp: 16 * kPldaMaxTiles)
 MAX_REF_LABELS = 64          # labels a recording can be scored against on the device (vbx_batch_set_reference)
 
 ABI_SYMBOLS = [
@@ -48,6 +50,7 @@ ABI_SYMBOLS = [
     'vbx_resnet_conv_ragged', 'vbx_resnet_stem_ragged', 'vbx_resnet_pool_ragged',
     'vbx_fbank_run_raw', 'vbx_fbank_get_signal', 'vbx_fbank_dither_time',
     'vbx_batch_set_reference', 'vbx_batch_get_scores', 'vbx_score_posteriors',
+    'vbx_plda_covariance', 'vbx_plda_covariance_resident', 'vbx_plda_scores', 'vbx_plda_scores_resident', 'vbx_plda_score_lda',
 ]
 
 
@@ -164,6 +167,11 @@ def load():
     lib.vbx_batch_set_reference.argtypes = [vp, C.c_int, vp, i32]
     lib.vbx_batch_get_scores.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
     lib.vbx_score_posteriors.argtypes = [vp, i64, i32, vp, vp, i32, C.c_int, vp]
+    lib.vbx_plda_covariance.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.vbx_plda_covariance_resident.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.vbx_plda_scores.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp, C.POINTER(vp)]
+    lib.vbx_plda_scores_resident.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, C.POINTER(vp)]
+    lib.vbx_plda_score_lda.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -784,6 +792,28 @@ class Scores:
         return cls(ctx, h)
 
     @classmethod
+    def plda(cls, ctx: Context, x, mu, proj, acvar):
+        """Dense PLDA scores (kaldi_ivector_plda_scoring_dense after its host part) of the rows ``x`` [T][D]: ``proj``
+        [D][d] is the reference's ``PCA . wccn``, ``acvar`` [d] the across-class variances.  The matrix is symmetric to the
+        last bit."""
+        x, mu, proj, acvar = _f64(x), _f64(mu), _f64(proj), _f64(acvar)
+        assert x.ndim == 2 and proj.shape == (x.shape[1], acvar.size) and mu.shape == (x.shape[1],)
+        h = C.c_void_p()
+        ctx.check(ctx._lib.vbx_plda_scores(ctx._h, x.shape[0], x.shape[1], _ptr(x), acvar.size, _ptr(mu), _ptr(proj),
+                                           _ptr(acvar), C.byref(h)), 'vbx_plda_scores')
+        return cls(ctx, h)
+
+    @classmethod
+    def plda_resident(cls, ctx: Context, xv: 'XVectors', row0, T, mu, proj, acvar):
+        """Dense PLDA scores of rows [row0, row0 + T) of the projected x-vectors already in HBM."""
+        mu, proj, acvar = _f64(mu), _f64(proj), _f64(acvar)
+        assert proj.shape == (xv.dl, acvar.size) and mu.shape == (xv.dl,)
+        h = C.c_void_p()
+        ctx.check(ctx._lib.vbx_plda_scores_resident(ctx._h, xv._h, int(row0), int(T), acvar.size, _ptr(mu), _ptr(proj),
+                                                    _ptr(acvar), C.byref(h)), 'vbx_plda_scores_resident')
+        return cls(ctx, h)
+
+    @classmethod
     def upload(cls, ctx: Context, s):
         s = _f64(s).reshape(-1)
         h = C.c_void_p()
@@ -1095,6 +1125,33 @@ class Batch:
 
 
 _default_ctx = {}
+
+
+def plda_covariance(ctx: Context, x):
+    """(mean [D], np.cov(x.T, bias=True) [D][D]) of the rows ``x`` [T][D], summed on the device in a fixed order."""
+    x = _f64(x)
+    assert x.ndim == 2
+    mean, cov = np.empty(x.shape[1]), np.empty((x.shape[1], x.shape[1]))
+    ctx.check(ctx._lib.vbx_plda_covariance(ctx._h, x.shape[0], x.shape[1], _ptr(x), _ptr(mean), _ptr(cov)), 'vbx_plda_covariance')
+    return mean, cov
+
+
+def plda_covariance_resident(ctx: Context, xv: 'XVectors', row0, T):
+    """plda_covariance of rows [row0, row0 + T) of the projected x-vectors already in HBM: the same bits."""
+    mean, cov = np.empty(xv.dl), np.empty((xv.dl, xv.dl))
+    ctx.check(ctx._lib.vbx_plda_covariance_resident(ctx._h, xv._h, int(row0), int(T), _ptr(mean), _ptr(cov)),
+              'vbx_plda_covariance_resident')
+    return mean, cov
+
+
+def plda_score_lda(ctx: Context, Fe, Ft, diagAC):
+    """PLDA_scoring_in_LDA_space(Fe, Ft, diagAC) -> [N][M] (diarization_lib.py:34-56)."""
+    Fe, Ft, diagAC = _f64(Fe), _f64(Ft), _f64(diagAC)
+    assert Fe.ndim == 2 and Ft.ndim == 2 and Fe.shape[1] == Ft.shape[1] == diagAC.size
+    out = np.empty((Fe.shape[0], Ft.shape[0]))
+    ctx.check(ctx._lib.vbx_plda_score_lda(ctx._h, Fe.shape[0], Ft.shape[0], Fe.shape[1], _ptr(Fe), _ptr(Ft), _ptr(diagAC),
+                                          _ptr(out)), 'vbx_plda_score_lda')
+    return out
 
 
 def linkage_variant():

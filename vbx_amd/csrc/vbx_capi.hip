@@ -15,6 +15,7 @@
 #include "vbx_score.hpp"
 #include "vbx_linkage.hpp"
 #include "vbx_ahc.hpp"
+#include "vbx_plda_score.hpp"
 #include "vbx_frontend.hpp"
 #include "vbx_fbank.hpp"
 #include "vbx_resnet.hpp"

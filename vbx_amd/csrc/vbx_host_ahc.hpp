@@ -469,4 +469,196 @@ int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, 
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------
+// Kaldi-recipe PLDA similarity (diarization_lib.py:34-93; kernels in vbx_plda_score.hpp)
+// ---------------------------------------------------------------------------------------
+
+// diarization_lib.py:49-55 for one across-class variance
+struct PldaTerms { double Lambda, Gamma, ld; };
+static PldaTerms plda_terms(double ac) {
+    const double iTC = 1.0 / (1.0 + ac), iWC2AC = 1.0 / (1.0 + 2.0 * ac);
+    return PldaTerms{-0.5 * (iWC2AC - 1.0), -0.25 * (iWC2AC + 1.0 - 2.0 * iTC), std::log(1.0 + 2.0 * ac) - 2.0 * std::log(1.0 + ac)};
+}
+
+// x: host rows [T][D] (uploaded; ld == D) or, with on_device, rows in HBM with leading dimension ld
+static int plda_covariance_impl(vbx_ctx* ctx, int64_t T, int32_t D, int ld, const double* x, bool on_device, double* mean,
+                                double* cov) {
+    if (D > 1024) FAIL(ctx, VBX_ERR_UNSUPPORTED, "PLDA covariance: D=%d, at most 1024 dimensions", (int)D);
+    if (T > 200000) FAIL(ctx, VBX_ERR_UNSUPPORTED, "PLDA covariance: T=%lld rows, at most 200000", (long long)T);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int Dp = round_up(D, 16), nchunks = (int)((T + vbx::kCovChunk - 1) / vbx::kCovChunk);
+    double *d_x = nullptr, *d_sum = nullptr, *d_mean = nullptr, *d_part = nullptr, *d_cov = nullptr;
+    int rc = on_device ? VBX_OK : dmalloc(ctx, &d_x, (size_t)T * D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_sum, (size_t)nchunks * D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_mean, (size_t)D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)nchunks * Dp * Dp);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_cov, (size_t)D * D);
+    if (rc == VBX_OK) {
+        hipStream_t st = ctx->stream;
+        hipError_t e = hipSuccess;
+        if (!on_device) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            const double* rows = on_device ? x : d_x;
+            const unsigned nb = (unsigned)((D + 63) / 64);
+            hipLaunchKernelGGL(vbx::cov_colsum_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, rows, (long long)T, (int)D, ld, d_sum);
+            hipLaunchKernelGGL(vbx::cov_mean_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, d_sum, nchunks, (long long)T, (int)D, d_mean);
+            hipLaunchKernelGGL(vbx::cov_partial_kernel, dim3(nb, nb, (unsigned)nchunks), dim3(256), 0, st, rows, d_mean, (long long)T, (int)D, ld, Dp, d_part);
+            hipLaunchKernelGGL(vbx::cov_finish_kernel, dim3((unsigned)((D * D + 255) / 256)), dim3(256), 0, st, d_part, nchunks, (long long)T, (int)D, Dp, d_cov);
+            e = hipMemcpyAsync(mean, d_mean, sizeof(double) * (size_t)D, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(cov, d_cov, sizeof(double) * (size_t)D * D, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) {
+            ctx->err = std::string("PLDA covariance kernels failed: ") + hipGetErrorString(e);
+            rc = VBX_ERR_HIP;
+        }
+    }
+    for (double* p : {d_x, d_sum, d_mean, d_part, d_cov}) ctx_free(ctx, p);
+    return rc;
+}
+
+int vbx_plda_covariance(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, double* mean, double* cov) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!x || !mean || !cov || T <= 0 || D <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_plda_covariance: bad argument");
+    return plda_covariance_impl(ctx, T, D, D, x, false, mean, cov);
+}
+
+int vbx_plda_covariance_resident(vbx_ctx* ctx, vbx_xvectors* xv, int64_t row0, int64_t T, double* mean, double* cov) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!xv || !mean || !cov || T <= 0 || row0 < 0 || row0 + T > xv->n || xv->ctx->device != ctx->device)
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_plda_covariance_resident: bad argument");
+    const int ld = round_up(xv->Dl, 4);
+    return plda_covariance_impl(ctx, T, xv->Dl, ld, xv->d_xproj + row0 * ld, true, mean, cov);
+}
+
+static int plda_scores_impl(vbx_ctx* ctx, int64_t T, int32_t D, int ld, const double* x, bool on_device, int32_t d,
+                            const double* mu, const double* proj, const double* acvar, vbx_scores** out) {
+    *out = nullptr;
+    if (T > 200000) FAIL(ctx, VBX_ERR_UNSUPPORTED, "T=%lld: the T x T score matrix would not fit the device", (long long)T);
+    if (d > 16 * vbx::kPldaMaxTiles) FAIL(ctx, VBX_ERR_UNSUPPORTED, "PLDA scores: d=%d, at most %d dimensions", (int)d, 16 * vbx::kPldaMaxTiles);
+    const int Dk = round_up(D, 4), dp = round_up(d, 16);
+    // one packed model block: mu [D] | proj padded [Dk][dp] | w [dp] | sqrt(Lambda) [dp] | Gamma [dp]
+    const size_t o_proj = (size_t)D, o_w = o_proj + (size_t)Dk * dp, o_sl = o_w + dp, o_gam = o_sl + dp, n_model = o_gam + dp;
+    std::vector<double> model(n_model, 0.0);
+    double kconst = 0.0;
+    for (int j = 0; j < D; ++j) {
+        model[j] = mu[j];
+        for (int k = 0; k < d; ++k) model[o_proj + (size_t)j * dp + k] = proj[(size_t)j * d + k];
+    }
+    for (int k = 0; k < d; ++k) {
+        const PldaTerms t = plda_terms(acvar[k]);
+        if (!(acvar[k] >= 0.0) || !(t.Lambda >= 0.0)) FAIL(ctx, VBX_ERR_INVALID, "PLDA scores: acvar[%d] = %g is not a variance", k, acvar[k]);
+        model[o_w + k] = 1.0 / (acvar[k] + 1.0);
+        model[o_sl + k] = std::sqrt(t.Lambda);
+        model[o_gam + k] = t.Gamma;
+        kconst += t.ld;
+    }
+    kconst *= -0.5;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    double *d_x = nullptr, *d_model = nullptr, *d_a = nullptr, *d_g = nullptr;
+    vbx_scores* sc = new vbx_scores();
+    sc->ctx = ctx;
+    sc->n = (long long)T * T;
+    int rc = on_device ? VBX_OK : dmalloc(ctx, &d_x, (size_t)T * D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_model, n_model);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_a, (size_t)T * dp);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_g, (size_t)T);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &sc->d_s, (size_t)sc->n);
+    if (rc == VBX_OK) {
+        hipStream_t st = ctx->stream;
+        hipError_t e = hipSuccess;
+        if (!on_device) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_model, model.data(), sizeof(double) * n_model, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(vbx::plda_project_kernel, dim3((unsigned)((T + 15) / 16)), dim3(64), 0, st, on_device ? x : d_x,
+                               (long long)T, (int)D, ld, d_model, d_model + o_proj, (int)d, dp, d_model + o_w, d_model + o_sl,
+                               d_model + o_gam, d_a, d_g);
+            const unsigned nb = (unsigned)((T + 63) / 64);
+            hipLaunchKernelGGL(vbx::plda_score_gemm_kernel, dim3(nb, nb), dim3(256), 0, st, d_a, d_a, d_g, d_g, kconst, sc->d_s,
+                               (long long)T, (long long)T, dp);
+            e = hipStreamSynchronize(st);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) {
+            ctx->err = std::string("PLDA score kernels failed: ") + hipGetErrorString(e);
+            rc = VBX_ERR_HIP;
+        }
+    }
+    for (double* p : {d_x, d_model, d_a, d_g}) ctx_free(ctx, p);
+    if (rc != VBX_OK) {
+        vbx_scores_destroy(sc);
+        return rc;
+    }
+    *out = sc;
+    return VBX_OK;
+}
+
+int vbx_plda_scores(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, int32_t d, const double* mu, const double* proj,
+                    const double* acvar, vbx_scores** out) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!x || !mu || !proj || !acvar || !out || T <= 0 || D <= 0 || d <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_plda_scores: bad argument");
+    return plda_scores_impl(ctx, T, D, D, x, false, d, mu, proj, acvar, out);
+}
+
+int vbx_plda_scores_resident(vbx_ctx* ctx, vbx_xvectors* xv, int64_t row0, int64_t T, int32_t d, const double* mu,
+                             const double* proj, const double* acvar, vbx_scores** out) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!xv || !mu || !proj || !acvar || !out || T <= 0 || d <= 0 || row0 < 0 || row0 + T > xv->n || xv->ctx->device != ctx->device)
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_plda_scores_resident: bad argument");
+    const int ld = round_up(xv->Dl, 4);               // (the padding columns are never read: the kernels stop at Dl)
+    return plda_scores_impl(ctx, T, xv->Dl, ld, xv->d_xproj + row0 * ld, true, d, mu, proj, acvar, out);
+}
+
+int vbx_plda_score_lda(vbx_ctx* ctx, int64_t N, int64_t M, int32_t D, const double* Fe, const double* Ft, const double* diagAC,
+                       double* out) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!Fe || !Ft || !diagAC || !out || N <= 0 || M <= 0 || D <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_plda_score_lda: bad argument");
+    if (N > 200000 || M > 200000) FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_plda_score_lda: %lld x %lld scores would not fit the device", (long long)N, (long long)M);
+    const int dp = round_up(D, 16);
+    std::vector<double> terms(2 * (size_t)D);                  // Lambda [D] | Gamma [D]
+    double kconst = 0.0;
+    for (int k = 0; k < D; ++k) {
+        const PldaTerms t = plda_terms(diagAC[k]);
+        terms[k] = t.Lambda;
+        terms[(size_t)D + k] = t.Gamma;
+        kconst += t.ld;
+    }
+    kconst *= -0.5;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    double *d_fe = nullptr, *d_ft = nullptr, *d_terms = nullptr, *d_a = nullptr, *d_b = nullptr, *d_r = nullptr, *d_c = nullptr,
+           *d_s = nullptr;
+    int rc = dmalloc(ctx, &d_fe, (size_t)N * D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_ft, (size_t)M * D);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_terms, terms.size());
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_a, (size_t)N * dp);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_b, (size_t)M * dp);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_r, (size_t)N);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_c, (size_t)M);
+    if (rc == VBX_OK) rc = dmalloc(ctx, &d_s, (size_t)N * (size_t)M);
+    if (rc == VBX_OK) {
+        hipStream_t st = ctx->stream;
+        hipError_t e = hipMemcpyAsync(d_fe, Fe, sizeof(double) * (size_t)N * D, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ft, Ft, sizeof(double) * (size_t)M * D, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_terms, terms.data(), sizeof(double) * terms.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(vbx::plda_lda_rows_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, d_fe, (long long)N, (int)D,
+                               (const double*)d_terms, (const double*)(d_terms + D), dp, d_a, d_r);
+            hipLaunchKernelGGL(vbx::plda_lda_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, d_ft, (long long)M, (int)D,
+                               (const double*)nullptr, (const double*)(d_terms + D), dp, d_b, d_c);
+            hipLaunchKernelGGL(vbx::plda_score_gemm_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, st,
+                               d_a, d_b, d_r, d_c, kconst, d_s, (long long)N, (long long)M, dp);
+            e = hipMemcpyAsync(out, d_s, sizeof(double) * (size_t)N * (size_t)M, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) {
+            ctx->err = std::string("PLDA LDA-space score kernels failed: ") + hipGetErrorString(e);
+            rc = VBX_ERR_HIP;
+        }
+    }
+    for (double* p : {d_fe, d_ft, d_terms, d_a, d_b, d_r, d_c, d_s}) ctx_free(ctx, p);
+    return rc;
+}
+
 }  // extern "C"

@@ -70,7 +70,8 @@ def load_models(xvec_transform, plda_file):
         W = np.linalg.inv(plda_tr.T.dot(plda_tr))
         B = np.linalg.inv((plda_tr.T / plda_psi).dot(plda_tr))
         acvar, wccn = eigh(B, W)
-    return dict(mean1=mean1, mean2=mean2, lda=lda, plda_mu=plda_mu, plda_psi=acvar[::-1], plda_tr=wccn.T[::-1])
+    return dict(mean1=mean1, mean2=mean2, lda=lda, plda_mu=plda_mu, plda_psi=acvar[::-1], plda_tr=wccn.T[::-1],
+                kaldi_plda=(plda_mu, plda_tr, plda_psi))          # the raw model: what --ahc-scores plda scores under
 
 
 def cut_linkage(lin_mat, thr, threshold):
@@ -98,7 +99,8 @@ class DeviceStages:
 
     project   every x-vector of this rank goes up ONCE; the projections of vbhmm.py:125-129 and the PLDA projection of
               vbhmm.py:153 run on the device for all recordings together and stay resident (vbx_xvectors)
-    ahc       per recording: cosine-similarity matrix of its resident rows, two-Gaussian calibration and the
+    ahc       per recording: cosine-similarity matrix of its resident rows (or, ``ahc_scores='plda'``, their dense PLDA
+              scores under the raw Kaldi model: diarization_lib.py:59-93), two-Gaussian calibration and the
               average-linkage nearest-neighbour chain, all on the T x T matrix where it lies in HBM (vbhmm.py:135-141);
               the T - 1 merges come back and are cut on the host (vbhmm.py:142-146).  Every driver thread has its own
               context (device stream), so the chains of several recordings run side by side on different CUs
@@ -130,6 +132,8 @@ class DeviceStages:
         self.row0 = np.concatenate([[0], np.cumsum(self.T)]).astype(np.int64)
         self.Phi = np.ascontiguousarray(models['plda_psi'][:lda_dim])
         self.lda_dim = lda_dim
+        self.kaldi_plda = models.get('kaldi_plda')
+        self._plda_full = None
         if not recordings:
             return
         x = np.concatenate([np.asarray(r[2]) for r in recordings])
@@ -141,9 +145,28 @@ class DeviceStages:
     # the host routine needs ~3 ns per matrix entry plus the condensed matrix over PCIe (3 ms at T = 1025): the device from ~600
     DEVICE_LINKAGE_FROM = 600
 
-    def ahc(self, k, threshold):
+    def _plda_scores(self, k, target_energy):
+        """Dense PLDA scores of the resident rows of recording k (kaldi_ivector_plda_scoring_dense)."""
+        from . import diarization_lib
+        if self.kaldi_plda is None:
+            raise ValueError("ahc_scores='plda' needs the raw PLDA model: load_models()['kaldi_plda']")
+        if target_energy >= 1.0 and self._plda_full is None:         # all dimensions kept: one projection for every recording
+            self._plda_full = diarization_lib.plda_projection(self.kaldi_plda, None)     # (pure: a race computes it twice)
+        sc, _pca_dim = diarization_lib.plda_dense_scores(self._thread_ctx(), self.kaldi_plda,
+                                                         resident=(self.xv, self.row0[k], self.T[k]),
+                                                         target_energy=target_energy, full_projection=self._plda_full)
+        return sc
+
+    def ahc(self, k, threshold, ahc_scores='cos', target_energy=1.0):
         """-> (AHC labels of recording k, calibrated threshold)."""
-        sc = self._capi.Scores.cos_similarity_resident(self._thread_ctx(), self.xv, self.row0[k], self.T[k])
+        if ahc_scores == 'plda':
+            if self.T[k] == 1:                        # nothing to score: one x-vector is one cluster
+                return np.zeros(1, dtype=np.int64), float('nan')
+            sc = self._plda_scores(k, target_energy)
+        elif ahc_scores == 'cos':
+            sc = self._capi.Scores.cos_similarity_resident(self._thread_ctx(), self.xv, self.row0[k], self.T[k])
+        else:
+            raise ValueError(f"ahc_scores must be 'cos' or 'plda', not {ahc_scores!r}")
         try:
             thr, _ = sc.two_gmm_calib(20, want_llr=False)
             if self.T[k] >= self.DEVICE_LINKAGE_FROM and self._capi.linkage_variant() == 'scipy':
@@ -276,10 +299,11 @@ def _write_rttm_files(args, file_name, st, segs_dict):
             write_rttm(fp, file_name, out_labels2, starts, ends)
 
 
-def diarize(args, stages=None, log=print):
+def diarize(args, stages=None, log=print, ahc_scores=None):
     """The whole archive.  ``stages`` defaults to ``DeviceStages()`` (the CPU test-suite injects an object with the same
     four methods built on its checkers).  Returns ``({recording: dict(labels1st, labels2nd, n_iters, thr)}, timing)``
-    for the recordings of this rank.
+    for the recordings of this rank.  ``ahc_scores`` ('cos' | 'plda', default: ``args.ahc_scores``, 'cos' where absent)
+    names the similarity of the AHC stage; 'plda' uses ``args.target_energy``.
 
     A recording the device path cannot take (more than ``VBX_MAX_SPEAKERS`` = 16 384 AHC clusters, or one whose batch
     fails) does not take the archive down with it: every other recording is diarized and written, then a
@@ -287,6 +311,11 @@ def diarize(args, stages=None, log=print):
     from .batch import shard_recordings
     from ._capi import MAX_SPEAKERS, VbxError
     assert 0 <= args.loopP <= 1, f'Expecting loopP between 0 and 1, got {args.loopP} instead.'
+    if ahc_scores is None:
+        ahc_scores = getattr(args, 'ahc_scores', 'cos')
+    if ahc_scores not in ('cos', 'plda'):
+        raise ValueError(f"ahc_scores must be 'cos' or 'plda', not {ahc_scores!r}")
+    ahc_kw = dict(ahc_scores='plda', target_energy=getattr(args, 'target_energy', 1.0)) if ahc_scores == 'plda' else {}
     t_start = time.perf_counter()
     segs_dict = read_xvector_timing_dict(args.segments_file)
     models = load_models(args.xvec_transform, args.plda_file)
@@ -313,7 +342,7 @@ def diarize(args, stages=None, log=print):
 
         def prepare(k):
             file_name, seg_names, _ = recordings[k]
-            labels1st, thr = stages.ahc(k, args.threshold)
+            labels1st, thr = stages.ahc(k, args.threshold, **ahc_kw)
             st = dict(labels1st=labels1st, labels2nd=None, thr=thr, n_iters=0, seg_names=seg_names)
             if not want_vb:
                 _write_rttm_files(args, file_name, st, segs_dict)        # AHC only: the result is final
@@ -397,7 +426,11 @@ def build_parser():
     p.add_argument('--Fb', required=True, type=float, help='Parameter of VB-HMM (see VBx.VBx)')
     p.add_argument('--loopP', required=True, type=float, help='Parameter of VB-HMM (see VBx.VBx)')
     p.add_argument('--target-energy', required=False, type=float, default=1.0,
-                   help='accepted for compatibility (only used by the PLDA-scoring AHC the driver does not call)')
+                   help='Parameter affecting AHC if the similarity matrix is obtained with PLDA (--ahc-scores plda): the '
+                        'share of the x-vectors\' variability the PCA before the scoring keeps; >= 1 keeps every dimension')
+    p.add_argument('--ahc-scores', required=False, type=str, default='cos', choices=['cos', 'plda'],
+                   help='similarity of the AHC stage: cosine (what the reference driver computes) or the Kaldi-recipe '
+                        'PLDA scores of diarization_lib.kaldi_ivector_plda_scoring_dense')
     p.add_argument('--init-smoothing', required=False, type=float, default=5.0,
                    help='smoothing of the hard AHC labels into the initial soft assignments')
     p.add_argument('--output-2nd', required=False, type=bool, default=False,

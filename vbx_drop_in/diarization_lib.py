@@ -1,6 +1,7 @@
 """Drop-in for the reference's ``VBx/diarization_lib.py``: every name of the reference module, with
 ``cos_similarity`` and ``twoGMMcalib_lin`` (the T*T score stage of the AHC initialisation,
-vbhmm.py:135-138) replaced by the MI355X implementations.
+vbhmm.py:135-138) and the Kaldi-recipe PLDA scoring (``PLDA_scoring_in_LDA_space``, ``kaldi_ivector_plda_scoring_dense``; the
+reference driver never calls them) replaced by the MI355X implementations.
 
 Put this directory in front of the reference's ``VBx/`` directory on ``sys.path`` (tools/run_vbhmm.py
 does); the reference module is then loaded from the next ``diarization_lib.py`` found on the path.
@@ -27,4 +28,5 @@ _ref = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(_ref)
 globals().update({k: v for k, v in vars(_ref).items() if not k.startswith('__')})
 
-from vbx_amd.diarization_lib import cos_similarity, twoGMMcalib_lin  # noqa: E402,F401
+from vbx_amd.diarization_lib import (cos_similarity, twoGMMcalib_lin,  # noqa: E402,F401
+                                     PLDA_scoring_in_LDA_space, kaldi_ivector_plda_scoring_dense)
