@@ -336,6 +336,17 @@ typedef struct vbx_xvectors vbx_xvectors;
 int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32_t fea_dim, const void* x, int x_dtype,
                          const double* mean1, const double* lda, const double* mean2, const double* plda_mu,
                          const double* plda_tr, vbx_xvectors** out);
+/* The same for x-vectors that already lie in HBM (the network left them there: vbx_resnet_run with out_on_device):
+ * d_x [n_src][Din] f32 on ctx's device; row i of the result is source row rows_host[i], i < n (host array, strictly
+ * increasing, every index < n_src; NULL: every row in order, n == n_src).  Nothing but the n indices and the model goes
+ * up; the first kernel reads its row through the index, the rest is vbx_xvectors_project's chain, so the result has the
+ * bits that entry gives from a host copy of the kept rows.  Runs on ctx's stream and ends with one synchronize. */
+int vbx_xvectors_project_device(vbx_ctx* ctx, int64_t n_src, int32_t Din, int32_t Dl, int32_t fea_dim, const float* d_x,
+                                int64_t n, const int64_t* rows_host, const double* mean1, const double* lda,
+                                const double* mean2, const double* plda_mu, const double* plda_tr, vbx_xvectors** out);
+/* flags_host[t] = 1 where row t of d_x [n][D] f32 (device memory of ctx's device) holds a NaN, else 0 -- predict.py:185's
+ * np.isnan(embedding).any(), an infinity is not flagged.  The n flags are all that comes back to the host. */
+int vbx_rows_nan_flags(vbx_ctx* ctx, const float* d_x, int64_t n, int32_t D, int32_t* flags_host);
 /* rows [row0, row0 + nrows) of xproj (which = 0, [nrows][Dl]) or fea (which = 1, [nrows][fea_dim]) to the host. */
 int vbx_xvectors_get(vbx_xvectors* xv, int which, int64_t row0, int64_t nrows, double* out);
 int vbx_xvectors_destroy(vbx_xvectors* xv);

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     'vbx_fbank_run_raw', 'vbx_fbank_get_signal', 'vbx_fbank_dither_time',
     'vbx_batch_set_reference', 'vbx_batch_get_scores', 'vbx_score_posteriors',
     'vbx_plda_covariance', 'vbx_plda_covariance_resident', 'vbx_plda_scores', 'vbx_plda_scores_resident', 'vbx_plda_score_lda',
+    'vbx_xvectors_project_device', 'vbx_rows_nan_flags',
 ]
 
 
@@ -172,6 +173,8 @@ def load():
     lib.vbx_plda_scores.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp, C.POINTER(vp)]
     lib.vbx_plda_scores_resident.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, C.POINTER(vp)]
     lib.vbx_plda_score_lda.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
+    lib.vbx_xvectors_project_device.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.vbx_rows_nan_flags.argtypes = [vp, vp, i64, i32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -370,11 +373,34 @@ class XVectors:
                   'vbx_xvectors_project')
         self._h, self.n, self.dl, self.fea_dim = h, n, dl, int(fea_dim)
 
+    @classmethod
+    def from_device(cls, ctx: Context, x_ptr, n_src, Din, rows, mean1, lda, mean2, plda_mu, plda_tr, fea_dim):
+        """The same from x-vectors that already lie in HBM (vbx_xvectors_project_device): f32 [n_src][Din] at the device
+        address ``x_ptr``, of which the rows ``rows`` are kept (strictly increasing indices; None: all of them).  Only the
+        indices go up; the result has the bits ``XVectors(ctx, x[rows], ...)`` gives from a host copy."""
+        self = cls.__new__(cls)
+        self.ctx, self._lib, self._h = ctx, ctx._lib, None
+        mean1, lda, mean2, plda_mu, plda_tr = _f64(mean1), _f64(lda), _f64(mean2), _f64(plda_mu), _f64(plda_tr)
+        n_src, din = int(n_src), int(Din)
+        dl = lda.shape[1]
+        assert lda.shape == (din, dl) and mean1.shape == (din,) and mean2.shape == (dl,) and plda_mu.shape == (dl,)
+        assert plda_tr.shape == (dl, dl)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = n_src if rows is None else rows.shape[0]
+        h = C.c_void_p()
+        ctx.check(self._lib.vbx_xvectors_project_device(ctx._h, n_src, din, dl, int(fea_dim), C.c_void_p(x_ptr), n, _ptr(rows),
+                                                        _ptr(mean1), _ptr(lda), _ptr(mean2), _ptr(plda_mu), _ptr(plda_tr),
+                                                        C.byref(h)), 'vbx_xvectors_project_device')
+        self._h, self.n, self.dl, self.fea_dim = h, n, dl, int(fea_dim)
+        return self
+
     def get(self, which, row0=0, nrows=None):
-        """rows of 'xproj' or 'fea' as a float64 array (tests; the driver never needs them on the host)."""
+        """rows of 'xproj' (or 0) or 'fea' (or 1) as a float64 array (tests; the driver never needs them on the host)."""
+        xproj = which == 'xproj' or (which is not None and not isinstance(which, str) and int(which) == 0)
         nrows = self.n - row0 if nrows is None else nrows
-        out = np.empty((nrows, self.dl if which == 'xproj' else self.fea_dim))
-        self.ctx.check(self._lib.vbx_xvectors_get(self._h, 0 if which == 'xproj' else 1, int(row0), int(nrows), _ptr(out)),
+        out = np.empty((nrows, self.dl if xproj else self.fea_dim))
+        self.ctx.check(self._lib.vbx_xvectors_get(self._h, 0 if xproj else 1, int(row0), int(nrows), _ptr(out)),
                        'vbx_xvectors_get')
         return out
 
@@ -1125,6 +1151,17 @@ class Batch:
 
 
 _default_ctx = {}
+
+
+def nan_rows(ctx: Context, x_ptr, n, D) -> np.ndarray:
+    """bool [n]: which rows of the f32 array [n][D] at the device address ``x_ptr`` hold a NaN (vbx_rows_nan_flags) --
+    ``np.isnan(x).any(1)`` with only the n flags coming back."""
+    n = int(n)
+    if n == 0:
+        return np.zeros(0, dtype=bool)
+    flags = np.empty(max(n, 0), dtype=np.int32)
+    ctx.check(ctx._lib.vbx_rows_nan_flags(ctx._h, C.c_void_p(x_ptr), n, int(D), _ptr(flags)), 'vbx_rows_nan_flags')
+    return flags != 0
 
 
 def plda_covariance(ctx: Context, x):

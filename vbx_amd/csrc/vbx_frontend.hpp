@@ -6,6 +6,7 @@
 //                                                                                 product: - plda_mu plda_tr^T)
 //   vbhmm.py:150-152   qinit = softmax(init_smoothing * onehot(AHC labels))       qinit_kernel, straight into gamma
 //   vbhmm.py:160-162   first / second speaker = argsort(-q, axis=1)[:, 0 / 1]     top2_kernel
+//   predict.py:185     np.isnan(embedding).any() per x-vector                     rows_nan_flags
 //
 // The products are small (n x 256 x 128 and n x 128 x 128 for n ~ 1e5 x-vectors of an archive: 9 GFLOP) and run on
 // v_mfma_f64_16x16x4; their point is that nothing but the raw x-vectors goes up and nothing but labels comes down.
@@ -14,26 +15,44 @@
 
 namespace vbx {
 
-// y[t][0..Kp) = (x[t] - mean) / |x[t] - mean|, zero-padded to Kp; x has row stride ldx.  One wavefront per row.
-// mean == nullptr: no centring; in place (y == x, ldx == Kp) is allowed: a row is read completely before it is written.
+// y[t][0..Kp) = (x[src] - mean) / |x[src] - mean|, zero-padded to Kp; x has row stride ldx.  One wavefront per row.
+// src = rows[t] (the kept rows of x-vectors that already lie in HBM: vbx_xvectors_project_device), or t where rows == nullptr.
+// mean == nullptr: no centring; in place (y == x, ldx == Kp, rows == nullptr) is allowed: a row is read completely before
+// it is written.
 template <typename XT>
 __global__ __launch_bounds__(256) void xv_center_norm_kernel(const XT* x, const double* __restrict__ mean,
-                                                              double* y, long long n, int D, int ldx, int Kp) {
+                                                              double* y, long long n, int D, int ldx, int Kp,
+                                                              const long long* __restrict__ rows) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long t = (long long)blockIdx.x * 4 + wave;
     if (t >= n) return;
+    const long long src = rows ? rows[t] : t;
     double ss = 0.0;
     for (int d = lane; d < D; d += 64) {
-        const double v = (double)x[t * ldx + d] - (mean ? mean[d] : 0.0);
+        const double v = (double)x[src * ldx + d] - (mean ? mean[d] : 0.0);
         ss += v * v;
     }
     ss = allreduce_sum<64>(ss);
     const double nrm = sqrt(ss);                               // diarization_lib.py:185: a / np.linalg.norm(a, axis=1)
     for (int d0 = 0; d0 < Kp; d0 += 64) {
         const int d = d0 + lane;
-        const double v = d < D ? (double)x[t * ldx + d] - (mean ? mean[d] : 0.0) : 0.0;
+        const double v = d < D ? (double)x[src * ldx + d] - (mean ? mean[d] : 0.0) : 0.0;
         if (d < Kp) y[t * Kp + d] = v / nrm;
     }
+}
+
+// flags[t] = 1 where row t of x [n][D] f32 holds a NaN, else 0 (predict.py:185: np.isnan(...).any(); an infinity is no
+// NaN).  One wavefront per row: strided loads, the test on the bits (exponent all ones, mantissa not zero), a wave-level
+// any; lane 0 stores the flag.
+__global__ __launch_bounds__(256) void rows_nan_flags_kernel(const float* __restrict__ x, int* __restrict__ flags,
+                                                             long long n, int D) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long t = (long long)blockIdx.x * 4 + wave;
+    if (t >= n) return;
+    bool nan = false;
+    for (int d = lane; d < D; d += 64) nan |= (__float_as_uint(x[t * D + d]) & 0x7FFFFFFFu) > 0x7F800000u;
+    const bool any = __ballot(nan) != 0;
+    if (lane == 0) flags[t] = any ? 1 : 0;
 }
 
 // C[t][c] = sum_k A[t][k] B[k][c] - sub[c] for c < N (stored with row stride ldc); A [n][Kp], B [Kp][Np], Kp % 4 == 0,

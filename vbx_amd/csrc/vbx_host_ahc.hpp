@@ -91,13 +91,12 @@ int vbx_xvectors_destroy(vbx_xvectors* xv) {
     return VBX_OK;
 }
 
-int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32_t fea_dim, const void* x, int x_dtype,
-                         const double* mean1, const double* lda, const double* mean2, const double* plda_mu,
-                         const double* plda_tr, vbx_xvectors** out) {
-    if (!ctx) return VBX_ERR_INVALID;
-    if (!out || !x || !mean1 || !lda || !mean2 || !plda_mu || !plda_tr || n <= 0 || Din <= 0 || Dl <= 0 || fea_dim <= 0 ||
-        fea_dim > Dl || (x_dtype != VBX_F32 && x_dtype != VBX_F64))
-        FAIL(ctx, VBX_ERR_INVALID, "vbx_xvectors_project: bad argument");
+static_assert(sizeof(long long) == sizeof(int64_t), "row indices go up as they come");
+// x: n rows on the host (uploaded), or with on_device the rows rows_host[0 .. n) (nullptr: the first n) of an array that
+// already lies in HBM; everything after the first kernel is the same chain
+static int xvectors_project_impl(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32_t fea_dim, const void* x, int x_dtype,
+                                 bool on_device, const int64_t* rows_host, const double* mean1, const double* lda,
+                                 const double* mean2, const double* plda_mu, const double* plda_tr, vbx_xvectors** out) {
     *out = nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int Kp = round_up(Din, 4), Np = round_up(Dl, 16), Kp2 = round_up(Dl, 4), Np2 = round_up(fea_dim, 16);
@@ -122,8 +121,10 @@ int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32
     xv->fea_dim = fea_dim;
     const size_t esz = x_dtype == VBX_F64 ? 8 : 4;
     void* d_x = nullptr;
+    long long* d_rows = nullptr;
     double *d_y1 = nullptr, *d_m1 = nullptr, *d_lda = nullptr, *d_m2 = nullptr, *d_pt = nullptr, *d_mu = nullptr;
-    int rc = dmalloc_bytes(ctx, &d_x, (size_t)n * Din * esz);
+    int rc = on_device ? VBX_OK : dmalloc_bytes(ctx, &d_x, (size_t)n * Din * esz);
+    if (rc == VBX_OK && rows_host) rc = dmalloc(ctx, &d_rows, (size_t)n);
     if (rc == VBX_OK) rc = dmalloc(ctx, &d_y1, (size_t)n * Kp);
     if (rc == VBX_OK) rc = dmalloc(ctx, &d_m1, (size_t)Din);
     if (rc == VBX_OK) rc = dmalloc(ctx, &d_lda, ldap.size());
@@ -135,7 +136,8 @@ int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32
     hipError_t e = hipSuccess;
     if (rc == VBX_OK) {
         hipStream_t st = ctx->stream;
-        e = hipMemcpyAsync(d_x, x, (size_t)n * Din * esz, hipMemcpyHostToDevice, st);
+        if (!on_device) e = hipMemcpyAsync(d_x, x, (size_t)n * Din * esz, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && rows_host) e = hipMemcpyAsync(d_rows, rows_host, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_m1, mean1, sizeof(double) * Din, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_lda, ldap.data(), sizeof(double) * ldap.size(), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_m2, m2p.data(), sizeof(double) * m2p.size(), hipMemcpyHostToDevice, st);
@@ -143,13 +145,14 @@ int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32
         if (e == hipSuccess) e = hipMemcpyAsync(d_mu, mup.data(), sizeof(double) * mup.size(), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
             const dim3 rows((unsigned)((n + 3) / 4)), blocks((unsigned)((n + 63) / 64));
+            const void* src = on_device ? x : d_x;
             if (x_dtype == VBX_F64)
-                hipLaunchKernelGGL((vbx::xv_center_norm_kernel<double>), rows, dim3(256), 0, st, (const double*)d_x, d_m1, d_y1, (long long)n, (int)Din, (int)Din, Kp);
+                hipLaunchKernelGGL((vbx::xv_center_norm_kernel<double>), rows, dim3(256), 0, st, (const double*)src, d_m1, d_y1, (long long)n, (int)Din, (int)Din, Kp, d_rows);
             else
-                hipLaunchKernelGGL((vbx::xv_center_norm_kernel<float>), rows, dim3(256), 0, st, (const float*)d_x, d_m1, d_y1, (long long)n, (int)Din, (int)Din, Kp);
+                hipLaunchKernelGGL((vbx::xv_center_norm_kernel<float>), rows, dim3(256), 0, st, (const float*)src, d_m1, d_y1, (long long)n, (int)Din, (int)Din, Kp, d_rows);
             hipLaunchKernelGGL(vbx::xv_gemm_kernel, blocks, dim3(256), 0, st, d_y1, d_lda, d_m2, xv->d_xproj, (long long)n, Kp, Np, (int)Dl, Kp2);
             // (the columns Dl .. Kp2 of xproj must be zero for the second product)
-            hipLaunchKernelGGL((vbx::xv_center_norm_kernel<double>), rows, dim3(256), 0, st, xv->d_xproj, (const double*)nullptr, xv->d_xproj, (long long)n, (int)Dl, Kp2, Kp2);
+            hipLaunchKernelGGL((vbx::xv_center_norm_kernel<double>), rows, dim3(256), 0, st, xv->d_xproj, (const double*)nullptr, xv->d_xproj, (long long)n, (int)Dl, Kp2, Kp2, (const long long*)nullptr);
             hipLaunchKernelGGL(vbx::xv_gemm_kernel, blocks, dim3(256), 0, st, xv->d_xproj, d_pt, d_mu, xv->d_fea, (long long)n, Kp2, Np2, (int)fea_dim, (int)fea_dim);
             e = hipStreamSynchronize(st);
         }
@@ -159,12 +162,74 @@ int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32
             rc = VBX_ERR_HIP;
         }
     }
-    for (void* p : {d_x, (void*)d_y1, (void*)d_m1, (void*)d_lda, (void*)d_m2, (void*)d_pt, (void*)d_mu}) ctx_free(ctx, p);
+    for (void* p : {d_x, (void*)d_rows, (void*)d_y1, (void*)d_m1, (void*)d_lda, (void*)d_m2, (void*)d_pt, (void*)d_mu}) ctx_free(ctx, p);
     if (rc != VBX_OK) {
         vbx_xvectors_destroy(xv);
         return rc;
     }
     *out = xv;
+    return VBX_OK;
+}
+
+int vbx_xvectors_project(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t Dl, int32_t fea_dim, const void* x, int x_dtype,
+                         const double* mean1, const double* lda, const double* mean2, const double* plda_mu,
+                         const double* plda_tr, vbx_xvectors** out) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!out || !x || !mean1 || !lda || !mean2 || !plda_mu || !plda_tr || n <= 0 || Din <= 0 || Dl <= 0 || fea_dim <= 0 ||
+        fea_dim > Dl || (x_dtype != VBX_F32 && x_dtype != VBX_F64))
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_xvectors_project: bad argument");
+    return xvectors_project_impl(ctx, n, Din, Dl, fea_dim, x, x_dtype, false, nullptr, mean1, lda, mean2, plda_mu, plda_tr, out);
+}
+
+// device memory of ctx's device?  (a host pointer, or an allocation of another device, is refused before any kernel reads it)
+static bool on_ctx_device(vbx_ctx* ctx, const void* p) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice && attr.device == ctx->device;
+}
+
+int vbx_xvectors_project_device(vbx_ctx* ctx, int64_t n_src, int32_t Din, int32_t Dl, int32_t fea_dim, const float* d_x,
+                                int64_t n, const int64_t* rows_host, const double* mean1, const double* lda,
+                                const double* mean2, const double* plda_mu, const double* plda_tr, vbx_xvectors** out) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!out || !d_x || !mean1 || !lda || !mean2 || !plda_mu || !plda_tr || n <= 0 || n_src <= 0 || n > n_src || Din <= 0 ||
+        Dl <= 0 || fea_dim <= 0 || fea_dim > Dl || (!rows_host && n != n_src))
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_xvectors_project_device: bad argument");
+    *out = nullptr;
+    for (int64_t i = 0; rows_host && i < n; ++i) {
+        if (rows_host[i] < 0 || rows_host[i] >= n_src)
+            FAIL(ctx, VBX_ERR_INVALID, "vbx_xvectors_project_device: rows[%lld] = %lld is outside the %lld source rows", (long long)i,
+                 (long long)rows_host[i], (long long)n_src);
+        if (i > 0 && rows_host[i] <= rows_host[i - 1])
+            FAIL(ctx, VBX_ERR_INVALID, "vbx_xvectors_project_device: rows[%lld] = %lld does not increase (rows[%lld] = %lld)", (long long)i,
+                 (long long)rows_host[i], (long long)(i - 1), (long long)rows_host[i - 1]);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!on_ctx_device(ctx, d_x))
+        FAIL(ctx, VBX_ERR_INVALID, "vbx_xvectors_project_device: x is not device memory of device %d", ctx->device);
+    return xvectors_project_impl(ctx, n, Din, Dl, fea_dim, d_x, VBX_F32, true, rows_host, mean1, lda, mean2, plda_mu, plda_tr, out);
+}
+
+int vbx_rows_nan_flags(vbx_ctx* ctx, const float* d_x, int64_t n, int32_t D, int32_t* flags_host) {
+    if (!ctx) return VBX_ERR_INVALID;
+    if (!d_x || !flags_host || n <= 0 || D <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_rows_nan_flags: bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!on_ctx_device(ctx, d_x)) FAIL(ctx, VBX_ERR_INVALID, "vbx_rows_nan_flags: x is not device memory of device %d", ctx->device);
+    int* d_flags = nullptr;
+    int rc = dmalloc(ctx, &d_flags, (size_t)n);
+    if (rc != VBX_OK) return rc;
+    hipLaunchKernelGGL(vbx::rows_nan_flags_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, d_x, d_flags, (long long)n, (int)D);
+    hipError_t e = hipMemcpyAsync(flags_host, d_flags, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    ctx_free(ctx, d_flags);
+    if (e != hipSuccess) {
+        ctx->err = std::string("vbx_rows_nan_flags failed: ") + hipGetErrorString(e);
+        return VBX_ERR_HIP;
+    }
     return VBX_OK;
 }
 

@@ -199,7 +199,8 @@ def write_plda(path, mean, trans, psi, dtype=np.float64):
 def read_xvector_timing_dict(path):
     """``{recording: (array of x-vector names, array [n, 2] of start / end seconds)}`` from a Kaldi 'segments' file
     (diarization_lib.py:96-113): consecutive lines with the same recording name form one entry, a recording that
-    appears again later replaces its earlier entry."""
+    appears again later replaces its earlier entry.  ``path`` may be an open text file (or an ``io.StringIO``): the
+    lines of a segments file that was never written go through the same parser, to the same doubles."""
     try:                                                          # C parser when pandas is around (100k lines: 10x)
         import pandas as pd
         tab = pd.read_csv(path, sep=r'\s+', header=None, dtype={0: str, 1: str}, engine='c', na_filter=False)
@@ -209,7 +210,8 @@ def read_xvector_timing_dict(path):
         times = tab.iloc[:, 2:].to_numpy(dtype=float)
     except ImportError:
         names, recs, times = [], [], []
-        with open(path) as fd:
+        import contextlib
+        with (contextlib.nullcontext(path) if hasattr(path, 'read') else open(path)) as fd:
             for line in fd:
                 f = line.split()
                 if not f:

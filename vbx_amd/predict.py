@@ -107,6 +107,27 @@ def ragged_batches(lengths, max_frames):
     return out
 
 
+def window_batches(plan, args, ragged):
+    """The model calls of one file, in the order embed_file makes them: [(indices into plan, length)].  With ragged, the
+    windows that are not full ones come first, in ragged batches (length None); the others are grouped by length, full
+    windows --batch-size at a time."""
+    groups = {}
+    for i, w in enumerate(plan):
+        groups.setdefault(w.end - w.start, []).append(i)
+    out = []
+    if ragged:
+        rest = [i for i, w in enumerate(plan) if w.end - w.start != args.seg_len]
+        groups = {n: idx for n, idx in groups.items() if n == args.seg_len}
+        lengths = [plan[i].end - plan[i].start for i in rest]
+        for part in ragged_batches(lengths, args.batch_size * args.seg_len):
+            out.append(([rest[j] for j in part], None))
+    for length, idx in groups.items():
+        step = args.batch_size if length == args.seg_len else len(idx)
+        for b0 in range(0, len(idx), step):
+            out.append((idx[b0:b0 + step], length))
+    return out
+
+
 def embed_file(embed, fe, fn, sig, segs, sr, args, embed_ragged=None):
     """(key, segments line, embedding) of every window of one file, in predict.py's order.  embed(fe, starts, length):
     the embeddings [n][E] (numpy) of the windows of `length` frames from feature rows `starts`.  embed_ragged(fe, starts,
@@ -116,24 +137,13 @@ def embed_file(embed, fe, fn, sig, segs, sr, args, embed_ragged=None):
     plan = fbank.window_plan(fn, segs, sr, args.seg_len, args.seg_jump)
     emb = [None] * len(plan)
     start = lambda i: rows[plan[i].seg] + plan[i].start
-    groups = {}
-    for i, w in enumerate(plan):
-        groups.setdefault(w.end - w.start, []).append(i)
-    if embed_ragged is not None:
-        rest = [i for i, w in enumerate(plan) if w.end - w.start != args.seg_len]
-        groups = {n: idx for n, idx in groups.items() if n == args.seg_len}
-        lengths = [plan[i].end - plan[i].start for i in rest]
-        for part in ragged_batches(lengths, args.batch_size * args.seg_len):
-            y = embed_ragged(fe, [start(rest[j]) for j in part], [lengths[j] for j in part])
-            for j, v in zip(part, y):
-                emb[rest[j]] = v
-    for length, idx in groups.items():
-        step = args.batch_size if length == args.seg_len else len(idx)
-        for b0 in range(0, len(idx), step):
-            part = idx[b0:b0 + step]
+    for part, length in window_batches(plan, args, embed_ragged is not None):
+        if length is None:
+            y = embed_ragged(fe, [start(i) for i in part], [plan[i].end - plan[i].start for i in part])
+        else:
             y = embed(fe, [start(i) for i in part], length)
-            for i, v in zip(part, y):
-                emb[i] = v
+        for i, v in zip(part, y):
+            emb[i] = v
     return [(w.key, w.line, e) for w, e in zip(plan, emb)]
 
 

@@ -34,7 +34,7 @@ import numpy as np
 from .kaldi_formats import (read_plda, read_vec_flt_ark_grouped, read_xvec_transform, read_xvector_timing_dict,
                             write_rttm)
 
-__all__ = ['main', 'diarize', 'DeviceStages', 'tune_host_process', 'load_models', 'cluster', 'cut_linkage', 'merge_adjacent_labels', 'l2_norm']
+__all__ = ['main', 'diarize', 'diarize_recordings', 'DeviceStages', 'tune_host_process', 'load_models', 'cluster', 'cut_linkage', 'merge_adjacent_labels', 'l2_norm']
 
 
 def l2_norm(vec_or_matrix):
@@ -127,18 +127,35 @@ class DeviceStages:
             self._thread_ctxs.append(ctx)
         return ctx
 
-    def project(self, recordings, models, lda_dim):
-        self.T = [len(r[1]) for r in recordings]
+    def _layout(self, T, models, lda_dim):
+        self.T = [int(t) for t in T]
         self.row0 = np.concatenate([[0], np.cumsum(self.T)]).astype(np.int64)
         self.Phi = np.ascontiguousarray(models['plda_psi'][:lda_dim])
         self.lda_dim = lda_dim
         self.kaldi_plda = models.get('kaldi_plda')
         self._plda_full = None
+
+    def project(self, recordings, models, lda_dim):
+        self._layout([len(r[1]) for r in recordings], models, lda_dim)
         if not recordings:
             return
         x = np.concatenate([np.asarray(r[2]) for r in recordings])
         self.xv = self._capi.XVectors(self.ctx, x, models['mean1'], models['lda'], models['mean2'], models['plda_mu'],
                                       models['plda_tr'], lda_dim)
+
+    def project_device(self, T, xvectors, models, lda_dim):
+        """Adopts x-vectors projected where the network left them (``XVectors.from_device`` with ``lda_dim`` as its
+        ``fea_dim``): recording k owns the T[k] rows from sum(T[:k]) on.  Nothing goes up; close() releases them."""
+        self._layout(T, models, lda_dim)
+        if xvectors is None:
+            if self.T:
+                raise ValueError('project_device: recordings without x-vectors')
+            return
+        if xvectors.n != int(self.row0[-1]) or xvectors.fea_dim != lda_dim or xvectors.ctx.device != self.ctx.device:
+            raise ValueError(f'project_device: {xvectors.n} rows of {xvectors.fea_dim} dimensions on device '
+                             f'{xvectors.ctx.device}, the recordings ask for {int(self.row0[-1])} of {lda_dim} on device '
+                             f'{self.ctx.device}')
+        self.xv = xvectors
 
     # The device linkage merges all reciprocal nearest-neighbour pairs per round on the whole chip (round 4: 1.2 ms at
     # T = 1025, 2.2 ms at 4000, 5.8 ms at 10 000, 19 ms at 20 000; the one-workgroup chain of rounds 2-3: 12 / 54 / 174 / 512 ms);
@@ -284,8 +301,10 @@ def _rank_world():
 
 
 def _write_rttm_files(args, file_name, st, segs_dict):
-    """vbhmm.py:166-179 for one recording."""
+    """vbhmm.py:166-179 for one recording (nothing where ``args.out_rttm_dir`` is None: a library call that wants labels only)."""
     assert np.all(segs_dict[file_name][0] == st['seg_names'])                 # vbhmm.py:166
+    if args.out_rttm_dir is None:
+        return
     start, end = segs_dict[file_name][1].T
     starts, ends, out_labels = merge_adjacent_labels(start, end, st['labels1st'])
     os.makedirs(args.out_rttm_dir, exist_ok=True)
@@ -307,15 +326,12 @@ def diarize(args, stages=None, log=print, ahc_scores=None):
 
     A recording the device path cannot take (more than ``VBX_MAX_SPEAKERS`` = 16 384 AHC clusters, or one whose batch
     fails) does not take the archive down with it: every other recording is diarized and written, then a
-    ``RuntimeError`` names the ones left out.  RTTM files are written as soon as their labels exist."""
+    ``RuntimeError`` names the ones left out.  RTTM files are written as soon as their labels exist.
+
+    This is the part that reads the files; the stages are ``diarize_recordings``."""
     from .batch import shard_recordings
-    from ._capi import MAX_SPEAKERS, VbxError
     assert 0 <= args.loopP <= 1, f'Expecting loopP between 0 and 1, got {args.loopP} instead.'
-    if ahc_scores is None:
-        ahc_scores = getattr(args, 'ahc_scores', 'cos')
-    if ahc_scores not in ('cos', 'plda'):
-        raise ValueError(f"ahc_scores must be 'cos' or 'plda', not {ahc_scores!r}")
-    ahc_kw = dict(ahc_scores='plda', target_energy=getattr(args, 'target_energy', 1.0)) if ahc_scores == 'plda' else {}
+    _ahc_kw(args, ahc_scores)                                     # (a bad name fails before anything is read)
     t_start = time.perf_counter()
     segs_dict = read_xvector_timing_dict(args.segments_file)
     models = load_models(args.xvec_transform, args.plda_file)
@@ -325,6 +341,36 @@ def diarize(args, stages=None, log=print, ahc_scores=None):
         assignment = shard_recordings([float(len(r[1])) ** 2 for r in recordings], world)
         recordings = [r for k, r in enumerate(recordings) if assignment[k] == rank]
     t_read = time.perf_counter()
+    return diarize_recordings(recordings, segs_dict, models, args, stages, log=log, ahc_scores=ahc_scores,
+                              t_start=t_start, t_read=t_read, rank=rank, world=world)
+
+
+def _ahc_kw(args, ahc_scores):
+    if ahc_scores is None:
+        ahc_scores = getattr(args, 'ahc_scores', 'cos')
+    if ahc_scores not in ('cos', 'plda'):
+        raise ValueError(f"ahc_scores must be 'cos' or 'plda', not {ahc_scores!r}")
+    return dict(ahc_scores='plda', target_energy=getattr(args, 'target_energy', 1.0)) if ahc_scores == 'plda' else {}
+
+
+def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=print, ahc_scores=None, xvectors=None,
+                       t_start=None, t_read=None, rank=0, world=1):
+    """The stages of ``diarize`` for recordings already in memory: ``[(name, seg_names, x_or_None)]``, ``segs_dict`` as
+    ``read_xvector_timing_dict`` gives it, ``models`` from ``load_models``, ``args`` with the hyper-parameters
+    (init, threshold, lda_dim, Fa, Fb, loopP, init_smoothing, output_2nd, out_rttm_dir and, optionally, precision,
+    ahc_scores, target_energy).  Returns what ``diarize`` returns.
+
+    ``xvectors``: the x-vectors of all recordings, in order, projected on the device already (``XVectors.from_device``,
+    ``fea_dim`` = ``args.lda_dim``); the third entry of a recording is not read then and nothing is uploaded
+    (``stages.project_device``).  ``stages`` adopts them: they are released with it (or by the caller of injected stages).
+    ``t_start`` / ``t_read``: when the caller began and finished reading, for the timing (default: now)."""
+    from ._capi import MAX_SPEAKERS, VbxError
+    assert 0 <= args.loopP <= 1, f'Expecting loopP between 0 and 1, got {args.loopP} instead.'
+    ahc_kw = _ahc_kw(args, ahc_scores)
+    if t_read is None:
+        t_read = time.perf_counter()
+    if t_start is None:
+        t_start = t_read
     want_vb = args.init.endswith('VB')
     own_stages = stages is None
     if own_stages:
@@ -332,7 +378,10 @@ def diarize(args, stages=None, log=print, ahc_scores=None):
     failed = {}
     try:
         # ---- stage 0: every x-vector of this rank to the device, projections for all recordings at once ---------------
-        stages.project(recordings, models, args.lda_dim)
+        if xvectors is None:
+            stages.project(recordings, models, args.lda_dim)
+        else:
+            stages.project_device([len(r[1]) for r in recordings], xvectors, models, args.lda_dim)
         t_proj = time.perf_counter()
 
         # ---- stage 1: AHC initialisation -----------------------------------------------------------------------------

@@ -419,13 +419,14 @@ class ResNet101:
             return np.empty((0, self.embed_dim), dtype=np.float32)
         return self.dev.run(x.shape[0], x.shape[2], x)
 
-    def embed_windows(self, fe, starts, length: int) -> np.ndarray:
+    def embed_windows(self, fe, starts, length: int, out_ptr=None) -> np.ndarray:
         """Embeddings of the windows ``fe.windows(starts, length)`` of a front end on the same device: gathered straight
-        into the network's input buffer."""
+        into the network's input buffer.  With ``out_ptr`` (a device address with room for [len(starts)][E] f32) they stay
+        on the device and None is returned."""
         starts = np.asarray(starts, dtype=np.int64)
         ptr = self.dev.input_buffer(len(starts), length)
         fe.dev.windows(starts, length, dst_ptr=ptr)
-        return self.dev.run(len(starts), length, x_ptr=ptr)
+        return self.dev.run(len(starts), length, x_ptr=ptr, out_ptr=out_ptr)
 
     def embed_ragged(self, windows, lengths=None):
         """Embeddings [n][E] of windows of mixed lengths in one run of the network; every one has the bits ``embed`` gives
@@ -459,18 +460,19 @@ class ResNet101:
             raise ValueError(f'embed_ragged: {x.size} values given, the lengths ask for {FEAT_DIM} x {int(lengths.sum())}')
         return self.dev.run_ragged(lengths, x)
 
-    def embed_windows_ragged(self, fe, starts, lengths) -> np.ndarray:
+    def embed_windows_ragged(self, fe, starts, lengths, out_ptr=None) -> np.ndarray:
         """Embeddings of the windows of lengths[w] frames from feature rows starts[w] of a front end on the same device:
-        one gather into the network's input buffer, one run of the network."""
+        one gather into the network's input buffer, one run of the network.  With ``out_ptr`` (a device address with room
+        for [len(starts)][E] f32) they stay on the device and None is returned."""
         starts = np.asarray(starts, dtype=np.int64).reshape(-1)
         lengths = np.asarray(lengths, dtype=np.int32).reshape(-1)
         if starts.size != lengths.size:
             raise ValueError(f'embed_windows_ragged: {starts.size} starts, {lengths.size} lengths')
         if starts.size == 0:
-            return np.empty((0, self.embed_dim), dtype=np.float32)
+            return None if out_ptr is not None else np.empty((0, self.embed_dim), dtype=np.float32)
         ptr = self.dev.input_buffer_ragged(lengths)
         fe.dev.windows_ragged(starts, lengths, dst_ptr=ptr)
-        return self.dev.run_ragged(lengths, x_ptr=ptr)
+        return self.dev.run_ragged(lengths, x_ptr=ptr, out_ptr=out_ptr)
 
     def times(self) -> dict:
         """Device ms of the last run: stem, layer1 .. layer4, pool_embed."""
