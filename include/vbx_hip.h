@@ -436,6 +436,19 @@ int vbx_plda_scores_resident(vbx_ctx* ctx, vbx_xvectors* xv, int64_t row0, int64
 int vbx_plda_score_lda(vbx_ctx* ctx, int64_t N, int64_t M, int32_t D, const double* Fe, const double* Ft,
                        const double* diagAC, double* out);
 
+/* ---- md-eval diarization error of RTTM turns (vbx_rttm_score.hpp) ------------------------------------------------------
+ * What `dscore/score.py --collar C [--ignore_overlaps]` of the reference's recipes reports, DER only, for n_pairs
+ * (reference, system) pairs in one call.  Per pair p, counts[p] = {n_edges, n_ref_turns, n_sys_turns, n_ref, n_sys}:
+ *   edges   its n_edges sorted distinct cell edges (n_edges - 1 cells; 0 or 1: no cell), pair after pair
+ *   turns   [n_ref_turns + n_sys_turns][2] = (begin, end) of its merged reference turns, then of its system turns
+ *   spk     the speaker index of every turn, in [0, n_ref) and [0, n_sys); n_ref, n_sys <= 64 (more: VBX_ERR_UNSUPPORTED)
+ * A cell is scored unless its midpoint lies strictly within collar of a begin or an end of a reference turn or
+ * (ignore_overlaps != 0) two or more reference speakers are active in it.  out receives per pair 4 + n_ref n_sys f64:
+ * scored reference speaker time, miss, false alarm, sum of w min(|R|, |S|), then C [n_ref][n_sys].  A pair's numbers
+ * are the same bits alone, in any batch and at any position in it.  Synchronises before it returns. */
+int vbx_rttm_score(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* edges, const double* turns,
+                   const int32_t* spk, double collar, int ignore_overlaps, double* out);
+
 /* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then

@@ -28,6 +28,9 @@ MAX_SPEAKERS = 16384
 PLDA_COV_CHUNK = 512         # rows of one partial of the PLDA covariance (vbx_plda_score.hpp: kCovChunk)
 PLDA_MAX_DIM = 256           # dimensions the PLDA projection kernel keeps (vbx_plda_score.hpp: 16 * kPldaMaxTiles)
 MAX_REF_LABELS = 64          # labels a recording can be scored against on the device (vbx_batch_set_reference)
+# vbx_rttm_score.hpp: cells per classification workgroup, turns per LDS chunk, cells per partial block, cells per LDS chunk of
+# the accumulation, speakers per side (kRttmClsBlock, kRttmTurnChunk, kRttmGroupCells, kRttmAccChunk, kRttmMaxSpk)
+RTTM_CLS_BLOCK, RTTM_TURN_CHUNK, RTTM_GROUP_CELLS, RTTM_ACC_CHUNK, RTTM_MAX_SPEAKERS = 256, 256, 1024, 256, 64
 
 ABI_SYMBOLS = [
     'vbx_abi_version', 'vbx_create', 'vbx_destroy', 'vbx_last_error', 'vbx_device_info',
@@ -52,6 +55,7 @@ ABI_SYMBOLS = [
     'vbx_batch_set_reference', 'vbx_batch_get_scores', 'vbx_score_posteriors',
     'vbx_plda_covariance', 'vbx_plda_covariance_resident', 'vbx_plda_scores', 'vbx_plda_scores_resident', 'vbx_plda_score_lda',
     'vbx_xvectors_project_device', 'vbx_rows_nan_flags',
+    'vbx_rttm_score',
 ]
 
 
@@ -175,6 +179,7 @@ def load():
     lib.vbx_plda_score_lda.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp]
     lib.vbx_xvectors_project_device.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
     lib.vbx_rows_nan_flags.argtypes = [vp, vp, i64, i32, vp]
+    lib.vbx_rttm_score.argtypes = [vp, i32, vp, vp, vp, vp, dbl, C.c_int, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1188,6 +1193,22 @@ def plda_score_lda(ctx: Context, Fe, Ft, diagAC):
     out = np.empty((Fe.shape[0], Ft.shape[0]))
     ctx.check(ctx._lib.vbx_plda_score_lda(ctx._h, Fe.shape[0], Ft.shape[0], Fe.shape[1], _ptr(Fe), _ptr(Ft), _ptr(diagAC),
                                           _ptr(out)), 'vbx_plda_score_lda')
+    return out
+
+
+def rttm_score(ctx: Context, counts, edges, turns, spk, collar, ignore_overlaps):
+    """vbx_rttm_score for the packed pairs: ``counts`` int32 [n][5] = (edges, reference turns, system turns, reference
+    speakers, system speakers) of every pair, ``edges`` f64, ``turns`` f64 [.][2], ``spk`` int32, pair after pair.  -> f64,
+    per pair 4 + n_ref n_sys numbers: scored reference time, miss, false alarm, sum of w min(|R|, |S|), then C."""
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, 5)
+    edges, turns = _f64(edges).reshape(-1), _f64(turns).reshape(-1, 2)
+    spk = np.ascontiguousarray(spk, dtype=np.int32).reshape(-1)
+    n_cnt = counts.astype(np.int64)
+    assert edges.size == n_cnt[:, 0].sum() and turns.shape[0] == spk.size == n_cnt[:, 1:3].sum()
+    out = np.empty(int((4 + n_cnt[:, 3] * n_cnt[:, 4]).sum()))
+    if counts.shape[0]:
+        ctx.check(ctx._lib.vbx_rttm_score(ctx._h, counts.shape[0], _ptr(counts), _ptr(edges), _ptr(turns), _ptr(spk), float(collar),
+                                          int(bool(ignore_overlaps)), _ptr(out)), 'vbx_rttm_score')
     return out
 
 

@@ -95,6 +95,7 @@ def build_parser():
     p.add_argument('--precision', default='fp64', choices=['fp64', 'fp32', 'fp32-split'],
                    help='arithmetic of the VB-HMM kernels (fp64 = the reference\'s dtype and iteration counts)')
     p.add_argument('--timing', action='store_true', help='print a JSON line with the stage timings')
+    vbhmm.add_score_arguments(p)
     return p
 
 
@@ -120,6 +121,11 @@ def _check(args, error):
         error('--out-ark-fn and --out-seg-fn go together: pass both or neither')
     if not 0 <= args.loopP <= 1:
         error(f'Expecting loopP between 0 and 1, got {args.loopP} instead.')
+    if getattr(args, 'ref_rttm_dir', None) is not None:
+        try:
+            vbhmm.check_ref_rttm_dir(args, int(os.environ.get('WORLD_SIZE', 1)))
+        except ValueError as exc:
+            error(str(exc))
 
 
 def parse_args(argv=None):
@@ -278,6 +284,8 @@ def _run(args, file_names, log=print):
             stages.close()
     for name, st in state.items():
         st['starts'], st['ends'] = segs_dict[name][1][:, 0].copy(), segs_dict[name][1][:, 1].copy()
+    if getattr(args, 'ref_rttm_dir', None) is not None:
+        vbhmm.score_state(args, state, device)
     for key in ('project', 'ahc', 'vb', 'rttm'):
         timing[key] = core[key]
     timing['total'] = time.perf_counter() - t_start
@@ -289,7 +297,7 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
                   init='AHC+VB', threshold=-0.015, lda_dim=128, Fa=0.3, Fb=17.0, loopP=0.99, target_energy=1.0,
                   ahc_scores='cos', init_smoothing=5.0, output_2nd=False, precision='fp64', gemm='exact', embed_dim=256,
                   seg_len=144, seg_jump=24, batch_size=128, no_dither=False, dither='host', out_ark_fn=None, out_seg_fn=None,
-                  log=None):
+                  log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False):
     """Diarize ``wav_dir/<name>.wav`` with the VAD labels ``lab_dir/<name>.lab`` for every name of ``file_names``.
 
     -> ``({recording: dict(labels1st, labels2nd, n_iters, thr, starts, ends)}, timing)``: per x-vector of the recording its
@@ -297,7 +305,11 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
     x-vector's start and end in seconds; ``timing`` in seconds with the keys read, fbank, network, project, ahc, vb, rttm,
     total.  A recording no x-vector is left of has no entry.  With ``out_rttm_dir`` the RTTM files ``python -m
     vbx_amd.diarize`` writes are written too (``<out_rttm_dir>2nd`` with ``output_2nd``).  ``checkpoint``: a path in
-    predict.py's ``--weights`` format, or a state_dict.  The hyper-parameters are the command line's."""
+    predict.py's ``--weights`` format, or a state_dict.  The hyper-parameters are the command line's.
+
+    ``ref_rttm_dir`` (needs ``out_rttm_dir``): the RTTM files written are scored against ``<ref_rttm_dir>/<name>.rttm`` on the
+    device with ``collar`` / ``ignore_overlaps`` (``vbx_amd.score``), the DER table is printed and every recording's entry
+    gets its ``der``.  Without it nothing is scored, printed or added."""
     args = argparse.Namespace(
         gpus=str(device), checkpoint=checkpoint, gemm=gemm, model=None, weights=None, model_file=None, backend='pytorch',
         ndim=fbank.N_MEL, embed_dim=embed_dim, seg_len=seg_len, seg_jump=seg_jump, in_file_list=None, in_lab_dir=lab_dir,
@@ -305,6 +317,8 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
         dither=dither, init=init, out_rttm_dir=out_rttm_dir, xvec_transform=xvec_transform, plda_file=plda_file,
         threshold=threshold, lda_dim=lda_dim, Fa=Fa, Fb=Fb, loopP=loopP, target_energy=target_energy, ahc_scores=ahc_scores,
         init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False)
+    if ref_rttm_dir is not None:
+        args.ref_rttm_dir, args.collar, args.ignore_overlaps = ref_rttm_dir, collar, ignore_overlaps
     if init not in ('AHC', 'AHC+VB'):
         raise ValueError(f"init must be 'AHC' or 'AHC+VB', not {init!r}")
 

@@ -341,8 +341,46 @@ def diarize(args, stages=None, log=print, ahc_scores=None):
         assignment = shard_recordings([float(len(r[1])) ** 2 for r in recordings], world)
         recordings = [r for k, r in enumerate(recordings) if assignment[k] == rank]
     t_read = time.perf_counter()
-    return diarize_recordings(recordings, segs_dict, models, args, stages, log=log, ahc_scores=ahc_scores,
-                              t_start=t_start, t_read=t_read, rank=rank, world=world)
+    ref_rttm_dir = getattr(args, 'ref_rttm_dir', None)
+    if ref_rttm_dir is not None:
+        check_ref_rttm_dir(args, world)
+    state, timing = diarize_recordings(recordings, segs_dict, models, args, stages, log=log, ahc_scores=ahc_scores,
+                                       t_start=t_start, t_read=t_read, rank=rank, world=world)
+    if ref_rttm_dir is not None:                                  # on the device the stages ran on (injected host stages: in numpy)
+        if stages is None:
+            from ._capi import default_context
+            device = default_context().device
+        else:
+            device = getattr(getattr(stages, 'ctx', None), 'device', None)
+        score_state(args, state, device)
+    return state, timing
+
+
+def check_ref_rttm_dir(args, world=None):
+    """``--ref-rttm-dir`` scores the RTTM files one process wrote: refused under ``torchrun`` with several ranks, and without
+    an output directory."""
+    if world is None:
+        world = _rank_world()[1]
+    if world > 1:
+        raise ValueError('--ref-rttm-dir is not supported with more than one rank: every rank writes only its share of the '
+                         'recordings; score the merged output with `python -m vbx_amd.score -r REF -s OUT/*.rttm`')
+    if args.out_rttm_dir is None:
+        raise ValueError('--ref-rttm-dir scores the RTTM files as written: it needs an output directory (out_rttm_dir)')
+    if not os.path.isdir(args.ref_rttm_dir):                      # (found before the run, not after it)
+        raise ValueError(f'--ref-rttm-dir {args.ref_rttm_dir}: no such directory')
+
+
+def score_state(args, state, device=None):
+    """The ``--ref-rttm-dir`` step of both drivers: the RTTM files just written, parsed back from their text, against
+    ``<ref_rttm_dir>/<recording>.rttm`` on the run's device (``device=None``, a run on injected host stages: in numpy); the
+    table goes to stdout and every recording's ``der`` into its state entry."""
+    from . import score
+    records, overall = score.score_written(args.out_rttm_dir, list(state), args.ref_rttm_dir, getattr(args, 'collar', 0.25),
+                                           getattr(args, 'ignore_overlaps', False), device)
+    print(score.format_table(records, overall))
+    for name, rec in records.items():
+        state[name]['der'] = rec['der']
+    return records, overall
 
 
 def _ahc_kw(args, ahc_scores):
@@ -487,11 +525,29 @@ def build_parser():
     p.add_argument('--precision', default='fp64', choices=['fp64', 'fp32', 'fp32-split'],
                    help='arithmetic of the VB-HMM kernels (fp64 = the reference\'s dtype and iteration counts)')
     p.add_argument('--timing', action='store_true', help='print a JSON line with the stage timings of this rank')
+    add_score_arguments(p)
     return p
 
 
+def add_score_arguments(p):
+    """The scoring step the reference's recipes run after this program (dscore/score.py), as an option of it."""
+    p.add_argument('--ref-rttm-dir', required=False, type=str, default=None,
+                   help='score the RTTM files written against <dir>/<recording>.rttm on the device and print the DER table '
+                        'of `python -m vbx_amd.score` (DER only; one process: not under torchrun with several ranks)')
+    p.add_argument('--collar', required=False, type=float, default=0.25,
+                   help='with --ref-rttm-dir: no-score zone round every reference turn boundary, seconds (default: %(default)s)')
+    p.add_argument('--ignore_overlaps', action='store_true',
+                   help='with --ref-rttm-dir: do not score where two or more reference speakers speak')
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.ref_rttm_dir is not None:
+        try:
+            check_ref_rttm_dir(args, int(os.environ.get('WORLD_SIZE', 1)))
+        except ValueError as exc:
+            parser.error(str(exc))
     dist = None
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:                  # launched by torchrun: one process per GPU
         import torch
