@@ -449,6 +449,23 @@ int vbx_plda_score_lda(vbx_ctx* ctx, int64_t N, int64_t M, int32_t D, const doub
 int vbx_rttm_score(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* edges, const double* turns,
                    const int32_t* spk, double collar, int ignore_overlaps, double* out);
 
+/* ---- ... of label sequences: many hypotheses per recording (vbx_labels_score.hpp) ---------------------------------------
+ * What vbx_rttm_score gives for the turns of vbhmm.merge_adjacent_labels(starts, ends, labels), with the turns and the cell
+ * edges of every hypothesis built on the device.  Per recording r, rec_counts[r] = {T, n_ref_turns, n_ref, n_ref_edges}:
+ *   seg_times  starts[T] then ends[T], recording after recording; finite, starts[i] < ends[i], both non-decreasing
+ *   ref_turns  [n_ref_turns][2] = (begin, end) of its merged reference turns, ref_spk their speakers in [0, n_ref)
+ *   ref_edges  the reference's part of the cell edges, strictly increasing: reference turn boundaries, their collar zone ends,
+ *              lo = min(first reference begin, starts[0]) and hi = max(last reference end, ends[T - 1]), clipped to [lo, hi]
+ * Per hypothesis h, hyp[h] = {recording, n_sys} and the T labels of that recording in [0, n_sys), hypothesis after
+ * hypothesis; system speaker s is label s.  n_ref, n_sys <= 64 (more: VBX_ERR_UNSUPPORTED).  out receives per hypothesis
+ * 4 + n_ref n_sys f64 as vbx_rttm_score gives them (a label that never occurs: a zero column); info (or NULL) per hypothesis
+ * {system turns, cell edges, low and high word of the mask of the labels that have a turn of positive duration}.
+ * Everything is checked on the host before the first launch.  A hypothesis's numbers are the same bits alone, in any batch
+ * and at any position in it.  Synchronises before it returns. */
+int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, const double* seg_times, const double* ref_turns,
+                     const int32_t* ref_spk, const double* ref_edges, int32_t n_hyp, const int32_t* hyp, const int32_t* labels,
+                     double collar, int ignore_overlaps, double* out, int32_t* info);
+
 /* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then

@@ -31,6 +31,7 @@ MAX_REF_LABELS = 64          # labels a recording can be scored against on the d
 # vbx_rttm_score.hpp: cells per classification workgroup, turns per LDS chunk, cells per partial block, cells per LDS chunk of
 # the accumulation, speakers per side (kRttmClsBlock, kRttmTurnChunk, kRttmGroupCells, kRttmAccChunk, kRttmMaxSpk)
 RTTM_CLS_BLOCK, RTTM_TURN_CHUNK, RTTM_GROUP_CELLS, RTTM_ACC_CHUNK, RTTM_MAX_SPEAKERS = 256, 256, 1024, 256, 64
+LABELS_BLOCK = 256           # vbx_labels_score.hpp: segments / boundaries per scan pass of a workgroup (kLabBlock)
 
 ABI_SYMBOLS = [
     'vbx_abi_version', 'vbx_create', 'vbx_destroy', 'vbx_last_error', 'vbx_device_info',
@@ -55,7 +56,7 @@ ABI_SYMBOLS = [
     'vbx_batch_set_reference', 'vbx_batch_get_scores', 'vbx_score_posteriors',
     'vbx_plda_covariance', 'vbx_plda_covariance_resident', 'vbx_plda_scores', 'vbx_plda_scores_resident', 'vbx_plda_score_lda',
     'vbx_xvectors_project_device', 'vbx_rows_nan_flags',
-    'vbx_rttm_score',
+    'vbx_rttm_score', 'vbx_labels_score',
 ]
 
 
@@ -180,6 +181,7 @@ def load():
     lib.vbx_xvectors_project_device.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
     lib.vbx_rows_nan_flags.argtypes = [vp, vp, i64, i32, vp]
     lib.vbx_rttm_score.argtypes = [vp, i32, vp, vp, vp, vp, dbl, C.c_int, vp]
+    lib.vbx_labels_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, dbl, C.c_int, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1210,6 +1212,30 @@ def rttm_score(ctx: Context, counts, edges, turns, spk, collar, ignore_overlaps)
         ctx.check(ctx._lib.vbx_rttm_score(ctx._h, counts.shape[0], _ptr(counts), _ptr(edges), _ptr(turns), _ptr(spk), float(collar),
                                           int(bool(ignore_overlaps)), _ptr(out)), 'vbx_rttm_score')
     return out
+
+
+def labels_score(ctx: Context, rec_counts, seg_times, ref_turns, ref_spk, ref_edges, hyp, labels, collar, ignore_overlaps):
+    """vbx_labels_score: ``rec_counts`` int32 [n_rec][4] = (T, reference turns, reference speakers, reference edges) of every
+    recording, ``seg_times`` f64 (starts[T] then ends[T] per recording), ``ref_turns`` f64 [.][2], ``ref_spk`` int32,
+    ``ref_edges`` f64, ``hyp`` int32 [n_hyp][2] = (recording, system speakers), ``labels`` int32, hypothesis after hypothesis.
+    -> (f64: per hypothesis 4 + n_ref n_sys numbers as ``rttm_score`` gives them, int32 [n_hyp][4]: system turns, cell edges,
+    low and high word of the mask of labels with a turn of positive duration)."""
+    rec_counts = np.ascontiguousarray(rec_counts, dtype=np.int32).reshape(-1, 4)
+    hyp = np.ascontiguousarray(hyp, dtype=np.int32).reshape(-1, 2)
+    seg_times, ref_turns, ref_edges = _f64(seg_times).reshape(-1), _f64(ref_turns).reshape(-1, 2), _f64(ref_edges).reshape(-1)
+    ref_spk = np.ascontiguousarray(ref_spk, dtype=np.int32).reshape(-1)
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    n_rec, n_hyp = rec_counts.astype(np.int64), hyp.astype(np.int64)
+    assert ((n_hyp[:, 0] >= 0) & (n_hyp[:, 0] < len(n_rec))).all(), 'a hypothesis names a recording that is not there'
+    assert seg_times.size == 2 * n_rec[:, 0].sum() and ref_turns.shape[0] == ref_spk.size == n_rec[:, 1].sum()
+    assert ref_edges.size == n_rec[:, 3].sum() and labels.size == n_rec[n_hyp[:, 0], 0].sum()
+    out = np.empty(int((4 + n_rec[n_hyp[:, 0], 2] * np.maximum(n_hyp[:, 1], 0)).sum()))
+    info = np.zeros((hyp.shape[0], 4), dtype=np.int32)
+    if hyp.shape[0]:
+        ctx.check(ctx._lib.vbx_labels_score(ctx._h, rec_counts.shape[0], _ptr(rec_counts), _ptr(seg_times), _ptr(ref_turns), _ptr(ref_spk),
+                                            _ptr(ref_edges), hyp.shape[0], _ptr(hyp), _ptr(labels), float(collar),
+                                            int(bool(ignore_overlaps)), _ptr(out), _ptr(info)), 'vbx_labels_score')
+    return out, info
 
 
 def linkage_variant():

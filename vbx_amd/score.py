@@ -35,7 +35,7 @@ import sys
 
 import numpy as np
 
-__all__ = ['read_turns', 'merge_turns', 'score_turns', 'score_rttm', 'score_written', 'format_table', 'build_parser', 'main']
+__all__ = ['read_turns', 'merge_turns', 'score_turns', 'score_labels', 'labels_turns', 'score_rttm', 'score_written', 'format_table', 'build_parser', 'main']
 
 MAX_DEVICE_SPEAKERS = 64      # speakers per side the device path takes (vbx_rttm_score.hpp: kRttmMaxSpk)
 
@@ -201,6 +201,113 @@ def score_turns(pairs, collar=0.0, ignore_overlaps=False, device=None):
         if totals[k] is None:
             totals[k] = _host_totals(p, collar, ignore_overlaps)
     return [_record(p, *t) for p, t in zip(preps, totals)]
+
+
+def labels_turns(starts, ends, labels):
+    """The system turns ``[(start, end, label)]`` of one label per segment: ``vbhmm.merge_adjacent_labels``, what the RTTM
+    writer is given (labels as Python ints)."""
+    from .vbhmm import merge_adjacent_labels
+    if len(labels) == 0:
+        return []
+    s, e, l = merge_adjacent_labels(np.asarray(starts, dtype=np.float64), np.asarray(ends, dtype=np.float64), np.asarray(labels))
+    return [(float(a), float(b), int(c)) for a, b, c in zip(s, e, l)]
+
+
+class _LabelsRef:
+    """The reference's side of one recording for ``vbx_labels_score``, prepared once for all its label sequences: merged
+    turns, speaker names, and its part of the cell edges.  ``ok``: the device takes the recording -- at most 64 reference
+    speakers, segments of positive finite duration whose starts and ends both never decrease.  Then the turns of ANY label
+    sequence form a chain, their extent is [starts[0], ends[-1]], and ``lo`` / ``hi`` of ``_Pair`` do not depend on the labels."""
+
+    def __init__(self, ref_turns, starts, ends, collar):
+        ref = merge_turns(ref_turns, touching=False)
+        self.ref_names = sorted({t[2] for t in ref}, key=str)
+        ri = {s: i for i, s in enumerate(self.ref_names)}
+        self.rb = np.array([t[0] for t in ref], dtype=np.float64)
+        self.re = np.array([t[1] for t in ref], dtype=np.float64)
+        self.rs = np.array([ri[t[2]] for t in ref], dtype=np.int32)
+        self.starts, self.ends = np.asarray(starts, dtype=np.float64).reshape(-1), np.asarray(ends, dtype=np.float64).reshape(-1)
+        s, e = self.starts, self.ends
+        self.ok = bool(s.size > 0 and s.size == e.size and len(self.ref_names) <= MAX_DEVICE_SPEAKERS and np.isfinite(s).all()
+                       and np.isfinite(e).all() and (s < e).all() and (s[1:] >= s[:-1]).all() and (e[1:] >= e[:-1]).all())
+        if not self.ok:
+            return
+        lo, hi = min([s[0]] + self.rb[:1].tolist()), max([e[-1], self.re.max()] if self.re.size else [e[-1]])    # (rb is sorted)
+        vals = [self.rb, self.re, np.array([lo, hi])]
+        if collar > 0:
+            vals += [self.rb - collar, self.rb + collar, self.re - collar, self.re + collar]
+        self.edges = np.unique(np.clip(np.concatenate(vals), lo, hi))
+
+
+class _Names:
+    def __init__(self, ref_names, sys_names):
+        self.ref_names, self.sys_names = ref_names, sys_names
+
+
+def score_labels(items, collar=0.0, ignore_overlaps=False, device=None, timing=None):
+    """Score label sequences: ``items`` = ``[(reference turns, starts, ends, [labels, ...])]``, one entry per recording with the
+    times of its segments and any number of hypotheses, each one integer label per segment.  -> per item a list with one
+    record of ``score_turns`` per label sequence; the system speakers are the integer labels that have a turn.
+
+    ``device=None`` is ``score_turns([(reference turns, labels_turns(starts, ends, labels))], ..., device=None)``.
+    ``device=N``: the turns (``vbhmm.merge_adjacent_labels``) and the cell edges of every hypothesis are built on GPU N and the
+    reference's side is prepared once per recording (vbx_labels_score.hpp); the numbers are those of
+    ``score_turns(..., device=N)`` on the same turns.  What the device does not take runs on the numpy route: a recording with
+    more than 64 reference speakers or with segment times that decrease or have no duration, a hypothesis with more than 64
+    different labels.  ``timing``: a dict that receives the seconds of the host preparation, the device call and the mapping."""
+    import time
+    t0 = t1 = t2 = time.perf_counter()
+    collar = float(collar)
+    if not collar >= 0.0 or collar == float('inf'):
+        raise ValueError(f'collar must be a length >= 0, not {collar!r}')
+    out = [[None] * len(item[3]) for item in items]
+    host = []                                                         # (item, hypothesis) for the numpy route
+    if device is None:
+        host = [(k, j) for k, item in enumerate(items) for j in range(len(item[3]))]
+    else:
+        from . import _capi
+        refs, where, hyp, labs, names = [], [], [], [], []
+        for k, (ref_turns, starts, ends, hyps) in enumerate(items):
+            ref = _LabelsRef(ref_turns, starts, ends, collar) if len(hyps) else None
+            taken = False
+            for j, labels in enumerate(hyps):
+                labels = np.asarray(labels).reshape(-1)
+                uniq, inv = np.unique(labels, return_inverse=True)
+                if not ref.ok or labels.size != ref.starts.size or uniq.size > MAX_DEVICE_SPEAKERS:
+                    host.append((k, j))
+                    continue
+                taken = True
+                where.append((k, j))
+                hyp.append((len(refs), uniq.size))
+                labs.append(inv.astype(np.int32))
+                names.append([int(u) for u in uniq])
+            if taken:
+                refs.append(ref)
+        t1 = t2 = time.perf_counter()
+        if where:
+            rec_counts = [(r.starts.size, r.rb.size, len(r.ref_names), r.edges.size) for r in refs]
+            flat, info = _capi.labels_score(
+                _capi.default_context(int(device)), rec_counts, np.concatenate([a for r in refs for a in (r.starts, r.ends)]),
+                np.concatenate([np.stack([r.rb, r.re], axis=1) for r in refs]), np.concatenate([r.rs for r in refs]),
+                np.concatenate([r.edges for r in refs]), hyp, np.concatenate(labs), collar, ignore_overlaps)
+            t2 = time.perf_counter()
+            off = 0
+            for (k, j), (r, n_sys), lab_names, inf in zip(where, hyp, names, info):
+                ref, n_ref = refs[r], len(refs[r].ref_names)
+                tot = flat[off:off + 4].copy()
+                C = flat[off + 4:off + 4 + n_ref * n_sys].reshape(n_ref, n_sys)
+                off += 4 + n_ref * n_sys
+                mask = (int(inf[3]) & 0xffffffff) << 32 | (int(inf[2]) & 0xffffffff)
+                cols = sorted((c for c in range(n_sys) if mask >> c & 1), key=lambda c: str(lab_names[c]))     # the order of _Pair
+                out[k][j] = _record(_Names(ref.ref_names, [lab_names[c] for c in cols]), tot, np.ascontiguousarray(C[:, cols]))
+    if host:
+        records = score_turns([(items[k][0], labels_turns(items[k][1], items[k][2], items[k][3][j])) for k, j in host], collar,
+                              ignore_overlaps, None)
+        for (k, j), rec in zip(host, records):
+            out[k][j] = rec
+    if timing is not None:
+        timing.update(prepare=t1 - t0, device=t2 - t1, mapping=time.perf_counter() - t2)
+    return out
 
 
 def _pool(records):
