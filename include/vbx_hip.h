@@ -466,6 +466,31 @@ int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, con
                      const int32_t* ref_spk, const double* ref_edges, int32_t n_hyp, const int32_t* hyp, const int32_t* labels,
                      double collar, int ignore_overlaps, double* out, int32_t* info);
 
+/* ---- energy voice-activity detection (vbx_vad.hpp): the speech segments a .lab file lists ------------------------------
+ * Kaldi's energy VAD rule on the front end's frames, for n_rec recordings laid end to end in samples [n_samples] int16:
+ * rec [n_rec][2] = (first sample, samples) of each.  A recording of n samples has T = (n - winlen) / shift + 1 frames (0
+ * if n < winlen); frame t is the samples [t shift, t shift + winlen) as they are.  winlen / shift: 400 / 160 or 200 / 80,
+ * others VBX_ERR_UNSUPPORTED.  Per recording
+ *   N[t]   = winlen sum x^2 - (sum x)^2, exact in int64;  e[t] = log(max(N[t] / winlen, 1)) in f64
+ *   theta  = energy_threshold + mean_scale * sum_t e[t] / T   (T = 0: energy_threshold)
+ *   raw[t] = n_hot >= n_in * proportion in f64: n_in the frames of [t - context, t + context] inside [0, T), n_hot those
+ *            of them with e > theta
+ * then, on the maximal runs of raw: every gap between two runs shorter than min_silence frames closes, every run then
+ * shorter than min_speech frames goes, what is left grows by pad frames on both sides, clipped to [0, T), and runs that
+ * touch or overlap become one.
+ *   counts [n_rec]       the segments of every recording (0 where T = 0)
+ *   segs   [sum][2]      their frames [a, b), recording after recording; the caller provides sum_r (T_r + 1) / 2 pairs,
+ *                        only sum counts of them are written
+ *   N, e, raw [sum T]    the frames of all recordings end to end (int64, f64, bytes), theta [n_rec]; each may be NULL
+ *   ms [2]               device milliseconds of the upload and of the kernels (HIP events); may be NULL
+ * A recording's numbers are the same bits alone, in any batch and at any place in it.  VBX_ERR_INVALID with a message: a
+ * NULL pointer, n_rec <= 0, a recording outside the samples, a parameter that is not finite, or a count outside [0, 2^30].
+ * Synchronises before it returns. */
+int vbx_vad_energy(vbx_ctx* ctx, int64_t n_samples, const int16_t* samples, int32_t n_rec, const int64_t* rec, int32_t winlen,
+                   int32_t shift, double energy_threshold, double mean_scale, int32_t context, double proportion,
+                   int32_t min_silence, int32_t min_speech, int32_t pad, int32_t* counts, int32_t* segs, int64_t* N, double* e,
+                   double* theta, uint8_t* raw, float* ms);
+
 /* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then

@@ -32,6 +32,9 @@ MAX_REF_LABELS = 64          # labels a recording can be scored against on the d
 # the accumulation, speakers per side (kRttmClsBlock, kRttmTurnChunk, kRttmGroupCells, kRttmAccChunk, kRttmMaxSpk)
 RTTM_CLS_BLOCK, RTTM_TURN_CHUNK, RTTM_GROUP_CELLS, RTTM_ACC_CHUNK, RTTM_MAX_SPEAKERS = 256, 256, 1024, 256, 64
 LABELS_BLOCK = 256           # vbx_labels_score.hpp: segments / boundaries per scan pass of a workgroup (kLabBlock)
+# vbx_vad.hpp: frames per energy / decision workgroup, frames per pass of the run-boundary compaction, runs per pass of the
+# run-list stages (kVadTile, kVadRunPass, kLabBlock)
+VAD_TILE, VAD_RUN_PASS, VAD_RUN_BLOCK = 256, 4096, 256
 
 ABI_SYMBOLS = [
     'vbx_abi_version', 'vbx_create', 'vbx_destroy', 'vbx_last_error', 'vbx_device_info',
@@ -57,6 +60,7 @@ ABI_SYMBOLS = [
     'vbx_plda_covariance', 'vbx_plda_covariance_resident', 'vbx_plda_scores', 'vbx_plda_scores_resident', 'vbx_plda_score_lda',
     'vbx_xvectors_project_device', 'vbx_rows_nan_flags',
     'vbx_rttm_score', 'vbx_labels_score',
+    'vbx_vad_energy',
 ]
 
 
@@ -182,6 +186,7 @@ def load():
     lib.vbx_rows_nan_flags.argtypes = [vp, vp, i64, i32, vp]
     lib.vbx_rttm_score.argtypes = [vp, i32, vp, vp, vp, vp, dbl, C.c_int, vp]
     lib.vbx_labels_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, dbl, C.c_int, vp, vp]
+    lib.vbx_vad_energy.argtypes = [vp, i64, vp, i32, vp, i32, i32, dbl, dbl, i32, dbl, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1212,6 +1217,27 @@ def rttm_score(ctx: Context, counts, edges, turns, spk, collar, ignore_overlaps)
         ctx.check(ctx._lib.vbx_rttm_score(ctx._h, counts.shape[0], _ptr(counts), _ptr(edges), _ptr(turns), _ptr(spk), float(collar),
                                           int(bool(ignore_overlaps)), _ptr(out)), 'vbx_rttm_score')
     return out
+
+
+def vad_energy(ctx: Context, samples, rec, winlen, shift, energy_threshold, mean_scale, context, proportion, min_silence,
+               min_speech, pad, details=False, times=False):
+    """vbx_vad_energy: ``samples`` int16 (the recordings end to end), ``rec`` int64 [n][2] = (first sample, samples).
+    -> (counts int32 [n], segs int32 [sum counts][2] in frames, details, ms): details is None or (N int64, e f64, theta f64
+    [n], raw uint8) over the frames of all recordings end to end, ms None or the device milliseconds (upload, kernels)."""
+    samples = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
+    rec = np.ascontiguousarray(rec, dtype=np.int64).reshape(-1, 2)
+    T = np.where(rec[:, 1] >= winlen, (rec[:, 1] - winlen) // shift + 1, 0)
+    counts = np.zeros(rec.shape[0], dtype=np.int32)
+    segs = np.empty((int(((T + 1) // 2).sum()), 2), dtype=np.int32)
+    frames = int(T.sum())
+    det = (np.empty(frames, dtype=np.int64), np.empty(frames), np.empty(rec.shape[0]), np.empty(frames, dtype=np.uint8)) if details else None
+    ms = np.zeros(2, dtype=np.float32) if times else None
+    N, e, theta, raw = det if details else (None, None, None, None)
+    ctx.check(ctx._lib.vbx_vad_energy(ctx._h, samples.size, _ptr(samples), rec.shape[0], _ptr(rec), int(winlen), int(shift),
+                                      float(energy_threshold), float(mean_scale), int(context), float(proportion), int(min_silence),
+                                      int(min_speech), int(pad), _ptr(counts), _ptr(segs), _ptr(N), _ptr(e), _ptr(theta), _ptr(raw),
+                                      _ptr(ms)), 'vbx_vad_energy')
+    return counts, segs[:int(counts.sum())], det, ms
 
 
 def labels_score(ctx: Context, rec_counts, seg_times, ref_turns, ref_spk, ref_edges, hyp, labels, collar, ignore_overlaps):

@@ -575,7 +575,9 @@ def main(argv=None):
         return 1
     if args.timing:
         import json
-        print(json.dumps(timing))
+        # one write, line end included: the ranks of a torchrun job share the stream, and an unbuffered one takes print's
+        # text and line end separately, so that two ranks' lines could come out as one
+        sys.stdout.write(json.dumps(timing) + '\n')
     return 0
 
 
