@@ -491,6 +491,26 @@ int vbx_vad_energy(vbx_ctx* ctx, int64_t n_samples, const int16_t* samples, int3
                    int32_t min_silence, int32_t min_speech, int32_t pad, int32_t* counts, int32_t* segs, int64_t* N, double* e,
                    double* theta, uint8_t* raw, float* ms);
 
+/* ---- frame counts behind dscore's JER, B-cubed and information-theoretic columns (vbx_frame_score.hpp) --------------------
+ * dscore scores these columns on frames of `step` seconds: frame i exists for 0 <= i < int(hi / step), its time is the f64
+ * product step * i, a turn [b, e) holds the frames with b <= step * i < e, and the frames with lo <= step * i < hi count.
+ * For n_pairs (reference, system) pairs in one call; per pair p, counts[p] = {n_ref_turns, n_sys_turns, n_ref, n_sys}:
+ *   extent  [n_pairs][2] = (lo, hi), lo <= hi finite, hi / step < 2^40
+ *   turns   [n_ref_turns + n_sys_turns][2] = (begin, end) of its reference turns, then of its system turns, pair after pair;
+ *           lo <= begin <= end <= hi
+ *   spk     the speaker index of every turn, in [0, n_ref) and [0, n_sys); n_ref, n_sys <= 64 (more: VBX_ERR_UNSUPPORTED)
+ * A frame's class on a side is the set of the side's speakers active in it (the empty set is a class); classes are numbered
+ * in order of first appearance.
+ *   info    [n_pairs][4] = {cells, reference classes, system classes, 0}
+ *   classes [n_pairs][2][256]: the 64-bit speaker masks of the first 256 reference and of the first 256 system classes
+ *   out     int64, pair after pair: ref_durs [n_ref], sys_durs [n_sys], inter [n_ref][n_sys] (frames that hold both), then
+ *           cm [reference classes][system classes] -- left out for a pair with more than 256 classes on either side
+ * out_cap: the int64 out has room for; a result that needs more: VBX_ERR_INVALID, nothing written.  All sums are integers,
+ * no atomics: a pair's numbers are the same bytes alone, in any batch and at any place in it.  Everything the kernels index
+ * with is checked on the host before the first launch.  Synchronises before it returns. */
+int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* extent, const double* turns,
+                     const int32_t* spk, double step, int32_t* info, uint64_t* classes, int64_t* out, int64_t out_cap);
+
 /* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then

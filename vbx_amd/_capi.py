@@ -35,6 +35,9 @@ LABELS_BLOCK = 256           # vbx_labels_score.hpp: segments / boundaries per s
 # vbx_vad.hpp: frames per energy / decision workgroup, frames per pass of the run-boundary compaction, runs per pass of the
 # run-list stages (kVadTile, kVadRunPass, kLabBlock)
 VAD_TILE, VAD_RUN_PASS, VAD_RUN_BLOCK = 256, 4096, 256
+# vbx_frame_score.hpp: boundaries / cells / result entries per workgroup and per LDS chunk, speakers and classes per side
+# (kFrmBlock, kFrmMaxSpk, kFrmMaxCls)
+FRAME_BLOCK, FRAME_MAX_SPEAKERS, FRAME_MAX_CLASSES = 256, 64, 256
 
 ABI_SYMBOLS = [
     'vbx_abi_version', 'vbx_create', 'vbx_destroy', 'vbx_last_error', 'vbx_device_info',
@@ -61,6 +64,7 @@ ABI_SYMBOLS = [
     'vbx_xvectors_project_device', 'vbx_rows_nan_flags',
     'vbx_rttm_score', 'vbx_labels_score',
     'vbx_vad_energy',
+    'vbx_frame_counts',
 ]
 
 
@@ -187,6 +191,7 @@ def load():
     lib.vbx_rttm_score.argtypes = [vp, i32, vp, vp, vp, vp, dbl, C.c_int, vp]
     lib.vbx_labels_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, dbl, C.c_int, vp, vp]
     lib.vbx_vad_energy.argtypes = [vp, i64, vp, i32, vp, i32, i32, dbl, dbl, i32, dbl, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.vbx_frame_counts.argtypes = [vp, i32, vp, vp, vp, vp, dbl, vp, vp, vp, i64]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1238,6 +1243,28 @@ def vad_energy(ctx: Context, samples, rec, winlen, shift, energy_threshold, mean
                                       int(min_speech), int(pad), _ptr(counts), _ptr(segs), _ptr(N), _ptr(e), _ptr(theta), _ptr(raw),
                                       _ptr(ms)), 'vbx_vad_energy')
     return counts, segs[:int(counts.sum())], det, ms
+
+
+def frame_counts(ctx: Context, counts, extent, turns, spk, step):
+    """vbx_frame_counts for the packed pairs: ``counts`` int32 [n][4] = (reference turns, system turns, reference speakers,
+    system speakers) of every pair, ``extent`` f64 [n][2] = (lo, hi), ``turns`` f64 [.][2], ``spk`` int32, pair after pair.
+    -> (info int32 [n][4] = cells, reference classes, system classes, 0; classes uint64 [n][2][256]: the speaker masks of the
+    classes in order of first appearance; out int64, per pair ref_durs, sys_durs, inter [n_ref][n_sys] and -- unless a side
+    has more than 256 classes -- cm [reference classes][system classes])."""
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, 4)
+    extent, turns = _f64(extent).reshape(-1, 2), _f64(turns).reshape(-1, 2)
+    spk = np.ascontiguousarray(spk, dtype=np.int32).reshape(-1)
+    n = counts.astype(np.int64)
+    assert extent.shape[0] == n.shape[0] and turns.shape[0] == spk.size == n[:, :2].sum()
+    # classes on a side: at most one per cell, at most 2 (turns of the pair) + 1 cells
+    cls = np.minimum(2 * n[:, :2].sum(axis=1) + 1, FRAME_MAX_CLASSES)
+    out = np.empty(int((n[:, 2] + n[:, 3] + n[:, 2] * n[:, 3] + cls * cls).sum()), dtype=np.int64)
+    info = np.zeros((n.shape[0], 4), dtype=np.int32)
+    classes = np.zeros((n.shape[0], 2, FRAME_MAX_CLASSES), dtype=np.uint64)
+    if n.shape[0]:
+        ctx.check(ctx._lib.vbx_frame_counts(ctx._h, n.shape[0], _ptr(counts), _ptr(extent), _ptr(turns), _ptr(spk), float(step),
+                                            _ptr(info), _ptr(classes), _ptr(out), out.size), 'vbx_frame_counts')
+    return info, classes, out
 
 
 def labels_score(ctx: Context, rec_counts, seg_times, ref_turns, ref_spk, ref_edges, hyp, labels, collar, ignore_overlaps):

@@ -48,6 +48,7 @@ using namespace vbx;
 #include "vbx_rttm_score.hpp"    // md-eval DER of RTTM turns: kernels and entry point
 #include "vbx_labels_score.hpp"  // ... of label sequences: turns and cell edges built on the device
 #include "vbx_vad.hpp"           // energy voice-activity detection: the .lab files the front end reads
+#include "vbx_frame_score.hpp"   // frame counts behind dscore's JER, B-cubed and information-theoretic columns
 
 #ifdef VBX_PHASE_CLOCKS
 // instrumentation builds only: the per-tile phase stamps of chunk_post_mid_kernel (tile, {wave 0, wave 2}, 8)
