@@ -39,6 +39,7 @@ using namespace vbx;
 // The host side in reading order (each part opens and closes its own extern "C" block):
 #include "vbx_host_state.hpp"    // vbx_ctx, vbx_batch
 #include "vbx_host_launch.hpp"   // launch helpers of an iteration, allocator
+#include "vbx_host_call.hpp"     // the device scratch and error state of a one-shot entry point
 #include "vbx_host_batch.hpp"    // context API; a batch on one stream
 #include "vbx_host_group.hpp"    // stream groups, the public vbx_batch_* entry points, vbx_run
 #include "vbx_host_steps.hpp"    // step-level API of the parity tests

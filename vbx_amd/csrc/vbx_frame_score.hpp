@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void frame_acc_kernel(const FrmPair* __restric
 
 }  // namespace vbx
 
-// ---- host glue (included by vbx_capi.hip after vbx_labels_score.hpp) ---------------------------------------------------------
+// ---- host glue (included by vbx_capi.hip after vbx_host_call.hpp and vbx_labels_score.hpp) -----------------------------------
 extern "C" {
 
 int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* extent, const double* turns,
@@ -302,8 +302,7 @@ int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const
         if (nrt + nst > 0 && (!turns || !spk)) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: NULL argument");
         for (long long t = 0; t < (long long)nrt + nst; ++t) {
             const double b = turns[2 * (n_turns + t)], e = turns[2 * (n_turns + t) + 1];
-            const int sp = spk[n_turns + t], lim = t < nrt ? nr : ns;
-            if (sp < 0 || sp >= lim) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: pair %d: speaker %d of turn %lld outside [0, %d)", p, sp, t, lim);
+            if (int rc = check_turn_speakers(ctx, "vbx_frame_counts", "pair", p, "turn", spk + n_turns + t, t, 1, t < nrt ? nr : ns)) return rc;
             if (!(lo <= b && b <= e && e <= hi)) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: pair %d: turn %lld [%g, %g] outside the extent [%g, %g]", p, t, b, e, lo, hi);
         }
         FrmPair& pr = pairs[p];
@@ -325,69 +324,51 @@ int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const
     }
     if (n_bnd > 0x7fffffffLL || bnd_items.size() > 0x7fffffffULL)
         FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_frame_counts: %lld turns in one call", n_turns);
-    std::vector<double> tb((size_t)n_turns), te((size_t)n_turns);     // turns arrive as [n][2]; the kernels read two planes
-    for (long long t = 0; t < n_turns; ++t) {
-        tb[(size_t)t] = turns[2 * t];
-        te[(size_t)t] = turns[2 * t + 1];
-    }
+    const TurnPlanes tp(turns, n_turns);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    FrmPair* d_pairs = nullptr;
-    int2 *d_bitems = nullptr, *d_citems = nullptr, *d_aitems = nullptr;
-    double *d_tb = nullptr, *d_te = nullptr;
-    long long *d_idx = nullptr, *d_sorted = nullptr, *d_uniq = nullptr, *d_cnt = nullptr, *d_out = nullptr;
-    unsigned long long *d_r = nullptr, *d_s = nullptr, *d_classes = nullptr;
-    int *d_spk = nullptr, *d_rfirst = nullptr, *d_sfirst = nullptr, *d_rcls = nullptr, *d_scls = nullptr, *d_info = nullptr;
     std::vector<int32_t> got((size_t)n_pairs * vbx::kFrmInfo);
+    std::vector<int2> acc_items;
+    DeviceCall call(ctx);                         // (after every host buffer its copies read or write)
+    hipStream_t st = call.st;
     const size_t n_classes = (size_t)n_pairs * 2 * vbx::kFrmMaxCls;
     // ---- phase 1: cells, masks and classes of every pair ----
-    int rc = dmalloc(ctx, &d_pairs, pairs.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_bitems, bnd_items.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_citems, cell_items.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_tb, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_te, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_spk, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_idx, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_sorted, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_uniq, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_cnt, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_r, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_s, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rfirst, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_sfirst, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rcls, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_scls, (size_t)n_bnd);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_classes, n_classes);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_info, got.size());
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        e = hipMemcpyAsync(d_pairs, pairs.data(), sizeof(FrmPair) * pairs.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_bitems, bnd_items.data(), sizeof(int2) * bnd_items.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_citems, cell_items.data(), sizeof(int2) * cell_items.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_turns) e = hipMemcpyAsync(d_tb, tb.data(), sizeof(double) * (size_t)n_turns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_turns) e = hipMemcpyAsync(d_te, te.data(), sizeof(double) * (size_t)n_turns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_turns) e = hipMemcpyAsync(d_spk, spk, sizeof(int32_t) * (size_t)n_turns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(d_classes, 0, sizeof(unsigned long long) * n_classes, st);
-        if (e == hipSuccess) {
-            const dim3 nbi((unsigned)bnd_items.size()), nci((unsigned)cell_items.size()), np((unsigned)n_pairs), th(256);
-            hipLaunchKernelGGL(vbx::frame_bounds_kernel, nbi, th, 0, st, d_pairs, d_bitems, d_tb, d_te, step, d_idx);
-            hipLaunchKernelGGL(vbx::frame_sort_kernel, nbi, th, 0, st, d_pairs, d_bitems, d_idx, d_sorted);
-            hipLaunchKernelGGL(vbx::frame_cells_kernel, np, th, 0, st, d_pairs, d_sorted, d_uniq, d_info);
-            hipLaunchKernelGGL(vbx::frame_masks_kernel, nci, th, 0, st, d_pairs, d_citems, d_idx, d_spk, d_uniq, d_info, d_r, d_s, d_cnt);
-            hipLaunchKernelGGL(vbx::frame_firsts_kernel, nci, th, 0, st, d_pairs, d_citems, d_info, d_r, d_s, d_rfirst, d_sfirst);
-            hipLaunchKernelGGL(vbx::frame_classes_kernel, np, th, 0, st, d_pairs, d_r, d_s, d_rfirst, d_sfirst, d_rcls, d_scls, d_classes,
-                               d_info);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(got.data(), d_info, sizeof(int32_t) * got.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(classes, d_classes, sizeof(uint64_t) * n_classes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    FrmPair* d_pairs = call.upload(pairs.data(), pairs.size());
+    const int2* d_bitems = call.upload(bnd_items.data(), bnd_items.size());
+    const int2* d_citems = call.upload(cell_items.data(), cell_items.size());
+    const double* d_tb = call.upload(tp.beg.data(), (size_t)n_turns);
+    const double* d_te = call.upload(tp.end.data(), (size_t)n_turns);
+    const int* d_spk = call.upload(spk, (size_t)n_turns);
+    long long* d_idx = call.alloc<long long>((size_t)n_bnd);
+    long long* d_sorted = call.alloc<long long>((size_t)n_bnd);
+    long long* d_uniq = call.alloc<long long>((size_t)n_bnd);
+    long long* d_cnt = call.alloc<long long>((size_t)n_bnd);
+    auto* d_r = call.alloc<unsigned long long>((size_t)n_bnd);
+    auto* d_s = call.alloc<unsigned long long>((size_t)n_bnd);
+    int* d_rfirst = call.alloc<int>((size_t)n_bnd);
+    int* d_sfirst = call.alloc<int>((size_t)n_bnd);
+    int* d_rcls = call.alloc<int>((size_t)n_bnd);
+    int* d_scls = call.alloc<int>((size_t)n_bnd);
+    auto* d_classes = call.alloc<unsigned long long>(n_classes);
+    int* d_info = call.alloc<int>(got.size());
+    if (call.ok()) call.enqueued(hipMemsetAsync(d_classes, 0, sizeof(unsigned long long) * n_classes, st));
+    if (call.ok()) {
+        const dim3 nbi((unsigned)bnd_items.size()), nci((unsigned)cell_items.size()), np((unsigned)n_pairs), th(256);
+        hipLaunchKernelGGL(vbx::frame_bounds_kernel, nbi, th, 0, st, d_pairs, d_bitems, d_tb, d_te, step, d_idx);
+        hipLaunchKernelGGL(vbx::frame_sort_kernel, nbi, th, 0, st, d_pairs, d_bitems, d_idx, d_sorted);
+        hipLaunchKernelGGL(vbx::frame_cells_kernel, np, th, 0, st, d_pairs, d_sorted, d_uniq, d_info);
+        hipLaunchKernelGGL(vbx::frame_masks_kernel, nci, th, 0, st, d_pairs, d_citems, d_idx, d_spk, d_uniq, d_info, d_r, d_s, d_cnt);
+        hipLaunchKernelGGL(vbx::frame_firsts_kernel, nci, th, 0, st, d_pairs, d_citems, d_info, d_r, d_s, d_rfirst, d_sfirst);
+        hipLaunchKernelGGL(vbx::frame_classes_kernel, np, th, 0, st, d_pairs, d_r, d_s, d_rfirst, d_sfirst, d_rcls, d_scls, d_classes,
+                           d_info);
+        call.launched();
     }
+    call.download(got.data(), d_info, got.size());
+    call.download((unsigned long long*)classes, d_classes, n_classes);
+    call.sync();
     // ---- phase 2: the sums, sized by what came back; a pair with more classes than kFrmMaxCls a side gets no cm ----
-    std::vector<int2> acc_items;
     long long n_out = 0;
     bool sane = true;
-    if (rc == VBX_OK && e == hipSuccess) {
+    if (call.ok()) {
         for (int p = 0; p < n_pairs; ++p) {
             FrmPair& pr = pairs[p];
             int32_t* g = got.data() + (size_t)p * vbx::kFrmInfo;
@@ -408,26 +389,19 @@ int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const
         }
     }
     const bool room = n_out <= out_cap;
-    if (rc == VBX_OK && e == hipSuccess && sane && room && n_out > 0) {
-        rc = dmalloc(ctx, &d_aitems, acc_items.size());
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_out, (size_t)n_out);
-        if (rc == VBX_OK) {
-            e = hipMemcpyAsync(d_pairs, pairs.data(), sizeof(FrmPair) * pairs.size(), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_aitems, acc_items.data(), sizeof(int2) * acc_items.size(), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(vbx::frame_acc_kernel, dim3((unsigned)acc_items.size()), dim3(256), 0, st, d_pairs, d_aitems, d_r, d_s,
-                                   d_cnt, d_rfirst, d_sfirst, d_rcls, d_scls, d_out);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(int64_t) * (size_t)n_out, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (sane && room && n_out > 0) {
+        call.copy_in(d_pairs, pairs.data(), pairs.size());            // (with what came back)
+        const int2* d_aitems = call.upload(acc_items.data(), acc_items.size());
+        long long* d_out = call.alloc<long long>((size_t)n_out);
+        if (call.ok()) {
+            hipLaunchKernelGGL(vbx::frame_acc_kernel, dim3((unsigned)acc_items.size()), dim3(256), 0, st, d_pairs, d_aitems, d_r, d_s, d_cnt,
+                               d_rfirst, d_sfirst, d_rcls, d_scls, d_out);
+            call.launched();
         }
+        call.download((long long*)out, d_out, (size_t)n_out);
+        call.sync();
     }
-    for (void* p : {(void*)d_pairs, (void*)d_bitems, (void*)d_citems, (void*)d_aitems, (void*)d_tb, (void*)d_te, (void*)d_idx,
-                    (void*)d_sorted, (void*)d_uniq, (void*)d_cnt, (void*)d_out, (void*)d_r, (void*)d_s, (void*)d_classes, (void*)d_spk,
-                    (void*)d_rfirst, (void*)d_sfirst, (void*)d_rcls, (void*)d_scls, (void*)d_info}) ctx_free(ctx, p);
-    if (rc != VBX_OK) return rc;
-    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "frame count kernels failed: %s", hipGetErrorString(e));
+    if (int rc = call.finish("frame count kernels failed")) return rc;
     if (!sane) FAIL(ctx, VBX_ERR_HIP, "vbx_frame_counts: the cell or class counts that came back do not fit their room");
     if (!room) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: the result has %lld entries, out has room for %lld", n_out, (long long)out_cap);
     std::memcpy(info, got.data(), sizeof(int32_t) * got.size());

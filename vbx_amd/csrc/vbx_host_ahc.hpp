@@ -1,5 +1,6 @@
 // vbx_host_ahc.hpp -- C ABI: the rows next to the path -- score stage of the AHC initialisation, resident x-vectors, average linkage
-// (one translation unit with vbx_capi.hip, which includes the parts in order; not a stand-alone header)
+// (one translation unit with vbx_capi.hip, which includes the parts in order, this one after vbx_host_call.hpp: every entry
+// point here keeps its device scratch in a DeviceCall; not a stand-alone header)
 #pragma once
 // ---------------------------------------------------------------------------------------
 // score stage of the AHC initialisation (vbhmm.py:135-138)
@@ -23,43 +24,38 @@ int vbx_scores_destroy(vbx_scores* sc) {
 
 int64_t vbx_scores_count(const vbx_scores* sc) { return sc ? sc->n : 0; }
 
+// the end of every function that makes a handle: out it goes, or away where filling it failed (*out is NULL already)
+static int scores_result(vbx_scores* sc, int rc, vbx_scores** out) {
+    if (rc == VBX_OK) *out = sc;
+    else vbx_scores_destroy(sc);
+    return rc;
+}
+
 // x: host pointer (uploaded) or, with on_device, rows already resident in HBM
 static int cos_similarity_impl(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, bool on_device, vbx_scores** out) {
     if (T > 200000) FAIL(ctx, VBX_ERR_UNSUPPORTED, "T=%lld: the T x T score matrix would not fit the device", (long long)T);
     *out = nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int Dp = round_up(D, 16);
-    double *d_x = nullptr, *d_xn = nullptr;
     vbx_scores* sc = new vbx_scores();
     sc->ctx = ctx;
     sc->n = (long long)T * T;
-    int rc = on_device ? VBX_OK : dmalloc(ctx, &d_x, (size_t)T * D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_xn, (size_t)T * Dp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &sc->d_s, (size_t)sc->n);
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        if (!on_device) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(vbx::cos_norm_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, ctx->stream,
-                               on_device ? x : d_x, d_xn, (long long)T, (int)D, Dp);
+    int rc;
+    {
+        DeviceCall call(ctx);
+        const double* rows = on_device ? x : call.upload(x, (size_t)T * D);
+        double* d_xn = call.alloc<double>((size_t)T * Dp);
+        if (call.ok()) call.rc = dmalloc(ctx, &sc->d_s, (size_t)sc->n);
+        if (call.ok()) {
+            hipLaunchKernelGGL(vbx::cos_norm_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, call.st, rows, d_xn, (long long)T, (int)D, Dp);
             const unsigned nb = (unsigned)((T + 63) / 64);
-            hipLaunchKernelGGL(vbx::cos_gemm_kernel, dim3(nb, nb), dim3(256), 0, ctx->stream, d_xn, sc->d_s, (long long)T, Dp);
-            e = hipStreamSynchronize(ctx->stream);
+            hipLaunchKernelGGL(vbx::cos_gemm_kernel, dim3(nb, nb), dim3(256), 0, call.st, d_xn, sc->d_s, (long long)T, Dp);
+            call.launched();
         }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("cos_similarity kernels failed: ") + hipGetErrorString(e);
-            rc = VBX_ERR_HIP;
-        }
-    }
-    if (!on_device) ctx_free(ctx, d_x);
-    ctx_free(ctx, d_xn);
-    if (rc != VBX_OK) {
-        vbx_scores_destroy(sc);
-        return rc;
-    }
-    *out = sc;
-    return VBX_OK;
+        call.sync();
+        rc = call.finish("cos_similarity kernels failed");
+    }                                             // (the scratch is back, the stream idle: the handle may go too)
+    return scores_result(sc, rc, out);
 }
 
 int vbx_cos_similarity(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, vbx_scores** out) {
@@ -120,32 +116,22 @@ static int xvectors_project_impl(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t D
     xv->Dl = Dl;
     xv->fea_dim = fea_dim;
     const size_t esz = x_dtype == VBX_F64 ? 8 : 4;
-    void* d_x = nullptr;
-    long long* d_rows = nullptr;
-    double *d_y1 = nullptr, *d_m1 = nullptr, *d_lda = nullptr, *d_m2 = nullptr, *d_pt = nullptr, *d_mu = nullptr;
-    int rc = on_device ? VBX_OK : dmalloc_bytes(ctx, &d_x, (size_t)n * Din * esz);
-    if (rc == VBX_OK && rows_host) rc = dmalloc(ctx, &d_rows, (size_t)n);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_y1, (size_t)n * Kp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_m1, (size_t)Din);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_lda, ldap.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_m2, m2p.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_pt, ptp.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_mu, mup.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &xv->d_xproj, (size_t)n * Kp2);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &xv->d_fea, (size_t)n * fea_dim);
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        if (!on_device) e = hipMemcpyAsync(d_x, x, (size_t)n * Din * esz, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && rows_host) e = hipMemcpyAsync(d_rows, rows_host, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_m1, mean1, sizeof(double) * Din, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_lda, ldap.data(), sizeof(double) * ldap.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_m2, m2p.data(), sizeof(double) * m2p.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_pt, ptp.data(), sizeof(double) * ptp.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_mu, mup.data(), sizeof(double) * mup.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
+    int rc;
+    {
+        DeviceCall call(ctx);
+        hipStream_t st = call.st;
+        const void* src = on_device ? x : call.upload(static_cast<const char*>(x), (size_t)n * Din * esz);
+        const long long* d_rows = rows_host ? call.upload((const long long*)rows_host, (size_t)n) : nullptr;
+        double* d_y1 = call.alloc<double>((size_t)n * Kp);
+        const double* d_m1 = call.upload(mean1, (size_t)Din);
+        const double* d_lda = call.upload(ldap.data(), ldap.size());
+        const double* d_m2 = call.upload(m2p.data(), m2p.size());
+        const double* d_pt = call.upload(ptp.data(), ptp.size());
+        const double* d_mu = call.upload(mup.data(), mup.size());
+        if (call.ok()) call.rc = dmalloc(ctx, &xv->d_xproj, (size_t)n * Kp2);
+        if (call.ok()) call.rc = dmalloc(ctx, &xv->d_fea, (size_t)n * fea_dim);
+        if (call.ok()) {
             const dim3 rows((unsigned)((n + 3) / 4)), blocks((unsigned)((n + 63) / 64));
-            const void* src = on_device ? x : d_x;
             if (x_dtype == VBX_F64)
                 hipLaunchKernelGGL((vbx::xv_center_norm_kernel<double>), rows, dim3(256), 0, st, (const double*)src, d_m1, d_y1, (long long)n, (int)Din, (int)Din, Kp, d_rows);
             else
@@ -154,15 +140,11 @@ static int xvectors_project_impl(vbx_ctx* ctx, int64_t n, int32_t Din, int32_t D
             // (the columns Dl .. Kp2 of xproj must be zero for the second product)
             hipLaunchKernelGGL((vbx::xv_center_norm_kernel<double>), rows, dim3(256), 0, st, xv->d_xproj, (const double*)nullptr, xv->d_xproj, (long long)n, (int)Dl, Kp2, Kp2, (const long long*)nullptr);
             hipLaunchKernelGGL(vbx::xv_gemm_kernel, blocks, dim3(256), 0, st, xv->d_xproj, d_pt, d_mu, xv->d_fea, (long long)n, Kp2, Np2, (int)fea_dim, (int)fea_dim);
-            e = hipStreamSynchronize(st);
+            call.launched();
         }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("x-vector projection failed: ") + hipGetErrorString(e);
-            rc = VBX_ERR_HIP;
-        }
-    }
-    for (void* p : {d_x, (void*)d_rows, (void*)d_y1, (void*)d_m1, (void*)d_lda, (void*)d_m2, (void*)d_pt, (void*)d_mu}) ctx_free(ctx, p);
+        call.sync();
+        rc = call.finish("x-vector projection failed");
+    }                                             // (the scratch is back, the stream idle: the handle may go too)
     if (rc != VBX_OK) {
         vbx_xvectors_destroy(xv);
         return rc;
@@ -218,19 +200,15 @@ int vbx_rows_nan_flags(vbx_ctx* ctx, const float* d_x, int64_t n, int32_t D, int
     if (!d_x || !flags_host || n <= 0 || D <= 0) FAIL(ctx, VBX_ERR_INVALID, "vbx_rows_nan_flags: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!on_ctx_device(ctx, d_x)) FAIL(ctx, VBX_ERR_INVALID, "vbx_rows_nan_flags: x is not device memory of device %d", ctx->device);
-    int* d_flags = nullptr;
-    int rc = dmalloc(ctx, &d_flags, (size_t)n);
-    if (rc != VBX_OK) return rc;
-    hipLaunchKernelGGL(vbx::rows_nan_flags_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, d_x, d_flags, (long long)n, (int)D);
-    hipError_t e = hipMemcpyAsync(flags_host, d_flags, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    ctx_free(ctx, d_flags);
-    if (e != hipSuccess) {
-        ctx->err = std::string("vbx_rows_nan_flags failed: ") + hipGetErrorString(e);
-        return VBX_ERR_HIP;
+    DeviceCall call(ctx);
+    int* d_flags = call.alloc<int>((size_t)n);
+    if (call.ok()) {
+        hipLaunchKernelGGL(vbx::rows_nan_flags_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, call.st, d_x, d_flags, (long long)n, (int)D);
+        call.launched();
     }
-    return VBX_OK;
+    call.download(flags_host, d_flags, (size_t)n);
+    call.sync();
+    return call.finish("vbx_rows_nan_flags failed");
 }
 
 int vbx_xvectors_get(vbx_xvectors* xv, int which, int64_t row0, int64_t nrows, double* out) {
@@ -271,12 +249,7 @@ int vbx_scores_upload(vbx_ctx* ctx, int64_t n, const double* s, vbx_scores** out
             rc = VBX_ERR_HIP;
         }
     }
-    if (rc != VBX_OK) {
-        vbx_scores_destroy(sc);
-        return rc;
-    }
-    *out = sc;
-    return VBX_OK;
+    return scores_result(sc, rc, out);
 }
 
 int vbx_scores_get(vbx_scores* sc, int64_t offset, int64_t count, double* out) {
@@ -357,114 +330,95 @@ int vbx_scores_linkage_average(vbx_scores* sc, int64_t T, double* Z) {
     constexpr long long kStageMin = 4096, kRoundsFrom = 256, kRoundsStop = 48;
     const char* dev_mode = experiment_env("VBX_AMD_LINKAGE_DEVICE");           // (read per call: tests compare the two in one process)
     const bool rounds_on = !(dev_mode && std::strcmp(dev_mode, "chain") == 0);
-    int *d_size = nullptr, *d_size2 = nullptr, *d_chain = nullptr, *d_orig = nullptr, *d_orig2 = nullptr, *d_old = nullptr,
-        *d_newidx = nullptr, *d_state = nullptr, *d_nn = nullptr, *d_role = nullptr;
-    double *d_alt = nullptr, *d_cmp = nullptr, *d_nnd = nullptr;
-    vbx::ChainMergeDev* d_merges = nullptr;
-    vbx::RnnPair* d_pairs = nullptr;
     const bool rounds = rounds_on && T >= kRoundsFrom;
-    int rc = dmalloc(ctx, &d_size, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_chain, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_orig, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_state, (size_t)4);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_merges, (size_t)(T - 1));
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_size2, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_orig2, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_old, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_newidx, (size_t)T);
-    if (rc == VBX_OK && rounds) {
-        rc = dmalloc(ctx, &d_nn, (size_t)T);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_nnd, (size_t)T);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_role, (size_t)T);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_pairs, (size_t)(T / 2 + 1));
-    }
     std::vector<vbx::ChainMerge> merges((size_t)(T - 1));
     static_assert(sizeof(vbx::ChainMerge) == sizeof(vbx::ChainMergeDev), "merge record layout");
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        std::vector<int> ones((size_t)T, 1), iota((size_t)T);
-        for (long long i = 0; i < T; ++i) iota[(size_t)i] = (int)i;
-        const int zero4[4] = {0, 0, 0, 0};
-        e = hipMemcpyAsync(d_size, ones.data(), sizeof(int) * (size_t)T, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_orig, iota.data(), sizeof(int) * (size_t)T, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_state, zero4, sizeof(zero4), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);                 // (the host vectors go out of scope below)
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(vbx::linkage_prepare_kernel, dim3((unsigned)T), dim3(256), 0, st, sc->d_s, (long long)T);
-            double* cur = sc->d_s;
-            int *size_c = d_size, *size_a = d_size2, *orig_c = d_orig, *orig_a = d_orig2;
-            long long n_cur = T, done = 0;
-            auto compact_into = [&](double* dst, long long n_new) {       // the live clusters move up, in order
-                hipLaunchKernelGGL(vbx::linkage_compact_index_kernel, dim3(1), dim3(1024), 0, st, (int)n_cur, size_c, orig_c,
-                                   d_chain, d_state, size_a, orig_a, d_old, d_newidx);
-                hipLaunchKernelGGL(vbx::linkage_compact_matrix_kernel, dim3((unsigned)n_new), dim3(256), 0, st, cur, (int)n_cur,
-                                   dst, (int)n_new, d_old);
-                std::swap(size_c, size_a);
-                std::swap(orig_c, orig_a);
-                n_cur = n_new;
-            };
-            if (rounds) {
-                // rounds of reciprocal pairs on the matrix as it lies (dead rows and columns are skipped, not removed: a
-                // round reads n_live x n entries), until few clusters are left or a round hardly merges anything
-                int stalled = 0;
-                while (e == hipSuccess && T - done > kRoundsStop && stalled < 3) {
-                    const int n = (int)T;
-                    hipLaunchKernelGGL(vbx::rnn_rowmin_kernel, dim3((unsigned)n), dim3(256), 0, st, cur, n, size_c, d_nn, d_nnd);
-                    hipLaunchKernelGGL(vbx::rnn_pairs_kernel, dim3(1), dim3(1024), 0, st, n, size_c, orig_c, d_nn, d_nnd, d_pairs,
-                                       d_role, d_merges, d_state);
-                    int st_host[4] = {0, 0, 0, 0};
-                    e = hipMemcpyAsync(st_host, d_state, sizeof st_host, hipMemcpyDeviceToHost, st);
-                    if (e == hipSuccess) e = hipStreamSynchronize(st);
-                    if (e != hipSuccess) break;
-                    const int np = st_host[3];
-                    if (np <= 0) break;                                    // (cannot happen: the smallest pair is reciprocal)
-                    hipLaunchKernelGGL(vbx::rnn_rows_kernel, dim3((unsigned)np), dim3(256), 0, st, cur, n, size_c, d_pairs);
-                    hipLaunchKernelGGL(vbx::rnn_cols_kernel, dim3((unsigned)n), dim3(256), 0, st, cur, n, size_c, d_role, d_pairs, d_state);
-                    hipLaunchKernelGGL(vbx::rnn_canon_kernel, dim3((unsigned)np), dim3(256), 0, st, cur, n, d_pairs, d_state);
-                    hipLaunchKernelGGL(vbx::rnn_sizes_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, size_c, d_pairs, d_state);
-                    stalled = ((long long)np * 64 < T - done) ? stalled + 1 : 0;
-                    done = st_host[2];
-                }
-                if (e == hipSuccess && done < T - 1) {                     // what is left goes to the chain, compacted
-                    const long long n_new = T - done;
-                    rc = dmalloc(ctx, &d_cmp, (size_t)(n_new * n_new));
-                    if (rc == VBX_OK) {
-                        compact_into(d_cmp, n_new);
-                        cur = d_cmp;
-                    }
+    std::vector<int> ones((size_t)T, 1), iota((size_t)T);
+    for (long long i = 0; i < T; ++i) iota[(size_t)i] = (int)i;
+    const int zero4[4] = {0, 0, 0, 0};
+    DeviceCall call(ctx);
+    hipStream_t st = call.st;
+    int* d_size = call.upload(ones.data(), (size_t)T);
+    int* d_chain = call.alloc<int>((size_t)T);
+    int* d_orig = call.upload(iota.data(), (size_t)T);
+    int* d_state = call.upload(zero4, (size_t)4);
+    auto* d_merges = call.alloc<vbx::ChainMergeDev>((size_t)(T - 1));
+    int* d_size2 = call.alloc<int>((size_t)T);
+    int* d_orig2 = call.alloc<int>((size_t)T);
+    int* d_old = call.alloc<int>((size_t)T);
+    int* d_newidx = call.alloc<int>((size_t)T);
+    int* d_nn = rounds ? call.alloc<int>((size_t)T) : nullptr;
+    double* d_nnd = rounds ? call.alloc<double>((size_t)T) : nullptr;
+    int* d_role = rounds ? call.alloc<int>((size_t)T) : nullptr;
+    auto* d_pairs = rounds ? call.alloc<vbx::RnnPair>((size_t)(T / 2 + 1)) : nullptr;
+    if (call.ok()) {
+        hipLaunchKernelGGL(vbx::linkage_prepare_kernel, dim3((unsigned)T), dim3(256), 0, st, sc->d_s, (long long)T);
+        double* cur = sc->d_s;
+        int *size_c = d_size, *size_a = d_size2, *orig_c = d_orig, *orig_a = d_orig2;
+        long long n_cur = T, done = 0;
+        auto compact_into = [&](double* dst, long long n_new) {           // the live clusters move up, in order
+            hipLaunchKernelGGL(vbx::linkage_compact_index_kernel, dim3(1), dim3(1024), 0, st, (int)n_cur, size_c, orig_c, d_chain,
+                               d_state, size_a, orig_a, d_old, d_newidx);
+            hipLaunchKernelGGL(vbx::linkage_compact_matrix_kernel, dim3((unsigned)n_new), dim3(256), 0, st, cur, (int)n_cur, dst,
+                               (int)n_new, d_old);
+            std::swap(size_c, size_a);
+            std::swap(orig_c, orig_a);
+            n_cur = n_new;
+        };
+        if (rounds) {
+            // rounds of reciprocal pairs on the matrix as it lies (dead rows and columns are skipped, not removed: a
+            // round reads n_live x n entries), until few clusters are left or a round hardly merges anything
+            int stalled = 0;
+            while (T - done > kRoundsStop && stalled < 3) {
+                const int n = (int)T;
+                hipLaunchKernelGGL(vbx::rnn_rowmin_kernel, dim3((unsigned)n), dim3(256), 0, st, cur, n, size_c, d_nn, d_nnd);
+                hipLaunchKernelGGL(vbx::rnn_pairs_kernel, dim3(1), dim3(1024), 0, st, n, size_c, orig_c, d_nn, d_nnd, d_pairs, d_role,
+                                   d_merges, d_state);
+                call.launched();
+                int st_host[4] = {0, 0, 0, 0};
+                call.download(st_host, d_state, (size_t)4);
+                call.sync();
+                if (!call.ok()) break;
+                const int np = st_host[3];
+                if (np <= 0) break;                                        // (cannot happen: the smallest pair is reciprocal)
+                hipLaunchKernelGGL(vbx::rnn_rows_kernel, dim3((unsigned)np), dim3(256), 0, st, cur, n, size_c, d_pairs);
+                hipLaunchKernelGGL(vbx::rnn_cols_kernel, dim3((unsigned)n), dim3(256), 0, st, cur, n, size_c, d_role, d_pairs, d_state);
+                hipLaunchKernelGGL(vbx::rnn_canon_kernel, dim3((unsigned)np), dim3(256), 0, st, cur, n, d_pairs, d_state);
+                hipLaunchKernelGGL(vbx::rnn_sizes_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, size_c, d_pairs, d_state);
+                call.launched();
+                stalled = ((long long)np * 64 < T - done) ? stalled + 1 : 0;
+                done = st_host[2];
+            }
+            if (call.ok() && done < T - 1) {                               // what is left goes to the chain, compacted
+                const long long n_new = T - done;
+                double* d_cmp = call.alloc<double>((size_t)(n_new * n_new));
+                if (call.ok()) {
+                    compact_into(d_cmp, n_new);
+                    cur = d_cmp;
                 }
             }
-            if (rc == VBX_OK && e == hipSuccess && done < T - 1) {
-                const bool stages = n_cur >= 2 * kStageMin;
-                const long long n_alt = stages ? n_cur - n_cur / 4 : 0;
-                if (stages) rc = dmalloc(ctx, &d_alt, (size_t)(n_alt * n_alt));
-                double* alt = d_alt;
-                while (rc == VBX_OK && done < T - 1) {
-                    const long long remaining = T - 1 - done;
-                    const long long m = (stages && n_cur >= 2 * kStageMin) ? std::min(remaining, n_cur / 4) : remaining;
-                    hipLaunchKernelGGL(vbx::nn_chain_kernel, dim3(1), dim3(1024), 0, st, cur, (int)n_cur, size_c, d_chain, orig_c,
-                                       d_state, d_merges, (int)done, (int)(done + m));
-                    done += m;
-                    if (done < T - 1) {
-                        compact_into(alt, n_cur - m);
-                        std::swap(cur, alt);
-                    }
-                }
-            }
-            if (e == hipSuccess) e = hipGetLastError();
         }
-        if (rc == VBX_OK && e == hipSuccess) e = hipMemcpyAsync(merges.data(), d_merges, sizeof(vbx::ChainMerge) * merges.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (call.ok() && done < T - 1) {
+            const bool stages = n_cur >= 2 * kStageMin;
+            const long long n_alt = stages ? n_cur - n_cur / 4 : 0;
+            double* alt = stages ? call.alloc<double>((size_t)(n_alt * n_alt)) : nullptr;
+            while (call.ok() && done < T - 1) {
+                const long long remaining = T - 1 - done;
+                const long long m = (stages && n_cur >= 2 * kStageMin) ? std::min(remaining, n_cur / 4) : remaining;
+                hipLaunchKernelGGL(vbx::nn_chain_kernel, dim3(1), dim3(1024), 0, st, cur, (int)n_cur, size_c, d_chain, orig_c, d_state,
+                                   d_merges, (int)done, (int)(done + m));
+                done += m;
+                if (done < T - 1) {
+                    compact_into(alt, n_cur - m);
+                    std::swap(cur, alt);
+                }
+            }
+        }
+        call.launched();
     }
-    for (void* p : {(void*)d_size2, (void*)d_orig, (void*)d_orig2, (void*)d_old, (void*)d_newidx, (void*)d_state, (void*)d_alt,
-                    (void*)d_cmp, (void*)d_nn, (void*)d_nnd, (void*)d_role, (void*)d_pairs})
-        ctx_free(ctx, p);
-    ctx_free(ctx, d_size);
-    ctx_free(ctx, d_chain);
-    ctx_free(ctx, d_merges);
-    if (rc != VBX_OK) return rc;
-    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "device linkage failed: %s", hipGetErrorString(e));
+    call.download((vbx::ChainMergeDev*)merges.data(), d_merges, merges.size());
+    call.sync();
+    if (int rc = call.finish("device linkage failed")) return rc;
     vbx::finish_linkage(T, merges.data(), Z);
     return VBX_OK;
 }
@@ -476,18 +430,15 @@ int vbx_scores_get_condensed(vbx_scores* sc, int64_t T, double scale, double* ou
     if (T == 1) return VBX_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t m = (size_t)T * (size_t)(T - 1) / 2;
-    double* d_c = nullptr;
-    int rc = dmalloc(ctx, &d_c, m);
-    if (rc != VBX_OK) return rc;
-    hipLaunchKernelGGL(vbx::condense_kernel, dim3((unsigned)(T - 1)), dim3(256), 0, ctx->stream, sc->d_s, d_c, (long long)T, scale);
-    hipError_t e = hipMemcpyAsync(out, d_c, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    ctx_free(ctx, d_c);
-    if (e != hipSuccess) {
-        ctx->err = std::string("vbx_scores_get_condensed: ") + hipGetErrorString(e);
-        return VBX_ERR_HIP;
+    DeviceCall call(ctx);
+    double* d_c = call.alloc<double>(m);
+    if (call.ok()) {
+        hipLaunchKernelGGL(vbx::condense_kernel, dim3((unsigned)(T - 1)), dim3(256), 0, call.st, sc->d_s, d_c, (long long)T, scale);
+        call.launched();
     }
-    return VBX_OK;
+    call.download(out, d_c, m);
+    call.sync();
+    return call.finish("vbx_scores_get_condensed");
 }
 
 int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, double* llr) {
@@ -495,15 +446,14 @@ int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, 
     vbx_ctx* ctx = sc->ctx;
     if (niters < 1 || !threshold) FAIL(ctx, VBX_ERR_INVALID, "vbx_scores_two_gmm_calib: niters must be >= 1");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int nb = (int)std::min<long long>(vbx::kGmmPartials, (sc->n + 255) / 256);
-    double *d_par = nullptr, *d_part = nullptr, *d_llr = nullptr;
-    int rc = dmalloc(ctx, &d_par, 16);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)nb * 6);
-    if (rc == VBX_OK && llr) rc = dmalloc(ctx, &d_llr, (size_t)sc->n);
     double par[16];
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
+    DeviceCall call(ctx);
+    hipStream_t st = call.st;
+    const int nb = (int)std::min<long long>(vbx::kGmmPartials, (sc->n + 255) / 256);
+    double* d_par = call.alloc<double>(16);
+    double* d_part = call.alloc<double>((size_t)nb * 6);
+    double* d_llr = llr ? call.alloc<double>((size_t)sc->n) : nullptr;
+    if (call.ok()) {
         hipLaunchKernelGGL((vbx::gmm_moment_kernel<0>), dim3(nb), dim3(256), 0, st, sc->d_s, sc->n, d_par, d_part);
         hipLaunchKernelGGL(vbx::gmm_init_kernel, dim3(1), dim3(256), 0, st, d_part, nb, sc->n, d_par, 0);
         hipLaunchKernelGGL((vbx::gmm_moment_kernel<1>), dim3(nb), dim3(256), 0, st, sc->d_s, sc->n, d_par, d_part);
@@ -513,24 +463,18 @@ int vbx_scores_two_gmm_calib(vbx_scores* sc, int32_t niters, double* threshold, 
             hipLaunchKernelGGL(vbx::gmm_update_kernel, dim3(1), dim3(256), 0, st, d_part, nb, d_par);
         }
         if (llr) hipLaunchKernelGGL(vbx::gmm_llr_kernel, dim3(nb), dim3(256), 0, st, sc->d_s, sc->n, d_par, d_llr);
-        e = hipMemcpyAsync(par, d_par, sizeof(double) * 16, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess && llr) e = hipMemcpy(llr, d_llr, sizeof(double) * (size_t)sc->n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("twoGMMcalib kernels failed: ") + hipGetErrorString(e);
-            rc = VBX_ERR_HIP;
-        }
+        call.launched();
     }
+    call.download(par, d_par, (size_t)16);
+    if (llr) call.download(llr, d_llr, (size_t)sc->n);
+    call.sync();
+    const int rc = call.finish("twoGMMcalib kernels failed");
     if (rc == VBX_OK) {
         // diarization_lib.py:30 with the final weights / means / var
         const double w0 = par[0], w1 = par[1], m0 = par[2], m1 = par[3], var = par[4];
         const double t0 = std::log(w0 * w0 / var) - m0 * m0 / var, t1 = std::log(w1 * w1 / var) - m1 * m1 / var;
         *threshold = -0.5 * (t0 - t1) / (m0 / var - m1 / var);
     }
-    ctx_free(ctx, d_par);
-    ctx_free(ctx, d_part);
-    ctx_free(ctx, d_llr);
     return rc;
 }
 
@@ -552,35 +496,25 @@ static int plda_covariance_impl(vbx_ctx* ctx, int64_t T, int32_t D, int ld, cons
     if (T > 200000) FAIL(ctx, VBX_ERR_UNSUPPORTED, "PLDA covariance: T=%lld rows, at most 200000", (long long)T);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int Dp = round_up(D, 16), nchunks = (int)((T + vbx::kCovChunk - 1) / vbx::kCovChunk);
-    double *d_x = nullptr, *d_sum = nullptr, *d_mean = nullptr, *d_part = nullptr, *d_cov = nullptr;
-    int rc = on_device ? VBX_OK : dmalloc(ctx, &d_x, (size_t)T * D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_sum, (size_t)nchunks * D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_mean, (size_t)D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)nchunks * Dp * Dp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_cov, (size_t)D * D);
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        hipError_t e = hipSuccess;
-        if (!on_device) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            const double* rows = on_device ? x : d_x;
-            const unsigned nb = (unsigned)((D + 63) / 64);
-            hipLaunchKernelGGL(vbx::cov_colsum_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, rows, (long long)T, (int)D, ld, d_sum);
-            hipLaunchKernelGGL(vbx::cov_mean_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, d_sum, nchunks, (long long)T, (int)D, d_mean);
-            hipLaunchKernelGGL(vbx::cov_partial_kernel, dim3(nb, nb, (unsigned)nchunks), dim3(256), 0, st, rows, d_mean, (long long)T, (int)D, ld, Dp, d_part);
-            hipLaunchKernelGGL(vbx::cov_finish_kernel, dim3((unsigned)((D * D + 255) / 256)), dim3(256), 0, st, d_part, nchunks, (long long)T, (int)D, Dp, d_cov);
-            e = hipMemcpyAsync(mean, d_mean, sizeof(double) * (size_t)D, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(cov, d_cov, sizeof(double) * (size_t)D * D, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("PLDA covariance kernels failed: ") + hipGetErrorString(e);
-            rc = VBX_ERR_HIP;
-        }
+    DeviceCall call(ctx);
+    hipStream_t st = call.st;
+    const double* rows = on_device ? x : call.upload(x, (size_t)T * D);
+    double* d_sum = call.alloc<double>((size_t)nchunks * D);
+    double* d_mean = call.alloc<double>((size_t)D);
+    double* d_part = call.alloc<double>((size_t)nchunks * Dp * Dp);
+    double* d_cov = call.alloc<double>((size_t)D * D);
+    if (call.ok()) {
+        const unsigned nb = (unsigned)((D + 63) / 64);
+        hipLaunchKernelGGL(vbx::cov_colsum_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, rows, (long long)T, (int)D, ld, d_sum);
+        hipLaunchKernelGGL(vbx::cov_mean_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, d_sum, nchunks, (long long)T, (int)D, d_mean);
+        hipLaunchKernelGGL(vbx::cov_partial_kernel, dim3(nb, nb, (unsigned)nchunks), dim3(256), 0, st, rows, d_mean, (long long)T, (int)D, ld, Dp, d_part);
+        hipLaunchKernelGGL(vbx::cov_finish_kernel, dim3((unsigned)((D * D + 255) / 256)), dim3(256), 0, st, d_part, nchunks, (long long)T, (int)D, Dp, d_cov);
+        call.launched();
     }
-    for (double* p : {d_x, d_sum, d_mean, d_part, d_cov}) ctx_free(ctx, p);
-    return rc;
+    call.download(mean, d_mean, (size_t)D);
+    call.download(cov, d_cov, (size_t)D * D);
+    call.sync();
+    return call.finish("PLDA covariance kernels failed");
 }
 
 int vbx_plda_covariance(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, double* mean, double* cov) {
@@ -621,42 +555,30 @@ static int plda_scores_impl(vbx_ctx* ctx, int64_t T, int32_t D, int ld, const do
     }
     kconst *= -0.5;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    double *d_x = nullptr, *d_model = nullptr, *d_a = nullptr, *d_g = nullptr;
     vbx_scores* sc = new vbx_scores();
     sc->ctx = ctx;
     sc->n = (long long)T * T;
-    int rc = on_device ? VBX_OK : dmalloc(ctx, &d_x, (size_t)T * D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_model, n_model);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_a, (size_t)T * dp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_g, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &sc->d_s, (size_t)sc->n);
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        hipError_t e = hipSuccess;
-        if (!on_device) e = hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)T * D, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_model, model.data(), sizeof(double) * n_model, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(vbx::plda_project_kernel, dim3((unsigned)((T + 15) / 16)), dim3(64), 0, st, on_device ? x : d_x,
-                               (long long)T, (int)D, ld, d_model, d_model + o_proj, (int)d, dp, d_model + o_w, d_model + o_sl,
-                               d_model + o_gam, d_a, d_g);
+    int rc;
+    {
+        DeviceCall call(ctx);
+        hipStream_t st = call.st;
+        const double* rows = on_device ? x : call.upload(x, (size_t)T * D);
+        const double* d_model = call.upload(model.data(), n_model);
+        double* d_a = call.alloc<double>((size_t)T * dp);
+        double* d_g = call.alloc<double>((size_t)T);
+        if (call.ok()) call.rc = dmalloc(ctx, &sc->d_s, (size_t)sc->n);
+        if (call.ok()) {
+            hipLaunchKernelGGL(vbx::plda_project_kernel, dim3((unsigned)((T + 15) / 16)), dim3(64), 0, st, rows, (long long)T, (int)D, ld,
+                               d_model, d_model + o_proj, (int)d, dp, d_model + o_w, d_model + o_sl, d_model + o_gam, d_a, d_g);
             const unsigned nb = (unsigned)((T + 63) / 64);
             hipLaunchKernelGGL(vbx::plda_score_gemm_kernel, dim3(nb, nb), dim3(256), 0, st, d_a, d_a, d_g, d_g, kconst, sc->d_s,
                                (long long)T, (long long)T, dp);
-            e = hipStreamSynchronize(st);
+            call.launched();
         }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("PLDA score kernels failed: ") + hipGetErrorString(e);
-            rc = VBX_ERR_HIP;
-        }
-    }
-    for (double* p : {d_x, d_model, d_a, d_g}) ctx_free(ctx, p);
-    if (rc != VBX_OK) {
-        vbx_scores_destroy(sc);
-        return rc;
-    }
-    *out = sc;
-    return VBX_OK;
+        call.sync();
+        rc = call.finish("PLDA score kernels failed");
+    }                                             // (the scratch is back, the stream idle: the handle may go too)
+    return scores_result(sc, rc, out);
 }
 
 int vbx_plda_scores(vbx_ctx* ctx, int64_t T, int32_t D, const double* x, int32_t d, const double* mu, const double* proj,
@@ -691,39 +613,28 @@ int vbx_plda_score_lda(vbx_ctx* ctx, int64_t N, int64_t M, int32_t D, const doub
     }
     kconst *= -0.5;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    double *d_fe = nullptr, *d_ft = nullptr, *d_terms = nullptr, *d_a = nullptr, *d_b = nullptr, *d_r = nullptr, *d_c = nullptr,
-           *d_s = nullptr;
-    int rc = dmalloc(ctx, &d_fe, (size_t)N * D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_ft, (size_t)M * D);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_terms, terms.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_a, (size_t)N * dp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_b, (size_t)M * dp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_r, (size_t)N);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_c, (size_t)M);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_s, (size_t)N * (size_t)M);
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        hipError_t e = hipMemcpyAsync(d_fe, Fe, sizeof(double) * (size_t)N * D, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_ft, Ft, sizeof(double) * (size_t)M * D, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_terms, terms.data(), sizeof(double) * terms.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(vbx::plda_lda_rows_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, d_fe, (long long)N, (int)D,
-                               (const double*)d_terms, (const double*)(d_terms + D), dp, d_a, d_r);
-            hipLaunchKernelGGL(vbx::plda_lda_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, d_ft, (long long)M, (int)D,
-                               (const double*)nullptr, (const double*)(d_terms + D), dp, d_b, d_c);
-            hipLaunchKernelGGL(vbx::plda_score_gemm_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, st,
-                               d_a, d_b, d_r, d_c, kconst, d_s, (long long)N, (long long)M, dp);
-            e = hipMemcpyAsync(out, d_s, sizeof(double) * (size_t)N * (size_t)M, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            ctx->err = std::string("PLDA LDA-space score kernels failed: ") + hipGetErrorString(e);
-            rc = VBX_ERR_HIP;
-        }
+    DeviceCall call(ctx);
+    hipStream_t st = call.st;
+    const double* d_fe = call.upload(Fe, (size_t)N * D);
+    const double* d_ft = call.upload(Ft, (size_t)M * D);
+    const double* d_terms = call.upload(terms.data(), terms.size());
+    double* d_a = call.alloc<double>((size_t)N * dp);
+    double* d_b = call.alloc<double>((size_t)M * dp);
+    double* d_r = call.alloc<double>((size_t)N);
+    double* d_c = call.alloc<double>((size_t)M);
+    double* d_s = call.alloc<double>((size_t)N * (size_t)M);
+    if (call.ok()) {
+        hipLaunchKernelGGL(vbx::plda_lda_rows_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, d_fe, (long long)N, (int)D, d_terms,
+                           d_terms + D, dp, d_a, d_r);
+        hipLaunchKernelGGL(vbx::plda_lda_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, d_ft, (long long)M, (int)D,
+                           (const double*)nullptr, d_terms + D, dp, d_b, d_c);
+        hipLaunchKernelGGL(vbx::plda_score_gemm_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0, st, d_a,
+                           d_b, d_r, d_c, kconst, d_s, (long long)N, (long long)M, dp);
+        call.launched();
     }
-    for (double* p : {d_fe, d_ft, d_terms, d_a, d_b, d_r, d_c, d_s}) ctx_free(ctx, p);
-    return rc;
+    call.download(out, d_s, (size_t)N * (size_t)M);
+    call.sync();
+    return call.finish("PLDA LDA-space score kernels failed");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // vbx_host_steps.hpp -- C ABI: step-level entry points (forward_backward, mstep, loglik) the parity tests call
-// (one translation unit with vbx_capi.hip, which includes the parts in order; not a stand-alone header)
+// (one translation unit with vbx_capi.hip, which includes the parts in order, this one after vbx_host_call.hpp: the entry
+// points without a batch behind them keep their device scratch in a DeviceCall; not a stand-alone header)
 #pragma once
 extern "C" {
 
@@ -149,25 +150,18 @@ int fb_dense_impl(vbx_ctx* ctx, int64_t T, int32_t S, const double* lls, const d
             m1[(size_t)j * Sp + i] = a;                              // backward: M[k][o] = A[o][k]
         }
     }
-    R *d_m0 = nullptr, *d_m1 = nullptr, *d_b = nullptr, *d_v0 = nullptr, *d_ah = nullptr, *d_bh = nullptr, *d_fs = nullptr, *d_bs = nullptr;
-    int rc = dmalloc(ctx, &d_m0, m0.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_m1, m1.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_b, cells);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_v0, (size_t)Sp);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_ah, cells);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_bh, cells);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_fs, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_bs, (size_t)T);
-    auto release = [&]() {
-        for (void* p : {(void*)d_m0, (void*)d_m1, (void*)d_b, (void*)d_v0, (void*)d_ah, (void*)d_bh, (void*)d_fs, (void*)d_bs}) ctx_free(ctx, p);
-    };
-    if (rc != VBX_OK) { release(); return rc; }
-    hipStream_t st = ctx->stream;
-    hipError_t e = hipMemcpyAsync(d_m0, m0.data(), sizeof(R) * m0.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_m1, m1.data(), sizeof(R) * m1.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_b, bm.data(), sizeof(R) * cells, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_v0, v0.data(), sizeof(R) * Sp, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    std::vector<R> ah(cells), bh(cells), fs((size_t)T), bs((size_t)T);
+    DeviceCall call(ctx);
+    hipStream_t st = call.st;
+    const R* d_m0 = call.upload(m0.data(), m0.size());
+    const R* d_m1 = call.upload(m1.data(), m1.size());
+    const R* d_b = call.upload(bm.data(), cells);
+    const R* d_v0 = call.upload(v0.data(), (size_t)Sp);
+    R* d_ah = call.alloc<R>(cells);
+    R* d_bh = call.alloc<R>(cells);
+    R* d_fs = call.alloc<R>((size_t)T);
+    R* d_bs = call.alloc<R>((size_t)T);
+    if (call.ok()) {
 #define VBX_FB_DENSE(SP_) hipLaunchKernelGGL((fb_dense_kernel<R, SP_>), dim3(2), dim3(FbDenseCfg<SP_>::kThreads), 0, st, \
                                              d_m0, d_m1, d_b, d_v0, d_ah, d_bh, d_fs, d_bs, (int)T, (int)S)
         switch (Sp) {
@@ -182,16 +176,14 @@ int fb_dense_impl(vbx_ctx* ctx, int64_t T, int32_t S, const double* lls, const d
                 break;
         }
 #undef VBX_FB_DENSE
-        e = hipGetLastError();
+        call.launched();
     }
-    std::vector<R> ah(cells), bh(cells), fs((size_t)T), bs((size_t)T);
-    if (e == hipSuccess) e = hipMemcpyAsync(ah.data(), d_ah, sizeof(R) * cells, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(bh.data(), d_bh, sizeof(R) * cells, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(fs.data(), d_fs, sizeof(R) * (size_t)T, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(bs.data(), d_bs, sizeof(R) * (size_t)T, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    release();
-    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "forward_backward (dense): %s", hipGetErrorString(e));
+    call.download(ah.data(), d_ah, cells);
+    call.download(bh.data(), d_bh, cells);
+    call.download(fs.data(), d_fs, (size_t)T);
+    call.download(bs.data(), d_bs, (size_t)T);
+    call.sync();
+    if (int rc = call.finish("forward_backward (dense)")) return rc;
     // lfw[t] = log ahat[t] + sum_{u<=t} (log s_u + m_u);  lbw[t] = log bhat[t] + sum_{u>=t, u<T-1} log q_u + sum_{u>t} m_u
     double cum = 0.0;
     for (int64_t t = 0; t < T; ++t) {
@@ -315,38 +307,22 @@ int score_posteriors_impl(vbx_ctx* ctx, int64_t T, int32_t S, const double* gamm
     std::vector<R> gp;
     pack_matrix<R, double>(gp, gamma, T, S, Sp, (R)0);        // (fp32: rounded here, as a batch holds it)
     const size_t block = (size_t)2 * n_ref * Sp;
-    R* d_gamma = nullptr;
-    RecDesc* d_rd = nullptr;
-    ScoreRec* d_sr = nullptr;
-    int* d_lab = nullptr;
-    int2* d_items = nullptr;
-    double *d_part = nullptr, *d_hist = nullptr;
-    int rc = dmalloc(ctx, &d_gamma, gp.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rd, 1);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_sr, 1);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_lab, (size_t)T);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_items, items.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, block * sr.ngroups);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_hist, block);
     std::vector<double> padded(block);
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        e = hipMemcpyAsync(d_gamma, gp.data(), sizeof(R) * gp.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rd, &rd, sizeof rd, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_sr, &sr, sizeof sr, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_lab, ref, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_items, items.data(), sizeof(int2) * items.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            score_launch<R>(st, d_gamma, Sp, 1, 1, d_rd, d_sr, d_lab, d_items, (int)items.size(), n_ref, nullptr, 0, d_part, d_hist);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(padded.data(), d_hist, sizeof(double) * block, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    DeviceCall call(ctx);
+    R* d_gamma = call.upload(gp.data(), gp.size());
+    RecDesc* d_rd = call.upload(&rd, (size_t)1);
+    ScoreRec* d_sr = call.upload(&sr, (size_t)1);
+    int* d_lab = call.upload(ref, (size_t)T);
+    int2* d_items = call.upload(items.data(), items.size());
+    double* d_part = call.alloc<double>(block * sr.ngroups);
+    double* d_hist = call.alloc<double>(block);
+    if (call.ok()) {
+        score_launch<R>(call.st, d_gamma, Sp, 1, 1, d_rd, d_sr, d_lab, d_items, (int)items.size(), n_ref, nullptr, 0, d_part, d_hist);
+        call.launched();
     }
-    for (void* p : {(void*)d_gamma, (void*)d_rd, (void*)d_sr, (void*)d_lab, (void*)d_items, (void*)d_part, (void*)d_hist}) ctx_free(ctx, p);
-    if (rc != VBX_OK) return rc;
-    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "score kernels failed: %s", hipGetErrorString(e));
+    call.download(padded.data(), d_hist, block);
+    call.sync();
+    if (int rc = call.finish("score kernels failed")) return rc;
     for (size_t r = 0; r < (size_t)2 * n_ref; ++r) std::memcpy(conf + r * S, padded.data() + r * Sp, sizeof(double) * S);
     return VBX_OK;
 }

@@ -28,8 +28,9 @@
 // Its speaker is left out of the mask of speakers with a turn of positive duration that this kernel also reduces (an OR:
 // any order gives the same bits), which is how the host names the columns as score._Pair would.
 //
-// Totals: rttm_cells_kernel, rttm_acc_kernel, rttm_fin_kernel of vbx_rttm_score.hpp UNCHANGED, on RttmPair records whose
-// turn_off / edge_off point into what A and B wrote.  Between the two phases ONE small download: (turns, edges, speaker
+// Totals: rttm_cells_kernel, rttm_acc_kernel, rttm_fin_kernel of vbx_rttm_score.hpp UNCHANGED, through that header's RttmPlan
+// (the same planning and launch code as vbx_rttm_score), on RttmPair records whose turn_off / edge_off point into what A and
+// B wrote.  Between the two phases ONE small download: (turns, edges, speaker
 // mask) per hypothesis, 16 bytes each; the grids are then exact, as in vbx_rttm_score, and not an upper bound.
 // No atomics anywhere: every sum and every scan runs in a fixed order, a hypothesis gives the same bytes in any batch.
 #pragma once
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void labels_edges_kernel(const LabRec* __restr
 
 }  // namespace vbx
 
-// ---- host glue (included by vbx_capi.hip after vbx_rttm_score.hpp) ----------------------------------------------------------
+// ---- host glue (included by vbx_capi.hip after vbx_host_call.hpp and vbx_rttm_score.hpp, whose RttmPlan phase 2 runs) -------
 extern "C" {
 
 int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, const double* seg_times, const double* ref_turns,
@@ -212,7 +213,6 @@ int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, con
                      double collar, int ignore_overlaps, double* out, int32_t* info) {
     using vbx::LabHyp;
     using vbx::LabRec;
-    using vbx::RttmPair;
     if (!ctx) return VBX_ERR_INVALID;
     if (n_rec <= 0 || n_hyp <= 0 || !rec_counts || !seg_times || !ref_edges || !hyp || !labels || !out)
         FAIL(ctx, VBX_ERR_INVALID, "vbx_labels_score: bad argument");
@@ -245,10 +245,7 @@ int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, con
             if (i > 0 && (st[i] < st[i - 1] || en[i] < en[i - 1]))
                 FAIL(ctx, VBX_ERR_INVALID, "vbx_labels_score: recording %d: times decrease at segment %d", r, i);
         }
-        for (int t = 0; t < nrt; ++t) {
-            const int sp = ref_spk[n_rturns + t];
-            if (sp < 0 || sp >= nr) FAIL(ctx, VBX_ERR_INVALID, "vbx_labels_score: recording %d: speaker %d of reference turn %d outside [0, %d)", r, sp, t, nr);
-        }
+        if (int bad = check_turn_speakers(ctx, "vbx_labels_score", "recording", r, "reference turn", ref_spk + n_rturns, 0, nrt, nr)) return bad;
         const double* ed = ref_edges + n_redges;
         for (int k = 0; k < nre; ++k)
             if (!std::isfinite(ed[k]) || (k > 0 && !(ed[k - 1] < ed[k])))
@@ -261,7 +258,7 @@ int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, con
     }
     // ---- the hypotheses ----
     std::vector<LabHyp> hyps((size_t)n_hyp);
-    long long n_lab = 0, n_turns = 0, n_edges = 0, n_pre = 0, n_out = 0;
+    long long n_lab = 0, n_turns = 0, n_edges = 0, n_pre = 0;
     for (int h = 0; h < n_hyp; ++h) {
         const int r = hyp[2 * (size_t)h], ns = hyp[2 * (size_t)h + 1];
         if (r < 0 || r >= n_rec) FAIL(ctx, VBX_ERR_INVALID, "vbx_labels_score: hypothesis %d names recording %d of %d", h, r, n_rec);
@@ -284,131 +281,53 @@ int vbx_labels_score(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, con
         n_turns += (long long)rc.n_ref_turns + rc.T;
         n_edges += (long long)rc.n_ref_edges + 2LL * rc.T;
         n_pre += 2LL * rc.T + 1;
-        n_out += vbx::kRttmTotals + (long long)rc.n_ref * ns;
     }
     if (n_turns > 0x7fffffffLL || n_edges > 0x7fffffffLL)
         FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_labels_score: %lld edges, %lld turns in one call", n_edges, n_turns);
-    std::vector<double> rb((size_t)n_rturns), re((size_t)n_rturns);   // reference turns arrive as [n][2]; the kernels read two planes
-    for (long long t = 0; t < n_rturns; ++t) {
-        rb[(size_t)t] = ref_turns[2 * t];
-        re[(size_t)t] = ref_turns[2 * t + 1];
-    }
+    const TurnPlanes rt(ref_turns, n_rturns);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    LabRec* d_recs = nullptr;
-    LabHyp* d_hyps = nullptr;
-    RttmPair* d_pairs = nullptr;
-    int2 *d_cls = nullptr, *d_acc = nullptr;
-    double *d_seg = nullptr, *d_rb = nullptr, *d_re = nullptr, *d_redges = nullptr, *d_tb = nullptr, *d_te = nullptr, *d_edges = nullptr;
-    double *d_w = nullptr, *d_part = nullptr, *d_out = nullptr;
-    int *d_rspk = nullptr, *d_lab = nullptr, *d_spk = nullptr, *d_pre = nullptr, *d_info = nullptr;
-    unsigned long long *d_r = nullptr, *d_s = nullptr;
     std::vector<int32_t> counts((size_t)n_hyp * vbx::kLabInfo);
+    RttmPlan pl;
+    DeviceCall call(ctx);                         // (after every host buffer its copies read or write)
     // ---- phase 1: turns and edges of every hypothesis ----
-    int rc = dmalloc(ctx, &d_recs, recs.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_hyps, hyps.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_seg, (size_t)(2 * n_seg));
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rb, (size_t)n_rturns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_re, (size_t)n_rturns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rspk, (size_t)n_rturns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_redges, (size_t)n_redges);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_lab, (size_t)n_lab);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_tb, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_te, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_spk, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_edges, (size_t)n_edges);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_pre, (size_t)n_pre);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_info, counts.size());
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        e = hipMemcpyAsync(d_recs, recs.data(), sizeof(LabRec) * recs.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_hyps, hyps.data(), sizeof(LabHyp) * hyps.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_seg, seg_times, sizeof(double) * (size_t)(2 * n_seg), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_rturns) e = hipMemcpyAsync(d_rb, rb.data(), sizeof(double) * (size_t)n_rturns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_rturns) e = hipMemcpyAsync(d_re, re.data(), sizeof(double) * (size_t)n_rturns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_rturns) e = hipMemcpyAsync(d_rspk, ref_spk, sizeof(int32_t) * (size_t)n_rturns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_redges, ref_edges, sizeof(double) * (size_t)n_redges, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_lab, labels, sizeof(int32_t) * (size_t)n_lab, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(vbx::labels_turns_kernel, dim3((unsigned)n_hyp), dim3(256), 0, st, d_recs, d_hyps, d_seg, d_lab, d_rb, d_re,
-                               d_rspk, d_tb, d_te, d_spk, d_info);
-            hipLaunchKernelGGL(vbx::labels_edges_kernel, dim3((unsigned)n_hyp), dim3(256), 0, st, d_recs, d_hyps, d_redges, d_tb, d_te,
-                               d_spk, d_edges, d_pre, d_info);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_info, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const LabRec* d_recs = call.upload(recs.data(), recs.size());
+    const LabHyp* d_hyps = call.upload(hyps.data(), hyps.size());
+    const double* d_seg = call.upload(seg_times, (size_t)(2 * n_seg));
+    const double* d_rb = call.upload(rt.beg.data(), (size_t)n_rturns);
+    const double* d_re = call.upload(rt.end.data(), (size_t)n_rturns);
+    const int* d_rspk = call.upload(ref_spk, (size_t)n_rturns);
+    const double* d_redges = call.upload(ref_edges, (size_t)n_redges);
+    const int* d_lab = call.upload(labels, (size_t)n_lab);
+    double* d_tb = call.alloc<double>((size_t)n_turns);
+    double* d_te = call.alloc<double>((size_t)n_turns);
+    int* d_spk = call.alloc<int>((size_t)n_turns);
+    double* d_edges = call.alloc<double>((size_t)n_edges);
+    int* d_pre = call.alloc<int>((size_t)n_pre);
+    int* d_info = call.alloc<int>(counts.size());
+    if (call.ok()) {
+        hipLaunchKernelGGL(vbx::labels_turns_kernel, dim3((unsigned)n_hyp), dim3(256), 0, call.st, d_recs, d_hyps, d_seg, d_lab, d_rb,
+                           d_re, d_rspk, d_tb, d_te, d_spk, d_info);
+        hipLaunchKernelGGL(vbx::labels_edges_kernel, dim3((unsigned)n_hyp), dim3(256), 0, call.st, d_recs, d_hyps, d_redges, d_tb, d_te,
+                           d_spk, d_edges, d_pre, d_info);
+        call.launched();
     }
-    // ---- phase 2: the pairs of vbx_rttm_score on what phase 1 wrote, its three kernels unchanged ----
-    std::vector<RttmPair> pairs((size_t)n_hyp);
-    std::vector<int2> cls_items, acc_items;
-    long long n_cells = 0, n_part = 0, widest = 0;
-    int ycols = 1;
+    call.download(counts.data(), d_info, counts.size());
+    call.sync();
+    // ---- phase 2: the plan of vbx_rttm_score on what phase 1 wrote ----
     bool sane = true;
-    if (rc == VBX_OK && e == hipSuccess) {
-        long long out_off = 0;
-        for (int h = 0; h < n_hyp; ++h) {
-            const LabHyp& hy = hyps[h];
-            const LabRec& rec = recs[hy.rec];
-            const int nt = counts[(size_t)h * vbx::kLabInfo], ne = counts[(size_t)h * vbx::kLabInfo + 1];
-            if (nt < 1 || nt > rec.T || ne < rec.n_ref_edges || ne > rec.n_ref_edges + 2 * nt) {
-                sane = false;                                         // (what came back would index past its room)
-                break;
-            }
-            RttmPair& pr = pairs[h];
-            pr.edge_off = hy.edge_off;
-            pr.cell_off = n_cells;
-            pr.turn_off = hy.turn_off;
-            pr.part_off = n_part;
-            pr.out_off = out_off;
-            pr.n_cells = ne - 1;
-            pr.n_ref_turns = rec.n_ref_turns;
-            pr.n_sys_turns = nt;
-            pr.n_ref = rec.n_ref;
-            pr.n_sys = hy.n_sys;
-            pr.ngroups = (pr.n_cells + vbx::kRttmGroupCells - 1) / vbx::kRttmGroupCells;
-            const long long block = vbx::kRttmTotals + (long long)pr.n_ref * pr.n_sys;
-            for (int b = 0; b * vbx::kRttmClsBlock < pr.n_cells; ++b) cls_items.push_back(make_int2(h, b));
-            for (int g = 0; g < pr.ngroups; ++g) acc_items.push_back(make_int2(h, g));
-            n_cells += pr.n_cells;
-            n_part += block * pr.ngroups;
-            out_off += block;
-            widest = std::max(widest, block);
-            ycols = std::max(ycols, (pr.n_sys + vbx::kRttmCols - 1) / vbx::kRttmCols);
-        }
-        if (sane && (n_cells > 0x7fffffffLL || cls_items.size() > 0x7fffffffULL)) sane = false;
+    for (int h = 0; call.ok() && sane && h < n_hyp; ++h) {
+        const LabHyp& hy = hyps[h];
+        const LabRec& rec = recs[hy.rec];
+        const int nt = counts[(size_t)h * vbx::kLabInfo], ne = counts[(size_t)h * vbx::kLabInfo + 1];
+        sane = nt >= 1 && nt <= rec.T && ne >= rec.n_ref_edges && ne <= rec.n_ref_edges + 2 * nt;   // (else it would index past its room)
+        if (sane) rttm_plan_add(pl, ne - 1, rec.n_ref_turns, nt, rec.n_ref, hy.n_sys, hy.edge_off, hy.turn_off);
     }
-    if (rc == VBX_OK && e == hipSuccess && sane) {
-        rc = dmalloc(ctx, &d_pairs, pairs.size());
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_cls, cls_items.size());
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_acc, acc_items.size());
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_r, (size_t)n_cells);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_s, (size_t)n_cells);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_w, (size_t)n_cells);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)n_part);
-        if (rc == VBX_OK) rc = dmalloc(ctx, &d_out, (size_t)n_out);
-        if (rc == VBX_OK) {
-            e = hipMemcpyAsync(d_pairs, pairs.data(), sizeof(RttmPair) * pairs.size(), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_cls, cls_items.data(), sizeof(int2) * cls_items.size(), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_acc, acc_items.data(), sizeof(int2) * acc_items.size(), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(vbx::rttm_cells_kernel, dim3((unsigned)cls_items.size()), dim3(256), 0, st, d_pairs, d_cls, d_edges, d_tb,
-                                   d_te, d_spk, collar, ignore_overlaps ? 1 : 0, d_r, d_s, d_w);
-                hipLaunchKernelGGL(vbx::rttm_acc_kernel, dim3((unsigned)acc_items.size(), (unsigned)ycols), dim3(256), 0, st, d_pairs, d_acc,
-                                   d_r, d_s, d_w, d_part);
-                hipLaunchKernelGGL(vbx::rttm_fin_kernel, dim3((unsigned)n_hyp, (unsigned)((widest + 255) / 256)), dim3(256), 0, st, d_pairs,
-                                   d_part, d_out);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
+    if (pl.n_cells > 0x7fffffffLL || pl.cls_items.size() > 0x7fffffffULL) sane = false;
+    if (sane) {
+        rttm_plan_run(call, pl, d_edges, d_tb, d_te, d_spk, collar, ignore_overlaps, out);
+        call.sync();
     }
-    for (void* p : {(void*)d_recs, (void*)d_hyps, (void*)d_pairs, (void*)d_cls, (void*)d_acc, (void*)d_seg, (void*)d_rb, (void*)d_re,
-                    (void*)d_redges, (void*)d_tb, (void*)d_te, (void*)d_edges, (void*)d_w, (void*)d_part, (void*)d_out, (void*)d_rspk,
-                    (void*)d_lab, (void*)d_spk, (void*)d_pre, (void*)d_info, (void*)d_r, (void*)d_s}) ctx_free(ctx, p);
-    if (rc != VBX_OK) return rc;
-    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "labels score kernels failed: %s", hipGetErrorString(e));
+    if (int rc = call.finish("labels score kernels failed")) return rc;
     if (!sane) FAIL(ctx, VBX_ERR_HIP, "vbx_labels_score: the turn or edge counts that came back do not fit their room");
     if (info) std::memcpy(info, counts.data(), sizeof(int32_t) * counts.size());
     return VBX_OK;

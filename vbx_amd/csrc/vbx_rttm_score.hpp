@@ -176,19 +176,82 @@ __global__ __launch_bounds__(256) void rttm_fin_kernel(const RttmPair* __restric
 
 }  // namespace vbx
 
-// ---- host glue (included by vbx_capi.hip after the allocator of vbx_host_launch.hpp) --------------------------------------
+// ---- host glue (included by vbx_capi.hip after vbx_host_call.hpp) ------------------------------------------------------------
+namespace {
+
+// What the three kernels run on: the pairs, the work items of rttm_cells and rttm_acc, the sizes of what they write and the
+// grids of rttm_acc (ycols) and rttm_fin (widest).  vbx_rttm_score plans on turns and edges of the host, vbx_labels_score on
+// those its first phase left on the device: one plan, so a pair is cut the same way whichever way it came.
+struct RttmPlan {
+    std::vector<vbx::RttmPair> pairs;
+    std::vector<int2> cls_items, acc_items;
+    long long n_cells = 0, n_part = 0, n_out = 0, widest = 0;
+    int ycols = 1;
+};
+
+// the next pair: n_cells cells on the n_cells + 1 edges from edge_off; n_ref_turns, then n_sys_turns turns from turn_off
+void rttm_plan_add(RttmPlan& pl, int n_cells, int n_ref_turns, int n_sys_turns, int n_ref, int n_sys, long long edge_off,
+                   long long turn_off) {
+    const int p = (int)pl.pairs.size();
+    vbx::RttmPair pr;
+    pr.edge_off = edge_off;
+    pr.cell_off = pl.n_cells;
+    pr.turn_off = turn_off;
+    pr.part_off = pl.n_part;
+    pr.out_off = pl.n_out;
+    pr.n_cells = n_cells;
+    pr.n_ref_turns = n_ref_turns;
+    pr.n_sys_turns = n_sys_turns;
+    pr.n_ref = n_ref;
+    pr.n_sys = n_sys;
+    pr.ngroups = (n_cells + vbx::kRttmGroupCells - 1) / vbx::kRttmGroupCells;
+    const long long block = vbx::kRttmTotals + (long long)n_ref * n_sys;
+    for (int b = 0; b * vbx::kRttmClsBlock < n_cells; ++b) pl.cls_items.push_back(make_int2(p, b));
+    for (int g = 0; g < pr.ngroups; ++g) pl.acc_items.push_back(make_int2(p, g));
+    pl.pairs.push_back(pr);
+    pl.n_cells += n_cells;
+    pl.n_part += block * pr.ngroups;
+    pl.n_out += block;
+    pl.widest = std::max(pl.widest, block);
+    pl.ycols = std::max(pl.ycols, (n_sys + vbx::kRttmCols - 1) / vbx::kRttmCols);
+}
+
+// the plan goes up, the three kernels run on the edges and turns in HBM, out [n_out] comes back (enqueued, not waited for)
+void rttm_plan_run(DeviceCall& call, const RttmPlan& pl, const double* d_edges, const double* d_tb, const double* d_te,
+                   const int* d_spk, double collar, int ignore_overlaps, double* out) {
+    const vbx::RttmPair* d_pairs = call.upload(pl.pairs.data(), pl.pairs.size());
+    const int2* d_cls = call.upload(pl.cls_items.data(), pl.cls_items.size());
+    const int2* d_acc = call.upload(pl.acc_items.data(), pl.acc_items.size());
+    auto* d_r = call.alloc<unsigned long long>((size_t)pl.n_cells);
+    auto* d_s = call.alloc<unsigned long long>((size_t)pl.n_cells);
+    double* d_w = call.alloc<double>((size_t)pl.n_cells);
+    double* d_part = call.alloc<double>((size_t)pl.n_part);
+    double* d_out = call.alloc<double>((size_t)pl.n_out);
+    if (call.ok()) {
+        if (!pl.cls_items.empty())
+            hipLaunchKernelGGL(vbx::rttm_cells_kernel, dim3((unsigned)pl.cls_items.size()), dim3(256), 0, call.st, d_pairs, d_cls, d_edges,
+                               d_tb, d_te, d_spk, collar, ignore_overlaps ? 1 : 0, d_r, d_s, d_w);
+        if (!pl.acc_items.empty())
+            hipLaunchKernelGGL(vbx::rttm_acc_kernel, dim3((unsigned)pl.acc_items.size(), (unsigned)pl.ycols), dim3(256), 0, call.st, d_pairs,
+                               d_acc, d_r, d_s, d_w, d_part);
+        hipLaunchKernelGGL(vbx::rttm_fin_kernel, dim3((unsigned)pl.pairs.size(), (unsigned)((pl.widest + 255) / 256)), dim3(256), 0, call.st,
+                           d_pairs, d_part, d_out);
+        call.launched();
+    }
+    call.download(out, d_out, (size_t)pl.n_out);
+}
+
+}  // namespace
+
 extern "C" {
 
 int vbx_rttm_score(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* edges, const double* turns,
                    const int32_t* spk, double collar, int ignore_overlaps, double* out) {
-    using vbx::RttmPair;
     if (!ctx) return VBX_ERR_INVALID;
     if (n_pairs <= 0 || !counts || !out) FAIL(ctx, VBX_ERR_INVALID, "vbx_rttm_score: bad argument");
     if (!(collar >= 0.0) || !std::isfinite(collar)) FAIL(ctx, VBX_ERR_INVALID, "vbx_rttm_score: collar=%g is not a length", collar);
-    std::vector<RttmPair> pairs((size_t)n_pairs);
-    std::vector<int2> cls_items, acc_items;
-    long long n_edges = 0, n_cells = 0, n_turns = 0, n_part = 0, n_out = 0, widest = 0;
-    int ycols = 1;
+    RttmPlan pl;
+    long long n_edges = 0, n_turns = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const int32_t* c = counts + 5 * (size_t)p;
         const int ne = c[0], nrt = c[1], nst = c[2], nr = c[3], ns = c[4];
@@ -196,90 +259,26 @@ int vbx_rttm_score(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const d
             FAIL(ctx, VBX_ERR_INVALID, "vbx_rttm_score: pair %d: negative or oversized count", p);
         if (nr > vbx::kRttmMaxSpk || ns > vbx::kRttmMaxSpk)
             FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_rttm_score: pair %d has %d reference and %d system speakers, at most %d a side", p, nr, ns, vbx::kRttmMaxSpk);
-        RttmPair& pr = pairs[p];
-        pr.edge_off = n_edges;
-        pr.cell_off = n_cells;
-        pr.turn_off = n_turns;
-        pr.part_off = n_part;
-        pr.out_off = n_out;
-        pr.n_cells = ne > 0 ? ne - 1 : 0;
-        pr.n_ref_turns = nrt;
-        pr.n_sys_turns = nst;
-        pr.n_ref = nr;
-        pr.n_sys = ns;
-        pr.ngroups = (pr.n_cells + vbx::kRttmGroupCells - 1) / vbx::kRttmGroupCells;
-        const long long block = vbx::kRttmTotals + (long long)nr * ns;
         if (nrt + nst > 0 && (!turns || !spk)) FAIL(ctx, VBX_ERR_INVALID, "vbx_rttm_score: NULL argument");
-        for (long long t = 0; t < (long long)nrt + nst; ++t) {           // a speaker index is a shift count and a row on the device
-            const int sp = spk[n_turns + t], lim = t < nrt ? nr : ns;
-            if (sp < 0 || sp >= lim) FAIL(ctx, VBX_ERR_INVALID, "vbx_rttm_score: pair %d: speaker %d of turn %lld outside [0, %d)", p, sp, t, lim);
-        }
-        for (int b = 0; b * vbx::kRttmClsBlock < pr.n_cells; ++b) cls_items.push_back(make_int2(p, b));
-        for (int g = 0; g < pr.ngroups; ++g) acc_items.push_back(make_int2(p, g));
+        if (int rc = check_turn_speakers(ctx, "vbx_rttm_score", "pair", p, "turn", spk + n_turns, 0, nrt, nr)) return rc;
+        if (int rc = check_turn_speakers(ctx, "vbx_rttm_score", "pair", p, "turn", spk + n_turns + nrt, nrt, nst, ns)) return rc;
+        rttm_plan_add(pl, ne > 0 ? ne - 1 : 0, nrt, nst, nr, ns, n_edges, n_turns);
         n_edges += ne;
-        n_cells += pr.n_cells;
         n_turns += (long long)nrt + nst;
-        n_part += block * pr.ngroups;
-        n_out += block;
-        widest = std::max(widest, block);
-        ycols = std::max(ycols, (ns + vbx::kRttmCols - 1) / vbx::kRttmCols);
     }
     if (n_edges && !edges) FAIL(ctx, VBX_ERR_INVALID, "vbx_rttm_score: NULL argument");
-    if (n_cells > 0x7fffffffLL || n_turns > 0x7fffffffLL || cls_items.size() > 0x7fffffffULL)
-        FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_rttm_score: %lld cells, %lld turns in one call", n_cells, n_turns);
-    // turns arrive as [n][2] = (begin, end); the kernels read two planes
-    std::vector<double> tb((size_t)n_turns), te((size_t)n_turns);
-    for (long long t = 0; t < n_turns; ++t) {
-        tb[(size_t)t] = turns[2 * t];
-        te[(size_t)t] = turns[2 * t + 1];
-    }
+    if (pl.n_cells > 0x7fffffffLL || n_turns > 0x7fffffffLL || pl.cls_items.size() > 0x7fffffffULL)
+        FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_rttm_score: %lld cells, %lld turns in one call", pl.n_cells, n_turns);
+    const TurnPlanes tp(turns, n_turns);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    RttmPair* d_pairs = nullptr;
-    int2 *d_cls = nullptr, *d_acc = nullptr;
-    double *d_edges = nullptr, *d_tb = nullptr, *d_te = nullptr, *d_w = nullptr, *d_part = nullptr, *d_out = nullptr;
-    int* d_spk = nullptr;
-    unsigned long long *d_r = nullptr, *d_s = nullptr;
-    int rc = dmalloc(ctx, &d_pairs, pairs.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_cls, cls_items.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_acc, acc_items.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_edges, (size_t)n_edges);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_tb, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_te, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_spk, (size_t)n_turns);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_r, (size_t)n_cells);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_s, (size_t)n_cells);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_w, (size_t)n_cells);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)n_part);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_out, (size_t)n_out);
-    hipError_t e = hipSuccess;
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        e = hipMemcpyAsync(d_pairs, pairs.data(), sizeof(RttmPair) * pairs.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && !cls_items.empty()) e = hipMemcpyAsync(d_cls, cls_items.data(), sizeof(int2) * cls_items.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && !acc_items.empty()) e = hipMemcpyAsync(d_acc, acc_items.data(), sizeof(int2) * acc_items.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_edges) e = hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)n_edges, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_turns) e = hipMemcpyAsync(d_tb, tb.data(), sizeof(double) * (size_t)n_turns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_turns) e = hipMemcpyAsync(d_te, te.data(), sizeof(double) * (size_t)n_turns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && n_turns) e = hipMemcpyAsync(d_spk, spk, sizeof(int32_t) * (size_t)n_turns, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            if (!cls_items.empty())
-                hipLaunchKernelGGL(vbx::rttm_cells_kernel, dim3((unsigned)cls_items.size()), dim3(256), 0, st, d_pairs, d_cls, d_edges, d_tb,
-                                   d_te, d_spk, collar, ignore_overlaps ? 1 : 0, d_r, d_s, d_w);
-            if (!acc_items.empty())
-                hipLaunchKernelGGL(vbx::rttm_acc_kernel, dim3((unsigned)acc_items.size(), (unsigned)ycols), dim3(256), 0, st, d_pairs, d_acc,
-                                   d_r, d_s, d_w, d_part);
-            hipLaunchKernelGGL(vbx::rttm_fin_kernel, dim3((unsigned)n_pairs, (unsigned)((widest + 255) / 256)), dim3(256), 0, st, d_pairs,
-                               d_part, d_out);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    for (void* p : {(void*)d_pairs, (void*)d_cls, (void*)d_acc, (void*)d_edges, (void*)d_tb, (void*)d_te, (void*)d_spk, (void*)d_r,
-                    (void*)d_s, (void*)d_w, (void*)d_part, (void*)d_out}) ctx_free(ctx, p);
-    if (rc != VBX_OK) return rc;
-    if (e != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "RTTM score kernels failed: %s", hipGetErrorString(e));
-    return VBX_OK;
+    DeviceCall call(ctx);
+    const double* d_edges = call.upload(edges, (size_t)n_edges);
+    const double* d_tb = call.upload(tp.beg.data(), (size_t)n_turns);
+    const double* d_te = call.upload(tp.end.data(), (size_t)n_turns);
+    const int* d_spk = call.upload(spk, (size_t)n_turns);
+    rttm_plan_run(call, pl, d_edges, d_tb, d_te, d_spk, collar, ignore_overlaps, out);
+    call.sync();
+    return call.finish("RTTM score kernels failed");
 }
 
 }  // extern "C"

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void vad_pack_kernel(const VadRec* __restrict_
 
 }  // namespace vbx
 
-// ---- host glue (included by vbx_capi.hip after the allocator of vbx_host_launch.hpp) --------------------------------------
+// ---- host glue (included by vbx_capi.hip after vbx_host_call.hpp) ------------------------------------------------------------
 extern "C" {
 
 int vbx_vad_energy(vbx_ctx* ctx, int64_t n_samples, const int16_t* samples, int32_t n_rec, const int64_t* rec, int32_t winlen,
@@ -280,75 +280,62 @@ int vbx_vad_energy(vbx_ctx* ctx, int64_t n_samples, const int16_t* samples, int3
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // the samples are read as 16-byte chunks: the buffer ends on a chunk boundary (what lies past n_samples is masked out)
     const size_t n_pad = ((size_t)n_samples + 7) / 8 * 8;
-    short* d_smp = nullptr;
-    VadRec* d_recs = nullptr;
-    int2 *d_items = nullptr, *d_ra = nullptr, *d_rb = nullptr, *d_pack = nullptr;
-    long long* d_N = nullptr;
-    double *d_e = nullptr, *d_part = nullptr, *d_theta = nullptr;
-    unsigned char* d_raw = nullptr;
-    int* d_cnt = nullptr;
+    DeviceCall call(ctx);
+    hipStream_t st = call.st;
+    const unsigned grid = (unsigned)items.size();
+    short* d_smp = call.alloc<short>(n_pad);
+    VadRec* d_recs = call.alloc<VadRec>(recs.size());
+    int2* d_items = call.alloc<int2>(items.size());
+    int2* d_ra = call.alloc<int2>((size_t)slots);
+    int2* d_rb = call.alloc<int2>((size_t)slots);
+    int2* d_pack = call.alloc<int2>((size_t)slots);
+    long long* d_N = call.alloc<long long>((size_t)frames);
+    double* d_e = call.alloc<double>((size_t)frames);
+    double* d_part = call.alloc<double>((size_t)tiles);
+    double* d_theta = call.alloc<double>((size_t)n_rec);
+    unsigned char* d_raw = call.alloc<unsigned char>((size_t)frames);
+    int* d_cnt = call.alloc<int>((size_t)n_rec);
     hipEvent_t ev[3] = {};
-    int rc = dmalloc(ctx, &d_smp, n_pad);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_recs, recs.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_items, items.size());
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_ra, (size_t)slots);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_rb, (size_t)slots);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_pack, (size_t)slots);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_N, (size_t)frames);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_e, (size_t)frames);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_part, (size_t)tiles);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_theta, (size_t)n_rec);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_raw, (size_t)frames);
-    if (rc == VBX_OK) rc = dmalloc(ctx, &d_cnt, (size_t)n_rec);
-    hipError_t err = hipSuccess;
-    long long total = 0;
-    if (rc == VBX_OK) {
-        hipStream_t st = ctx->stream;
-        const unsigned grid = (unsigned)items.size();
-        for (auto& x : ev)
-            if (err == hipSuccess && ms) err = hipEventCreate(&x);
-        if (err == hipSuccess && ms) err = hipEventRecord(ev[0], st);
-        if (err == hipSuccess && n_samples) err = hipMemcpyAsync(d_smp, samples, sizeof(short) * (size_t)n_samples, hipMemcpyHostToDevice, st);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_recs, recs.data(), sizeof(VadRec) * recs.size(), hipMemcpyHostToDevice, st);
-        if (err == hipSuccess && grid) err = hipMemcpyAsync(d_items, items.data(), sizeof(int2) * items.size(), hipMemcpyHostToDevice, st);
-        if (err == hipSuccess && ms) err = hipEventRecord(ev[1], st);
-        if (err == hipSuccess) {
-            if (grid && winlen == 400)
-                hipLaunchKernelGGL((vbx::vad_energy_kernel<400, 160>), dim3(grid), dim3(256), 0, st, d_smp, d_recs, d_items, d_N, d_e, d_part);
-            else if (grid)
-                hipLaunchKernelGGL((vbx::vad_energy_kernel<200, 80>), dim3(grid), dim3(256), 0, st, d_smp, d_recs, d_items, d_N, d_e, d_part);
-            hipLaunchKernelGGL(vbx::vad_theta_kernel, dim3((unsigned)n_rec), dim3(256), 0, st, d_recs, d_part, energy_threshold, mean_scale,
-                               d_theta);
-            if (grid)
-                hipLaunchKernelGGL(vbx::vad_raw_kernel, dim3(grid), dim3(256), 0, st, d_recs, d_items, d_e, d_theta, context, proportion,
-                                   d_raw);
-            hipLaunchKernelGGL(vbx::vad_runs_kernel, dim3((unsigned)n_rec), dim3(256), 0, st, d_recs, d_raw, min_silence, min_speech, pad,
-                               d_ra, d_rb, d_cnt);
-            hipLaunchKernelGGL(vbx::vad_pack_kernel, dim3((unsigned)n_rec), dim3(256), 0, st, d_recs, d_rb, d_cnt, d_pack);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess && ms) err = hipEventRecord(ev[2], st);
-        if (err == hipSuccess) err = hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * (size_t)n_rec, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess && N && frames) err = hipMemcpyAsync(N, d_N, sizeof(int64_t) * (size_t)frames, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess && e && frames) err = hipMemcpyAsync(e, d_e, sizeof(double) * (size_t)frames, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess && raw && frames) err = hipMemcpyAsync(raw, d_raw, (size_t)frames, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess && theta) err = hipMemcpyAsync(theta, d_theta, sizeof(double) * (size_t)n_rec, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);         // (the host tables above go out of scope; counts has landed)
-        if (err == hipSuccess) {
-            for (int r = 0; r < n_rec; ++r) total += counts[r];
-            if (total) err = hipMemcpyAsync(segs, d_pack, sizeof(int2) * (size_t)total, hipMemcpyDeviceToHost, st);
-            if (err == hipSuccess) err = hipStreamSynchronize(st);
-        }
-        if (err == hipSuccess && ms) err = hipEventElapsedTime(&ms[0], ev[0], ev[1]);
-        if (err == hipSuccess && ms) err = hipEventElapsedTime(&ms[1], ev[1], ev[2]);
+    auto stamp = [&](int i) {                                         // timing (ms given): an event in the stream, here
+        if (ms && call.ok()) call.enqueued(hipEventRecord(ev[i], st));
+    };
+    for (auto& x : ev)
+        if (ms && call.ok()) call.note(hipEventCreate(&x));
+    stamp(0);
+    call.copy_in(d_smp, (const short*)samples, (size_t)n_samples);    // (every block is there already: ms[0] times the uploads alone)
+    call.copy_in(d_recs, recs.data(), recs.size());
+    call.copy_in(d_items, items.data(), items.size());
+    stamp(1);
+    if (call.ok()) {
+        if (grid && winlen == 400)
+            hipLaunchKernelGGL((vbx::vad_energy_kernel<400, 160>), dim3(grid), dim3(256), 0, st, d_smp, d_recs, d_items, d_N, d_e, d_part);
+        else if (grid)
+            hipLaunchKernelGGL((vbx::vad_energy_kernel<200, 80>), dim3(grid), dim3(256), 0, st, d_smp, d_recs, d_items, d_N, d_e, d_part);
+        hipLaunchKernelGGL(vbx::vad_theta_kernel, dim3((unsigned)n_rec), dim3(256), 0, st, d_recs, d_part, energy_threshold, mean_scale,
+                           d_theta);
+        if (grid)
+            hipLaunchKernelGGL(vbx::vad_raw_kernel, dim3(grid), dim3(256), 0, st, d_recs, d_items, d_e, d_theta, context, proportion, d_raw);
+        hipLaunchKernelGGL(vbx::vad_runs_kernel, dim3((unsigned)n_rec), dim3(256), 0, st, d_recs, d_raw, min_silence, min_speech, pad, d_ra,
+                           d_rb, d_cnt);
+        hipLaunchKernelGGL(vbx::vad_pack_kernel, dim3((unsigned)n_rec), dim3(256), 0, st, d_recs, d_rb, d_cnt, d_pack);
+        call.launched();
     }
+    stamp(2);
+    call.download(counts, d_cnt, (size_t)n_rec);
+    if (N) call.download((long long*)N, d_N, (size_t)frames);
+    if (e) call.download(e, d_e, (size_t)frames);
+    if (raw) call.download(raw, d_raw, (size_t)frames);
+    if (theta) call.download(theta, d_theta, (size_t)n_rec);
+    call.sync();                                                      // (counts has landed)
+    long long total = 0;
+    for (int r = 0; call.ok() && r < n_rec; ++r) total += counts[r];
+    call.download((int2*)segs, d_pack, (size_t)total);
+    call.sync();
+    if (ms && call.ok()) call.note(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+    if (ms && call.ok()) call.note(hipEventElapsedTime(&ms[1], ev[1], ev[2]));
     for (auto& x : ev)
         if (x) (void)hipEventDestroy(x);
-    for (void* p : {(void*)d_smp, (void*)d_recs, (void*)d_items, (void*)d_ra, (void*)d_rb, (void*)d_pack, (void*)d_N, (void*)d_e,
-                    (void*)d_part, (void*)d_theta, (void*)d_raw, (void*)d_cnt}) ctx_free(ctx, p);
-    if (rc != VBX_OK) return rc;
-    if (err != hipSuccess) FAIL(ctx, VBX_ERR_HIP, "energy VAD kernels failed: %s", hipGetErrorString(err));
-    return VBX_OK;
+    return call.finish("energy VAD kernels failed");
 }
 
 }  // extern "C"
