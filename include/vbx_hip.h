@@ -511,6 +511,27 @@ int vbx_vad_energy(vbx_ctx* ctx, int64_t n_samples, const int16_t* samples, int3
 int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* extent, const double* turns,
                      const int32_t* spk, double step, int32_t* info, uint64_t* classes, int64_t* out, int64_t out_cap);
 
+/* ---- any PCM recording to mono int16 at 8 or 16 kHz (vbx_resample.hpp) -------------------------------------------------
+ * n_rec recordings of one sample format, channel count and rate pair, their raw interleaved little-endian frames laid end to
+ * end in bytes [n_bytes] as they lie in their files: rec [n_rec][2] = (first byte, frames) of each, at any byte offset.
+ *   format    0: u8, 1: s16, 2: s24, 3: s32, 4: f32;  channels 1 .. 8
+ * A sample becomes an integer q at 24-bit scale: u8 (b - 128) << 16, s16 x << 8, s24 x, s32 x >> 8 (floor), f32 NaN -> 0 and
+ * otherwise rint-half-even(x 2^23) clamped to [-2^23, 2^23 - 1].  X[j] = sum of q over the channels of frame j.
+ *   L, M      sr_out / g and sr_in / g, g their gcd; L <= 640, M <= 1024;  P = 32 max(L, M)
+ *   table     [L][taps] int32, taps = 2 P / L + 1: table[p][k] = hq[p + k L], 0 past hq[2 P], for the integer prototype
+ *             hq[0 .. 2 P] whose every phase {p, p + L, ...} sums to 2^24 and sum |hq| < 2^26 (vbx_amd/audio.py)
+ * A recording of n frames gives n_out = ceil(n L / M) samples,
+ *   acc[m] = sum_j X[j] hq[P + m M - j L] over the j in [0, n) with |m M - j L| <= P     (exact in int64)
+ *   y[m]   = clamp(floor((2 acc + D) / (2 D)), -32768, 32767),  D = channels 2^32        (round half up)
+ *   out  [sum n_out]     the samples, recording after recording
+ *   ms   [2]             device milliseconds of the upload and of the kernel (HIP events); may be NULL
+ * A recording's samples are the same bits alone, in any batch and at any place in it; nothing is read across a recording's
+ * ends.  VBX_ERR_INVALID with a message: a NULL pointer, n_rec <= 0, a format, channel count, L, M or taps outside the above,
+ * a recording outside the bytes.  VBX_ERR_UNSUPPORTED: more than 2^30 frames or samples in a recording, or an L, M whose tile
+ * of 256 outputs spans more than 8192 input frames (M / L above 25).  Synchronises before it returns. */
+int vbx_resample_pcm(vbx_ctx* ctx, int64_t n_bytes, const uint8_t* bytes, int32_t n_rec, const int64_t* rec, int32_t format,
+                     int32_t channels, int32_t L, int32_t M, int32_t taps, const int32_t* table, int16_t* out, float* ms);
+
 /* ---- filterbank front end of the x-vector extractor (predict.py:150-204 with features.py) -----------------------
  * Per VAD segment: mirror padding (predict.py:173-174), frames of winlen samples every shift, zero mean, pre-emphasis,
  * window, |rfft(., nfft)|^2, log(max(1, P mel)) (features.py:fbank_htk with USEPOWER, ZMEANSOURCE), then

@@ -38,6 +38,9 @@ VAD_TILE, VAD_RUN_PASS, VAD_RUN_BLOCK = 256, 4096, 256
 # vbx_frame_score.hpp: boundaries / cells / result entries per workgroup and per LDS chunk, speakers and classes per side
 # (kFrmBlock, kFrmMaxSpk, kFrmMaxCls)
 FRAME_BLOCK, FRAME_MAX_SPEAKERS, FRAME_MAX_CLASSES = 256, 64, 256
+# vbx_resample.hpp: outputs per workgroup, input frames of a tile staged in LDS, table entries up to which the table is staged
+# in LDS too (kRsTile, kRsSpan, kRsTabLds)
+RESAMPLE_TILE, RESAMPLE_SPAN, RESAMPLE_TABLE_LDS = 256, 8192, 1024
 
 ABI_SYMBOLS = [
     'vbx_abi_version', 'vbx_create', 'vbx_destroy', 'vbx_last_error', 'vbx_device_info',
@@ -65,6 +68,7 @@ ABI_SYMBOLS = [
     'vbx_rttm_score', 'vbx_labels_score',
     'vbx_vad_energy',
     'vbx_frame_counts',
+    'vbx_resample_pcm',
 ]
 
 
@@ -192,6 +196,7 @@ def load():
     lib.vbx_labels_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, dbl, C.c_int, vp, vp]
     lib.vbx_vad_energy.argtypes = [vp, i64, vp, i32, vp, i32, i32, dbl, dbl, i32, dbl, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.vbx_frame_counts.argtypes = [vp, i32, vp, vp, vp, vp, dbl, vp, vp, vp, i64]
+    lib.vbx_resample_pcm.argtypes = [vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1243,6 +1248,22 @@ def vad_energy(ctx: Context, samples, rec, winlen, shift, energy_threshold, mean
                                       int(min_speech), int(pad), _ptr(counts), _ptr(segs), _ptr(N), _ptr(e), _ptr(theta), _ptr(raw),
                                       _ptr(ms)), 'vbx_vad_energy')
     return counts, segs[:int(counts.sum())], det, ms
+
+
+def resample_pcm(ctx: Context, data, rec, fmt, channels, L, M, table, times=False):
+    """vbx_resample_pcm: ``data`` uint8 (the raw interleaved frames of the recordings end to end), ``rec`` int64 [n][2] =
+    (first byte, frames), ``fmt`` 0 .. 4 = u8, s16, s24, s32, f32, ``table`` int32 [L][taps] (audio.phase_table).
+    -> (int16 samples of all recordings end to end, ms): ms is None or the device milliseconds (upload, kernel)."""
+    data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    rec = np.ascontiguousarray(rec, dtype=np.int64).reshape(-1, 2)
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    assert table.ndim == 2 and table.shape[0] == L
+    n_out = -((-np.maximum(rec[:, 1], 0) * int(L)) // int(M))
+    out = np.empty(int(n_out.sum()), dtype=np.int16)
+    ms = np.zeros(2, dtype=np.float32) if times else None
+    ctx.check(ctx._lib.vbx_resample_pcm(ctx._h, data.size, _ptr(data), rec.shape[0], _ptr(rec), int(fmt), int(channels), int(L), int(M),
+                                        table.shape[1], _ptr(table), _ptr(out), _ptr(ms)), 'vbx_resample_pcm')
+    return out, ms
 
 
 def frame_counts(ctx: Context, counts, extent, turns, spk, step):

@@ -66,6 +66,9 @@ def build_parser():
     p.add_argument('--in-file-list', required=True, type=str, help='input list of files')
     p.add_argument('--in-lab-dir', required=True, type=str, help='input directory with VAD labels')
     p.add_argument('--in-wav-dir', required=True, type=str, help='input directory with wavs')
+    p.add_argument('--resample-to', type=int, default=None, choices=[8000, 16000], metavar='{8000,16000}',
+                   help='take wavs of any PCM format, channel count and rate (vbx_amd.audio) and convert them on the device to '
+                        'mono 16-bit at this rate first (default: only mono 16-bit wavs at 8 or 16 kHz are taken)')
     p.add_argument('--out-ark-fn', type=str, default=None, help="optional: also write predict's embedding file")
     p.add_argument('--out-seg-fn', type=str, default=None, help="optional: also write predict's segments file")
     p.add_argument('--batch-size', type=int, default=128, help='full windows per model call')
@@ -119,6 +122,8 @@ def _check(args, error):
         error('--seg-len, --seg-jump and --batch-size must be positive')
     if (args.out_ark_fn is None) != (args.out_seg_fn is None):
         error('--out-ark-fn and --out-seg-fn go together: pass both or neither')
+    if getattr(args, 'resample_to', None) not in (None, 8000, 16000):
+        error(f'--resample-to must be 8000 or 16000, got {args.resample_to}')
     if not 0 <= args.loopP <= 1:
         error(f'Expecting loopP between 0 and 1, got {args.loopP} instead.')
     if getattr(args, 'ref_rttm_dir', None) is not None:
@@ -234,7 +239,7 @@ def _run(args, file_names, log=print):
     if not torch.cuda.is_available() or device >= torch.cuda.device_count():
         raise SystemExit(f'--gpus {args.gpus}: no such GPU visible to PyTorch')
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-    nxt = pool.submit(predict._load, args, file_names[0]) if file_names else None
+    nxt = pool.submit(predict._read_ahead, args, file_names[0]) if file_names else None
     try:
         net = xvector.ResNet101.from_checkpoint(args.checkpoint, device, embed_dim=args.embed_dim, gemm=args.gemm)
     except (ValueError, OSError) as exc:
@@ -245,8 +250,9 @@ def _run(args, file_names, log=print):
     with torch.no_grad():
         for k, fn in enumerate(file_names):
             t0 = time.perf_counter()
-            sr, sig, segs = nxt.result()
-            nxt = pool.submit(predict._load, args, file_names[k + 1]) if k + 1 < len(file_names) else None
+            got = nxt.result()
+            nxt = pool.submit(predict._read_ahead, args, file_names[k + 1]) if k + 1 < len(file_names) else None
+            sr, sig, segs = predict._loaded(args, fn, got, device)        # (--resample-to: the conversion, on this thread)
             timing['read'] += time.perf_counter() - t0
             fe = fbank.front_end(sr, device)
             if dest is None:
@@ -297,7 +303,7 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
                   init='AHC+VB', threshold=-0.015, lda_dim=128, Fa=0.3, Fb=17.0, loopP=0.99, target_energy=1.0,
                   ahc_scores='cos', init_smoothing=5.0, output_2nd=False, precision='fp64', gemm='exact', embed_dim=256,
                   seg_len=144, seg_jump=24, batch_size=128, no_dither=False, dither='host', out_ark_fn=None, out_seg_fn=None,
-                  log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False):
+                  log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False, resample_to=None):
     """Diarize ``wav_dir/<name>.wav`` with the VAD labels ``lab_dir/<name>.lab`` for every name of ``file_names``.
 
     -> ``({recording: dict(labels1st, labels2nd, n_iters, thr, starts, ends)}, timing)``: per x-vector of the recording its
@@ -309,14 +315,17 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
 
     ``ref_rttm_dir`` (needs ``out_rttm_dir``): the RTTM files written are scored against ``<ref_rttm_dir>/<name>.rttm`` on the
     device with ``collar`` / ``ignore_overlaps`` (``vbx_amd.score``), the DER table is printed and every recording's entry
-    gets its ``der``.  Without it nothing is scored, printed or added."""
+    gets its ``der``.  Without it nothing is scored, printed or added.
+
+    ``resample_to`` (8000 or 16000): the wav files may be of any format ``vbx_amd.audio`` reads and are converted on the
+    device to mono int16 at that rate first.  Without it only mono 16-bit files at 8 or 16 kHz are taken."""
     args = argparse.Namespace(
         gpus=str(device), checkpoint=checkpoint, gemm=gemm, model=None, weights=None, model_file=None, backend='pytorch',
         ndim=fbank.N_MEL, embed_dim=embed_dim, seg_len=seg_len, seg_jump=seg_jump, in_file_list=None, in_lab_dir=lab_dir,
         in_wav_dir=wav_dir, out_ark_fn=out_ark_fn, out_seg_fn=out_seg_fn, batch_size=batch_size, no_dither=no_dither,
         dither=dither, init=init, out_rttm_dir=out_rttm_dir, xvec_transform=xvec_transform, plda_file=plda_file,
         threshold=threshold, lda_dim=lda_dim, Fa=Fa, Fb=Fb, loopP=loopP, target_energy=target_energy, ahc_scores=ahc_scores,
-        init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False)
+        init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False, resample_to=resample_to)
     if ref_rttm_dir is not None:
         args.ref_rttm_dir, args.collar, args.ignore_overlaps = ref_rttm_dir, collar, ignore_overlaps
     if init not in ('AHC', 'AHC+VB'):

@@ -56,6 +56,9 @@ def parse_args(argv=None):
     p.add_argument('--dither', default='host', choices=['host', 'device'],
                    help="where the dither is drawn: by numpy on the host (default), or by the front end's MT19937 kernel on "
                         'the device, to the same bits')
+    p.add_argument('--resample-to', type=int, default=None, choices=[8000, 16000], metavar='{8000,16000}',
+                   help='take wavs of any PCM format, channel count and rate (vbx_amd.audio) and convert them on the device to '
+                        'mono 16-bit at this rate first (default: only mono 16-bit wavs at 8 or 16 kHz are taken)')
     args = p.parse_args(argv)
     if args.no_dither and args.dither == 'device':
         p.error('--no-dither and --dither device exclude each other')
@@ -84,7 +87,30 @@ def _ark_entry(key: str, vec: np.ndarray) -> bytes:
 
 
 def _load(args, fn):
-    samples, sr = fbank.read_wav(os.path.join(args.in_wav_dir, fn) + '.wav', raw=args.dither == 'device')
+    return _prepare(args, fn, *fbank.read_wav(os.path.join(args.in_wav_dir, fn) + '.wav', raw=args.dither == 'device'))
+
+
+def _read_ahead(args, fn):
+    """What the reader thread does for a file: all of _load, or with --resample-to only the reading of its bytes (the
+    conversion is a device call, and those stay on the thread that owns the context: _loaded)."""
+    if getattr(args, 'resample_to', None) is None:
+        return _load(args, fn)
+    from . import audio
+    return audio.read_audio(os.path.join(args.in_wav_dir, fn) + '.wav')
+
+
+def _loaded(args, fn, got, device):
+    """_load's result from _read_ahead's: with --resample-to the bytes become mono int16 at that rate on the device, and
+    everything after sees them as if fbank.read_wav had read the converted file."""
+    if getattr(args, 'resample_to', None) is None:
+        return got
+    from . import audio
+    data, fmt, channels, sr, _frames = got
+    samples = audio.to_mono16([data], fmt, channels, sr, args.resample_to, device=device)[0]
+    return _prepare(args, fn, samples if args.dither == 'device' else samples.astype(np.int64), args.resample_to)
+
+
+def _prepare(args, fn, samples, sr):
     labs = fbank.read_lab(os.path.join(args.in_lab_dir, fn) + '.lab', sr)
     if args.dither == 'device':                  # the samples as read: embed_file has the device dither them
         return sr, samples, fbank.segments(labs, len(samples), sr)
@@ -172,12 +198,13 @@ def main(argv=None):
             return model(fe.windows(starts, length, out='torch')).detach().cpu().numpy()
     file_names = [str(f) for f in np.atleast_1d(np.loadtxt(args.in_file_list, dtype=object))]
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
-    nxt = pool.submit(_load, args, file_names[0]) if file_names else None
+    nxt = pool.submit(_read_ahead, args, file_names[0]) if file_names else None
     with torch.no_grad(), open(args.out_seg_fn, 'w') as seg_file, open(args.out_ark_fn, 'wb') as ark_file:
         for k, fn in enumerate(file_names):
             t0 = time.time()
-            sr, sig, segs = nxt.result()
-            nxt = pool.submit(_load, args, file_names[k + 1]) if k + 1 < len(file_names) else None
+            got = nxt.result()
+            nxt = pool.submit(_read_ahead, args, file_names[k + 1]) if k + 1 < len(file_names) else None
+            sr, sig, segs = _loaded(args, fn, got, device)
             fe = fbank.front_end(sr, device)
             for key, line, vec in embed_file(embed, fe, fn, sig, segs, sr, args, embed_ragged):
                 if np.isnan(vec).any():

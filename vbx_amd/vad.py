@@ -174,6 +174,9 @@ def build_parser():
     p.add_argument('--out-lab-dir', required=True, type=str, help='output directory for the VAD labels')
     p.add_argument('--out-file-list', type=str, default=None, help='write the names that got a .lab file (the --in-file-list of predict / diarize)')
     p.add_argument('--device', type=int, default=None, metavar='N', help='run on GPU N (default: in numpy on the host)')
+    p.add_argument('--resample-to', type=int, default=None, choices=[8000, 16000], metavar='{8000,16000}',
+                   help='take wavs of any PCM format, channel count and rate (vbx_amd.audio) and convert them to mono 16-bit at this '
+                        'rate first, where the VAD runs (default: only mono 16-bit wavs at 8 or 16 kHz are taken)')
     p.add_argument('--energy-threshold', type=float, default=DEFAULTS['energy_threshold'], help='constant term of the threshold on the log energy')
     p.add_argument('--mean-scale', type=float, default=DEFAULTS['mean_scale'], help="factor of the recording's mean log energy in the threshold")
     p.add_argument('--context', type=int, default=DEFAULTS['context'], help='frames on either side that vote on a frame')
@@ -203,7 +206,12 @@ def main(argv=None):
     try:
         _check(params)
         names = [str(f) for f in np.atleast_1d(np.loadtxt(args.in_file_list, dtype=object))]
-        wavs = [fbank.read_wav(os.path.join(args.in_wav_dir, f'{fn}.wav'), raw=True) for fn in names]
+        paths = [os.path.join(args.in_wav_dir, f'{fn}.wav') for fn in names]
+        if args.resample_to is None:
+            wavs = [fbank.read_wav(path, raw=True) for path in paths]
+        else:                            # any PCM wav, converted where the VAD runs; from here on as if the converted file had been read
+            from . import audio
+            wavs = [(x, args.resample_to) for x in audio.convert_files(paths, args.resample_to, device=args.device)]
     except (ValueError, OSError) as exc:
         ap.error(str(exc))
     os.makedirs(args.out_lab_dir, exist_ok=True)
