@@ -511,6 +511,26 @@ int vbx_vad_energy(vbx_ctx* ctx, int64_t n_samples, const int16_t* samples, int3
 int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* extent, const double* turns,
                      const int32_t* spk, double step, int32_t* info, uint64_t* classes, int64_t* out, int64_t out_cap);
 
+/* ---- ... of label sequences: many hypotheses per recording (vbx_labels_frame.hpp) ---------------------------------------
+ * What vbx_frame_counts gives for the turns of vbhmm.merge_adjacent_labels(starts, ends, labels), with the turns of every
+ * hypothesis built on the device and the reference's side uploaded and cut into frames once per recording.  Per recording r,
+ * rec_counts[r] = {T, n_ref_turns, n_ref}:
+ *   seg_times  starts[T] then ends[T], recording after recording; finite, starts[i] < ends[i], both non-decreasing
+ *   ref_turns  [n_ref_turns][2] = (begin, end) of its merged reference turns, begin <= end finite; ref_spk their speakers in
+ *              [0, n_ref)
+ * A hypothesis's extent is its recording's: lo = min(reference begins, starts[0]), hi = max(reference ends, ends[T - 1]);
+ * hi / step < 2^40.  Per hypothesis h, hyp[h] = {recording, n_sys} and the T labels of that recording in [0, n_sys),
+ * hypothesis after hypothesis; system speaker s is label s.  n_ref, n_sys <= 64 (more: VBX_ERR_UNSUPPORTED).
+ *   info, classes, out, out_cap   per hypothesis what vbx_frame_counts gives per pair, in that layout (a label that never
+ *              occurs: sys_durs 0 and a zero column of inter)
+ *   label_masks [n_hyp]           bit s: label s has a turn of positive duration
+ * All sums are integers, no atomics: a hypothesis's numbers are the same bytes alone, in any batch, at any place in it and
+ * among other hypotheses of its recording, and the bytes vbx_frame_counts gives for the same turns.  Everything the kernels
+ * index with is checked on the host before the first launch.  Synchronises before it returns. */
+int vbx_labels_frame_counts(vbx_ctx* ctx, int32_t n_rec, const int32_t* rec_counts, const double* seg_times, const double* ref_turns,
+                            const int32_t* ref_spk, int32_t n_hyp, const int32_t* hyp, const int32_t* labels, double step,
+                            int32_t* info, uint64_t* classes, int64_t* out, int64_t out_cap, uint64_t* label_masks);
+
 /* ---- any PCM recording to mono int16 at 8 or 16 kHz (vbx_resample.hpp) -------------------------------------------------
  * n_rec recordings of one sample format, channel count and rate pair, their raw interleaved little-endian frames laid end to
  * end in bytes [n_bytes] as they lie in their files: rec [n_rec][2] = (first byte, frames) of each, at any byte offset.

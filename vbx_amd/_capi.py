@@ -67,7 +67,7 @@ ABI_SYMBOLS = [
     'vbx_xvectors_project_device', 'vbx_rows_nan_flags',
     'vbx_rttm_score', 'vbx_labels_score',
     'vbx_vad_energy',
-    'vbx_frame_counts',
+    'vbx_frame_counts', 'vbx_labels_frame_counts',
     'vbx_resample_pcm',
 ]
 
@@ -196,6 +196,7 @@ def load():
     lib.vbx_labels_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, dbl, C.c_int, vp, vp]
     lib.vbx_vad_energy.argtypes = [vp, i64, vp, i32, vp, i32, i32, dbl, dbl, i32, dbl, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.vbx_frame_counts.argtypes = [vp, i32, vp, vp, vp, vp, dbl, vp, vp, vp, i64]
+    lib.vbx_labels_frame_counts.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, dbl, vp, vp, vp, i64, vp]
     lib.vbx_resample_pcm.argtypes = [vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
@@ -1286,6 +1287,36 @@ def frame_counts(ctx: Context, counts, extent, turns, spk, step):
         ctx.check(ctx._lib.vbx_frame_counts(ctx._h, n.shape[0], _ptr(counts), _ptr(extent), _ptr(turns), _ptr(spk), float(step),
                                             _ptr(info), _ptr(classes), _ptr(out), out.size), 'vbx_frame_counts')
     return info, classes, out
+
+
+def labels_frame_counts(ctx: Context, rec_counts, seg_times, ref_turns, ref_spk, hyp, labels, step):
+    """vbx_labels_frame_counts: ``rec_counts`` int32 [n_rec][3] = (T, reference turns, reference speakers) of every recording,
+    ``seg_times`` f64 (starts[T] then ends[T] per recording), ``ref_turns`` f64 [.][2], ``ref_spk`` int32, ``hyp`` int32
+    [n_hyp][2] = (recording, system speakers), ``labels`` int32, hypothesis after hypothesis.
+    -> (info, classes, out) per hypothesis as ``frame_counts`` gives them per pair, and uint64 [n_hyp]: the mask of the labels
+    with a turn of positive duration."""
+    rec_counts = np.ascontiguousarray(rec_counts, dtype=np.int32).reshape(-1, 3)
+    hyp = np.ascontiguousarray(hyp, dtype=np.int32).reshape(-1, 2)
+    seg_times, ref_turns = _f64(seg_times).reshape(-1), _f64(ref_turns).reshape(-1, 2)
+    ref_spk = np.ascontiguousarray(ref_spk, dtype=np.int32).reshape(-1)
+    labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    n_rec, n_hyp = rec_counts.astype(np.int64), hyp.astype(np.int64)
+    assert ((n_hyp[:, 0] >= 0) & (n_hyp[:, 0] < len(n_rec))).all(), 'a hypothesis names a recording that is not there'
+    assert seg_times.size == 2 * n_rec[:, 0].sum() and ref_turns.shape[0] == ref_spk.size == n_rec[:, 1].sum()
+    assert labels.size == n_rec[n_hyp[:, 0], 0].sum()
+    of = n_rec[n_hyp[:, 0]]                                             # the recording of every hypothesis
+    # classes on a side: at most one per cell, at most 2 (reference turns + T) + 1 cells
+    cls = np.minimum(2 * (of[:, 1] + of[:, 0]) + 1, FRAME_MAX_CLASSES)
+    n_sys = np.maximum(n_hyp[:, 1], 0)
+    out = np.empty(int((of[:, 2] + n_sys + of[:, 2] * n_sys + cls * cls).sum()), dtype=np.int64)
+    info = np.zeros((hyp.shape[0], 4), dtype=np.int32)
+    classes = np.zeros((hyp.shape[0], 2, FRAME_MAX_CLASSES), dtype=np.uint64)
+    masks = np.zeros(hyp.shape[0], dtype=np.uint64)
+    if hyp.shape[0]:
+        ctx.check(ctx._lib.vbx_labels_frame_counts(ctx._h, rec_counts.shape[0], _ptr(rec_counts), _ptr(seg_times), _ptr(ref_turns),
+                                                   _ptr(ref_spk), hyp.shape[0], _ptr(hyp), _ptr(labels), float(step), _ptr(info),
+                                                   _ptr(classes), _ptr(out), out.size, _ptr(masks)), 'vbx_labels_frame_counts')
+    return info, classes, out, masks
 
 
 def labels_score(ctx: Context, rec_counts, seg_times, ref_turns, ref_spk, ref_edges, hyp, labels, collar, ignore_overlaps):

@@ -50,6 +50,7 @@ using namespace vbx;
 #include "vbx_labels_score.hpp"  // ... of label sequences: turns and cell edges built on the device
 #include "vbx_vad.hpp"           // energy voice-activity detection: the .lab files the front end reads
 #include "vbx_frame_score.hpp"   // frame counts behind dscore's JER, B-cubed and information-theoretic columns
+#include "vbx_labels_frame.hpp"  // ... of label sequences: the turns built on the device, the reference's side once per recording
 #include "vbx_resample.hpp"      // any PCM recording to mono int16 at 8 or 16 kHz: decode, downmix, polyphase filter
 
 #ifdef VBX_PHASE_CLOCKS

@@ -276,19 +276,154 @@ __global__ __launch_bounds__(256) void frame_acc_kernel(const FrmPair* __restric
 }  // namespace vbx
 
 // ---- host glue (included by vbx_capi.hip after vbx_host_call.hpp and vbx_labels_score.hpp) -----------------------------------
+namespace {
+
+// What the frame kernels run on: the pairs, the work items of the kernels that tile a pair's boundaries, cells and result
+// entries, and the room they need.  vbx_frame_counts plans on turns of the host, vbx_labels_frame_counts (vbx_labels_frame.hpp)
+// on those labels_turns_kernel left on the device: one plan, so a pair is cut and summed the same way whichever way it came.
+struct FrmPlan {
+    std::vector<vbx::FrmPair> pairs;
+    std::vector<int2> bnd_items, cell_items, acc_items;
+    long long n_bnd = 0, n_out = 0;
+};
+
+// what a plan's kernels read and write in HBM
+struct FrmDev {
+    vbx::FrmPair* pairs = nullptr;
+    const int2* bitems = nullptr;
+    const int2* citems = nullptr;
+    long long *idx = nullptr, *sorted = nullptr, *uniq = nullptr, *cnt = nullptr;
+    unsigned long long *r = nullptr, *s = nullptr, *classes = nullptr;
+    int *rfirst = nullptr, *sfirst = nullptr, *rcls = nullptr, *scls = nullptr, *info = nullptr;
+};
+
+// the next pair: n_ref_turns, then n_sys_turns turns from turn_off (n_sys_turns may be an upper bound that the device
+// replaces before frame_masks runs); room for its 2 (turns) + 2 boundaries and as many cells
+void frm_plan_add(FrmPlan& pl, int n_ref_turns, int n_sys_turns, int n_ref, int n_sys, double lo, double hi, double step,
+                  long long turn_off) {
+    const int p = (int)pl.pairs.size();
+    vbx::FrmPair pr = vbx::FrmPair{};
+    pr.turn_off = turn_off;
+    pr.bnd_off = pl.n_bnd;
+    pr.n_frames = hi > 0.0 ? (long long)(hi / step) : 0;
+    pr.lo = lo;
+    pr.hi = hi;
+    pr.n_ref_turns = n_ref_turns;
+    pr.n_sys_turns = n_sys_turns;
+    pr.n_ref = n_ref;
+    pr.n_sys = n_sys;
+    const int nb = 2 * (n_ref_turns + n_sys_turns) + 2;
+    for (int b = 0; b * vbx::kFrmBlock < nb; ++b) pl.bnd_items.push_back(make_int2(p, b));
+    for (int b = 0; b * vbx::kFrmBlock < nb - 1; ++b) pl.cell_items.push_back(make_int2(p, b));
+    pl.pairs.push_back(pr);
+    pl.n_bnd += nb;
+}
+
+bool frm_plan_fits(const FrmPlan& pl) { return pl.n_bnd <= 0x7fffffffLL && pl.bnd_items.size() <= 0x7fffffffULL; }
+
+// the plan goes up and gets its room; cut_only: the room of frame_bounds, frame_sort and frame_cells alone
+FrmDev frm_plan_upload(DeviceCall& call, const FrmPlan& pl, bool cut_only) {
+    FrmDev d;
+    const size_t n_bnd = (size_t)pl.n_bnd, n_pairs = pl.pairs.size();
+    d.pairs = call.upload(pl.pairs.data(), n_pairs);
+    d.bitems = call.upload(pl.bnd_items.data(), pl.bnd_items.size());
+    if (!cut_only) d.citems = call.upload(pl.cell_items.data(), pl.cell_items.size());
+    d.idx = call.alloc<long long>(n_bnd);
+    d.sorted = call.alloc<long long>(n_bnd);
+    d.uniq = call.alloc<long long>(n_bnd);
+    if (!cut_only) {
+        d.cnt = call.alloc<long long>(n_bnd);
+        d.r = call.alloc<unsigned long long>(n_bnd);
+        d.s = call.alloc<unsigned long long>(n_bnd);
+        d.rfirst = call.alloc<int>(n_bnd);
+        d.sfirst = call.alloc<int>(n_bnd);
+        d.rcls = call.alloc<int>(n_bnd);
+        d.scls = call.alloc<int>(n_bnd);
+        d.classes = call.alloc<unsigned long long>(n_pairs * 2 * vbx::kFrmMaxCls);
+    }
+    d.info = call.alloc<int>(n_pairs * vbx::kFrmInfo);
+    if (!cut_only && call.ok())
+        call.enqueued(hipMemsetAsync(d.classes, 0, sizeof(unsigned long long) * n_pairs * 2 * vbx::kFrmMaxCls, call.st));
+    return d;
+}
+
+// the sorted distinct frame indices of every pair's boundaries, from the turns in HBM: uniq and info[.][0] (enqueued)
+void frm_plan_cut(DeviceCall& call, const FrmPlan& pl, const FrmDev& d, const double* d_tb, const double* d_te, double step) {
+    if (!call.ok()) return;
+    const dim3 nbi((unsigned)pl.bnd_items.size()), np((unsigned)pl.pairs.size()), th(256);
+    hipLaunchKernelGGL(vbx::frame_bounds_kernel, nbi, th, 0, call.st, d.pairs, d.bitems, d_tb, d_te, step, d.idx);
+    hipLaunchKernelGGL(vbx::frame_sort_kernel, nbi, th, 0, call.st, d.pairs, d.bitems, d.idx, d.sorted);
+    hipLaunchKernelGGL(vbx::frame_cells_kernel, np, th, 0, call.st, d.pairs, d.sorted, d.uniq, d.info);
+    call.launched();
+}
+
+// masks and classes of every pair's cells; what sizes the result comes back into got and classes (enqueued, not waited for)
+void frm_plan_classes(DeviceCall& call, const FrmPlan& pl, const FrmDev& d, const int* d_spk, int32_t* got, uint64_t* classes) {
+    if (call.ok()) {
+        const dim3 nci((unsigned)pl.cell_items.size()), np((unsigned)pl.pairs.size()), th(256);
+        hipLaunchKernelGGL(vbx::frame_masks_kernel, nci, th, 0, call.st, d.pairs, d.citems, d.idx, d_spk, d.uniq, d.info, d.r, d.s, d.cnt);
+        hipLaunchKernelGGL(vbx::frame_firsts_kernel, nci, th, 0, call.st, d.pairs, d.citems, d.info, d.r, d.s, d.rfirst, d.sfirst);
+        hipLaunchKernelGGL(vbx::frame_classes_kernel, np, th, 0, call.st, d.pairs, d.r, d.s, d.rfirst, d.sfirst, d.rcls, d.scls, d.classes,
+                           d.info);
+        call.launched();
+    }
+    call.download(got, d.info, pl.pairs.size() * vbx::kFrmInfo);
+    call.download((unsigned long long*)classes, d.classes, pl.pairs.size() * 2 * vbx::kFrmMaxCls);
+}
+
+enum { kFrmSumsOk = 0, kFrmSumsInsane = 1, kFrmSumsNoRoom = 2 };
+
+// the sums, sized by what came back in got (synchronised); a pair with more classes than kFrmMaxCls a side gets no cm.
+// -> kFrmSumsInsane: what came back would index past its room; kFrmSumsNoRoom: the result has pl.n_out entries, more than
+// out_cap; nothing is launched or written in either case
+int frm_plan_sums(DeviceCall& call, FrmPlan& pl, const FrmDev& d, int32_t* got, int64_t* out, int64_t out_cap) {
+    pl.n_out = 0;
+    pl.acc_items.clear();
+    if (!call.ok()) return kFrmSumsOk;
+    for (size_t p = 0; p < pl.pairs.size(); ++p) {
+        vbx::FrmPair& pr = pl.pairs[p];
+        int32_t* g = got + p * vbx::kFrmInfo;
+        const int nb = 2 * (pr.n_ref_turns + pr.n_sys_turns) + 2;
+        g[3] = 0;
+        if (g[0] < 0 || g[0] > nb - 1 || g[1] < 0 || g[1] > g[0] || g[2] < 0 || g[2] > g[0]) return kFrmSumsInsane;
+        const bool fits = g[1] <= vbx::kFrmMaxCls && g[2] <= vbx::kFrmMaxCls;
+        pr.n_cells = g[0];
+        pr.n_rcls = fits ? g[1] : 0;
+        pr.n_scls = fits ? g[2] : 0;
+        pr.out_off = pl.n_out;
+        const long long block = (long long)pr.n_ref + pr.n_sys + (long long)pr.n_ref * pr.n_sys + (long long)pr.n_rcls * pr.n_scls;
+        for (long long b = 0; b * vbx::kFrmBlock < block; ++b) pl.acc_items.push_back(make_int2((int)p, (int)b));
+        pl.n_out += block;
+    }
+    if (pl.n_out > out_cap) return kFrmSumsNoRoom;
+    if (pl.n_out > 0) {
+        call.copy_in(d.pairs, pl.pairs.data(), pl.pairs.size());        // (with what came back)
+        const int2* d_aitems = call.upload(pl.acc_items.data(), pl.acc_items.size());
+        long long* d_out = call.alloc<long long>((size_t)pl.n_out);
+        if (call.ok()) {
+            hipLaunchKernelGGL(vbx::frame_acc_kernel, dim3((unsigned)pl.acc_items.size()), dim3(256), 0, call.st, d.pairs, d_aitems, d.r, d.s,
+                               d.cnt, d.rfirst, d.sfirst, d.rcls, d.scls, d_out);
+            call.launched();
+        }
+        call.download((long long*)out, d_out, (size_t)pl.n_out);
+        call.sync();
+    }
+    return kFrmSumsOk;
+}
+
+}  // namespace
+
 extern "C" {
 
 int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const double* extent, const double* turns,
                      const int32_t* spk, double step, int32_t* info, uint64_t* classes, int64_t* out, int64_t out_cap) {
-    using vbx::FrmPair;
     if (!ctx) return VBX_ERR_INVALID;
     if (n_pairs <= 0 || !counts || !extent || !info || !classes || !out || out_cap < 0)
         FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: bad argument");
     if (!(step > 0.0) || !std::isfinite(step)) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: step=%g is not a length", step);
     // ---- the pairs: everything the kernels index or shift with is checked here, before any launch ----
-    std::vector<FrmPair> pairs((size_t)n_pairs);
-    std::vector<int2> bnd_items, cell_items;
-    long long n_turns = 0, n_bnd = 0;
+    FrmPlan pl;
+    long long n_turns = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const int32_t* c = counts + 4 * (size_t)p;
         const int nrt = c[0], nst = c[1], nr = c[2], ns = c[3];
@@ -305,105 +440,27 @@ int vbx_frame_counts(vbx_ctx* ctx, int32_t n_pairs, const int32_t* counts, const
             if (int rc = check_turn_speakers(ctx, "vbx_frame_counts", "pair", p, "turn", spk + n_turns + t, t, 1, t < nrt ? nr : ns)) return rc;
             if (!(lo <= b && b <= e && e <= hi)) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: pair %d: turn %lld [%g, %g] outside the extent [%g, %g]", p, t, b, e, lo, hi);
         }
-        FrmPair& pr = pairs[p];
-        pr = FrmPair{};
-        pr.turn_off = n_turns;
-        pr.bnd_off = n_bnd;
-        pr.n_frames = hi > 0.0 ? (long long)(hi / step) : 0;
-        pr.lo = lo;
-        pr.hi = hi;
-        pr.n_ref_turns = nrt;
-        pr.n_sys_turns = nst;
-        pr.n_ref = nr;
-        pr.n_sys = ns;
-        const int nb = 2 * (nrt + nst) + 2;
-        for (int b = 0; b * vbx::kFrmBlock < nb; ++b) bnd_items.push_back(make_int2(p, b));
-        for (int b = 0; b * vbx::kFrmBlock < nb - 1; ++b) cell_items.push_back(make_int2(p, b));
+        frm_plan_add(pl, nrt, nst, nr, ns, lo, hi, step, n_turns);
         n_turns += (long long)nrt + nst;
-        n_bnd += nb;
     }
-    if (n_bnd > 0x7fffffffLL || bnd_items.size() > 0x7fffffffULL)
-        FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_frame_counts: %lld turns in one call", n_turns);
+    if (!frm_plan_fits(pl)) FAIL(ctx, VBX_ERR_UNSUPPORTED, "vbx_frame_counts: %lld turns in one call", n_turns);
     const TurnPlanes tp(turns, n_turns);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<int32_t> got((size_t)n_pairs * vbx::kFrmInfo);
-    std::vector<int2> acc_items;
     DeviceCall call(ctx);                         // (after every host buffer its copies read or write)
-    hipStream_t st = call.st;
-    const size_t n_classes = (size_t)n_pairs * 2 * vbx::kFrmMaxCls;
     // ---- phase 1: cells, masks and classes of every pair ----
-    FrmPair* d_pairs = call.upload(pairs.data(), pairs.size());
-    const int2* d_bitems = call.upload(bnd_items.data(), bnd_items.size());
-    const int2* d_citems = call.upload(cell_items.data(), cell_items.size());
+    const FrmDev d = frm_plan_upload(call, pl, false);
     const double* d_tb = call.upload(tp.beg.data(), (size_t)n_turns);
     const double* d_te = call.upload(tp.end.data(), (size_t)n_turns);
     const int* d_spk = call.upload(spk, (size_t)n_turns);
-    long long* d_idx = call.alloc<long long>((size_t)n_bnd);
-    long long* d_sorted = call.alloc<long long>((size_t)n_bnd);
-    long long* d_uniq = call.alloc<long long>((size_t)n_bnd);
-    long long* d_cnt = call.alloc<long long>((size_t)n_bnd);
-    auto* d_r = call.alloc<unsigned long long>((size_t)n_bnd);
-    auto* d_s = call.alloc<unsigned long long>((size_t)n_bnd);
-    int* d_rfirst = call.alloc<int>((size_t)n_bnd);
-    int* d_sfirst = call.alloc<int>((size_t)n_bnd);
-    int* d_rcls = call.alloc<int>((size_t)n_bnd);
-    int* d_scls = call.alloc<int>((size_t)n_bnd);
-    auto* d_classes = call.alloc<unsigned long long>(n_classes);
-    int* d_info = call.alloc<int>(got.size());
-    if (call.ok()) call.enqueued(hipMemsetAsync(d_classes, 0, sizeof(unsigned long long) * n_classes, st));
-    if (call.ok()) {
-        const dim3 nbi((unsigned)bnd_items.size()), nci((unsigned)cell_items.size()), np((unsigned)n_pairs), th(256);
-        hipLaunchKernelGGL(vbx::frame_bounds_kernel, nbi, th, 0, st, d_pairs, d_bitems, d_tb, d_te, step, d_idx);
-        hipLaunchKernelGGL(vbx::frame_sort_kernel, nbi, th, 0, st, d_pairs, d_bitems, d_idx, d_sorted);
-        hipLaunchKernelGGL(vbx::frame_cells_kernel, np, th, 0, st, d_pairs, d_sorted, d_uniq, d_info);
-        hipLaunchKernelGGL(vbx::frame_masks_kernel, nci, th, 0, st, d_pairs, d_citems, d_idx, d_spk, d_uniq, d_info, d_r, d_s, d_cnt);
-        hipLaunchKernelGGL(vbx::frame_firsts_kernel, nci, th, 0, st, d_pairs, d_citems, d_info, d_r, d_s, d_rfirst, d_sfirst);
-        hipLaunchKernelGGL(vbx::frame_classes_kernel, np, th, 0, st, d_pairs, d_r, d_s, d_rfirst, d_sfirst, d_rcls, d_scls, d_classes,
-                           d_info);
-        call.launched();
-    }
-    call.download(got.data(), d_info, got.size());
-    call.download((unsigned long long*)classes, d_classes, n_classes);
+    frm_plan_cut(call, pl, d, d_tb, d_te, step);
+    frm_plan_classes(call, pl, d, d_spk, got.data(), classes);
     call.sync();
-    // ---- phase 2: the sums, sized by what came back; a pair with more classes than kFrmMaxCls a side gets no cm ----
-    long long n_out = 0;
-    bool sane = true;
-    if (call.ok()) {
-        for (int p = 0; p < n_pairs; ++p) {
-            FrmPair& pr = pairs[p];
-            int32_t* g = got.data() + (size_t)p * vbx::kFrmInfo;
-            const int nb = 2 * (pr.n_ref_turns + pr.n_sys_turns) + 2;
-            g[3] = 0;
-            if (g[0] < 0 || g[0] > nb - 1 || g[1] < 0 || g[1] > g[0] || g[2] < 0 || g[2] > g[0]) {
-                sane = false;                                         // (what came back would index past its room)
-                break;
-            }
-            const bool fits = g[1] <= vbx::kFrmMaxCls && g[2] <= vbx::kFrmMaxCls;
-            pr.n_cells = g[0];
-            pr.n_rcls = fits ? g[1] : 0;
-            pr.n_scls = fits ? g[2] : 0;
-            pr.out_off = n_out;
-            const long long block = (long long)pr.n_ref + pr.n_sys + (long long)pr.n_ref * pr.n_sys + (long long)pr.n_rcls * pr.n_scls;
-            for (long long b = 0; b * vbx::kFrmBlock < block; ++b) acc_items.push_back(make_int2(p, (int)b));
-            n_out += block;
-        }
-    }
-    const bool room = n_out <= out_cap;
-    if (sane && room && n_out > 0) {
-        call.copy_in(d_pairs, pairs.data(), pairs.size());            // (with what came back)
-        const int2* d_aitems = call.upload(acc_items.data(), acc_items.size());
-        long long* d_out = call.alloc<long long>((size_t)n_out);
-        if (call.ok()) {
-            hipLaunchKernelGGL(vbx::frame_acc_kernel, dim3((unsigned)acc_items.size()), dim3(256), 0, st, d_pairs, d_aitems, d_r, d_s, d_cnt,
-                               d_rfirst, d_sfirst, d_rcls, d_scls, d_out);
-            call.launched();
-        }
-        call.download((long long*)out, d_out, (size_t)n_out);
-        call.sync();
-    }
+    // ---- phase 2: the sums, sized by what came back ----
+    const int sums = frm_plan_sums(call, pl, d, got.data(), out, out_cap);
     if (int rc = call.finish("frame count kernels failed")) return rc;
-    if (!sane) FAIL(ctx, VBX_ERR_HIP, "vbx_frame_counts: the cell or class counts that came back do not fit their room");
-    if (!room) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: the result has %lld entries, out has room for %lld", n_out, (long long)out_cap);
+    if (sums == kFrmSumsInsane) FAIL(ctx, VBX_ERR_HIP, "vbx_frame_counts: the cell or class counts that came back do not fit their room");
+    if (sums == kFrmSumsNoRoom) FAIL(ctx, VBX_ERR_INVALID, "vbx_frame_counts: the result has %lld entries, out has room for %lld", pl.n_out, (long long)out_cap);
     std::memcpy(info, got.data(), sizeof(int32_t) * got.size());
     return VBX_OK;
 }

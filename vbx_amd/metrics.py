@@ -40,7 +40,9 @@ frame indices of the turn boundaries -- never from one row per frame -- on the d
 sequence (``device=N``; vbx_frame_score.hpp) or in numpy (``device=None``).  The floating-point columns are always computed
 here, in float64, from those integers: both routes give the same records bit for bit.
 
-As a library: ``frame_counts``, ``score_turns``, ``score_rttm``, ``format_table``.
+As a library: ``frame_counts``, ``score_turns``, ``score_rttm``, ``format_table``; for label sequences -- many hypotheses per
+recording, the turns built on the device, as ``python -m vbx_amd.tune --criterion`` needs them -- ``frame_counts_labels`` and
+``score_labels`` (vbx_labels_frame.hpp).
 """
 from __future__ import annotations
 
@@ -53,7 +55,7 @@ import numpy as np
 from . import score as _score
 from .score import merge_turns
 
-__all__ = ['frame_counts', 'score_turns', 'score_rttm', 'format_table', 'build_parser', 'main']
+__all__ = ['frame_counts', 'frame_counts_labels', 'score_turns', 'score_labels', 'score_rttm', 'format_table', 'build_parser', 'main']
 
 MAX_DEVICE_SPEAKERS = 64      # speakers per side the device route takes (vbx_frame_score.hpp: kFrmMaxSpk)
 MAX_DEVICE_CLASSES = 256      # classes per side it returns (kFrmMaxCls)
@@ -222,6 +224,104 @@ def frame_counts(pairs, step=0.010, device=None):
     return _frame_counts([_Frames(ref, hyp) for ref, hyp in pairs], step, device)
 
 
+# ---- label sequences: many hypotheses per recording ---------------------------------------------------
+class _LabelsFrames:
+    """The reference's side of one recording for ``vbx_labels_frame_counts``, prepared once for all its label sequences:
+    merged turns and speaker names.  ``ok``: the device takes the recording -- at most 64 reference speakers, segments of
+    positive finite duration whose starts and ends both never decrease, fewer than 2^40 frames.  Then the turns of ANY label
+    sequence form a chain and ``lo`` / ``hi`` of ``_Frames`` do not depend on the labels (``score._LabelsRef``)."""
+
+    def __init__(self, ref_turns, starts, ends, step):
+        ref = merge_turns(ref_turns, touching=False)
+        self.ref_names = sorted({t[2] for t in ref}, key=str)
+        ri = {s: i for i, s in enumerate(self.ref_names)}
+        self.turns = np.array([t[:2] for t in ref], dtype=np.float64).reshape(-1, 2)
+        self.rs = np.array([ri[t[2]] for t in ref], dtype=np.int32)
+        s = self.starts = np.asarray(starts, dtype=np.float64).reshape(-1)
+        e = self.ends = np.asarray(ends, dtype=np.float64).reshape(-1)
+        self.ok = bool(s.size > 0 and s.size == e.size and len(self.ref_names) <= MAX_DEVICE_SPEAKERS and np.isfinite(s).all()
+                       and np.isfinite(e).all() and np.isfinite(self.turns).all() and (s < e).all() and (s[1:] >= s[:-1]).all()
+                       and (e[1:] >= e[:-1]).all())
+        if self.ok:
+            self.ok = max([e[-1]] + self.turns[:, 1].tolist()) / step < MAX_DEVICE_FRAMES
+
+
+def _labels_host_counts(item, labels, step):
+    return _host_counts(_Frames(item[0], _score.labels_turns(item[1], item[2], labels)), step)
+
+
+def frame_counts_labels(items, step=0.010, device=None, timing=None):
+    """The integers of ``frame_counts`` for label sequences: ``items`` = ``[(reference turns, starts, ends, [labels, ...])]``,
+    the items of ``score.score_labels``.  -> per item a list with, per label sequence, the record ``frame_counts([(reference
+    turns, score.labels_turns(starts, ends, labels))])`` gives; the system speakers are the integer labels that have a turn
+    of positive duration.
+
+    ``device=None``: that call, in numpy.  ``device=N``: ONE ``vbx_labels_frame_counts`` call for everything the device takes --
+    the turns of every hypothesis are built on GPU N, the reference's side goes up and is cut into frames once per recording
+    (vbx_labels_frame.hpp).  These run in numpy, item by item: more than 64 reference speakers or distinct labels, more than
+    256 classes on a side, segment times that decrease, a segment without duration.  Both routes count the same cells in
+    integers: the records are equal bit for bit.  ``timing``: a dict that receives the seconds of the host preparation, the
+    device call and the mapping of what came back."""
+    import time
+    t0 = t1 = t2 = time.perf_counter()
+    step = _check_step(step)
+    out = [[None] * len(item[3]) for item in items]
+    host = []                                                         # (item, hypothesis) for the numpy route
+    if device is None:
+        host = [(k, j) for k, item in enumerate(items) for j in range(len(item[3]))]
+    else:
+        from . import _capi
+        refs, where, hyp, labs, names = [], [], [], [], []
+        for k, (ref_turns, starts, ends, hyps) in enumerate(items):
+            ref = _LabelsFrames(ref_turns, starts, ends, step) if len(hyps) else None
+            taken = False
+            for j, labels in enumerate(hyps):
+                labels = np.asarray(labels).reshape(-1)
+                uniq, inv = np.unique(labels, return_inverse=True)
+                if not ref.ok or labels.size != ref.starts.size or uniq.size > MAX_DEVICE_SPEAKERS:
+                    host.append((k, j))
+                    continue
+                order = sorted(range(uniq.size), key=lambda c: str(int(uniq[c])))      # the order of _Frames: by name as text
+                rank = np.empty(uniq.size, dtype=np.int32)
+                rank[order] = np.arange(uniq.size, dtype=np.int32)
+                taken = True
+                where.append((k, j))
+                hyp.append((len(refs), uniq.size))
+                labs.append(rank[inv.reshape(-1)])
+                names.append([int(uniq[c]) for c in order])
+            if taken:
+                refs.append(ref)
+        t1 = t2 = time.perf_counter()
+        if where:
+            info, classes, flat, masks = _capi.labels_frame_counts(
+                _capi.default_context(int(device)), [(r.starts.size, r.rs.size, len(r.ref_names)) for r in refs],
+                np.concatenate([a for r in refs for a in (r.starts, r.ends)]), np.concatenate([r.turns for r in refs]),
+                np.concatenate([r.rs for r in refs]), hyp, np.concatenate(labs), step)
+            t2 = time.perf_counter()
+            off = 0
+            for (k, j), (r, ns), lab_names, (_, ncr, ncs, _), cls, mask in zip(where, hyp, names, info.tolist(), classes, masks.tolist()):
+                ref_names = refs[r].ref_names
+                nr = len(ref_names)
+                ref_durs, sys_durs = flat[off:off + nr].copy(), flat[off + nr:off + nr + ns]
+                inter = flat[off + nr + ns:off + nr + ns + nr * ns].reshape(nr, ns)
+                off += nr + ns + nr * ns
+                if ncr > MAX_DEVICE_CLASSES or ncs > MAX_DEVICE_CLASSES:
+                    host.append((k, j))                               # (the device returned no cm)
+                    continue
+                cm = flat[off:off + ncr * ncs].reshape(ncr, ncs).copy()
+                off += ncr * ncs
+                cols = [c for c in range(ns) if mask >> c & 1]        # a label whose only turns have no duration is no speaker
+                out[k][j] = dict(ref_speakers=list(ref_names), sys_speakers=[lab_names[c] for c in cols], ref_durs=ref_durs,
+                                 sys_durs=sys_durs[cols], inter=np.ascontiguousarray(inter[:, cols]),
+                                 ref_classes=[tuple(n for i, n in enumerate(ref_names) if int(m) >> i & 1) for m in cls[0, :ncr]],
+                                 sys_classes=[tuple(lab_names[c] for c in cols if int(m) >> c & 1) for m in cls[1, :ncs]], cm=cm)
+    for k, j in host:
+        out[k][j] = _labels_host_counts(items[k], items[k][3][j], step)
+    if timing is not None:
+        timing.update(prepare=t1 - t0, device=t2 - t1, mapping=time.perf_counter() - t2)
+    return out
+
+
 # ---- the floating-point columns, always here, from the integers -----------------------------------------------------------
 def _jer(rec):
     """per reference speaker with a frame: its Jaccard error in [0, 1], as {name: error}"""
@@ -300,6 +400,29 @@ def score_turns(pairs, collar=0.0, ignore_overlaps=False, step=0.010, device=Non
     der = _score.score_turns(pairs, collar, ignore_overlaps, device)
     counts = _frame_counts([_Frames(ref, hyp) for ref, hyp in pairs], step, device)
     return [_extend(d, c) for d, c in zip(der, counts)]
+
+
+def score_labels(items, collar=0.0, ignore_overlaps=False, step=0.010, device=None, timing=None):
+    """Score label sequences: ``items`` = ``[(reference turns, starts, ends, [labels, ...])]``, the items of
+    ``score.score_labels``.  -> per item a list with, per label sequence, exactly the record ``score_turns([(reference turns,
+    score.labels_turns(starts, ends, labels))], collar, ignore_overlaps, step, device)`` returns.  The DER part is
+    ``score.score_labels``, the integers are ``frame_counts_labels``: with ``device=N`` two device calls for all sequences of
+    all recordings, the reference's side prepared once per recording in both.  The floating-point columns are computed here
+    from the integers, as in ``score_turns``.  ``timing``: a dict that receives the seconds of the host preparation, the
+    device calls and the mapping (``linear_sum_assignment``, the records, the columns; ``columns`` names the columns' share)."""
+    import time
+    step = _check_step(step)
+    items = list(items)
+    t_der, t_cnt = {}, {}
+    der = _score.score_labels(items, collar, ignore_overlaps, device, timing=t_der)
+    counts = frame_counts_labels(items, step, device, timing=t_cnt)
+    t0 = time.perf_counter()
+    out = [[_extend(d, c) for d, c in zip(ds, cs)] for ds, cs in zip(der, counts)]
+    if timing is not None:
+        columns = time.perf_counter() - t0
+        timing.update(prepare=t_der['prepare'] + t_cnt['prepare'], device=t_der['device'] + t_cnt['device'],
+                      mapping=t_der['mapping'] + t_cnt['mapping'] + columns, columns=columns)
+    return out
 
 
 def _overall(records):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""python -m vbx_amd.tune: grid search over Fa, Fb and loopP on a labelled development set, scored with md-eval's DER.
+"""python -m vbx_amd.tune: grid search over Fa, Fb and loopP on a labelled development set, scored with md-eval's DER or
+with any other column of dscore's table.
 
     python -m vbx_amd.tune --xvec-ark-file x.ark --segments-file x.seg --xvec-transform transform.h5 --plda-file plda \\
         --threshold -0.015 --lda-dim 128 --ref-rttm-dir ref --Fa 0.2 0.3 0.4 --Fb 11 17 --loopP 0.9 0.99
@@ -12,6 +13,14 @@ label sequences of all points and recordings are scored against ``<ref-rttm-dir>
 builds the turns and the cell edges itself (``score.score_labels``, vbx_labels_score.hpp).  Printed: one line per grid point,
 ``Fa Fb loopP DER Miss FA Conf`` in percent of the scored reference time pooled over the recordings (the ``*** OVERALL ***``
 row of ``python -m vbx_amd.score``), in grid order; then the best point, the first in grid order among equals.
+
+``--criterion COLUMN`` judges the grid by another column of ``python -m vbx_amd.metrics``: ``jer``, ``b3_precision``,
+``b3_recall``, ``b3_f1``, ``gkt_ref_sys``, ``gkt_sys_ref``, ``h_ref_sys``, ``h_sys_ref``, ``mi``, ``nmi`` (``--step``: their frame step,
+0.010 s).  DER is time-weighted: a point that swallows a short speaker into a long one looks good; JER weighs every
+reference speaker the same.  The label sequences then go through ``metrics.score_labels`` (vbx_labels_frame.hpp beside
+vbx_labels_score.hpp), the table holds all eleven columns pooled by the OVERALL rules of ``vbx_amd.metrics``, and the best
+point is the smallest ``der``, ``jer``, ``h_ref_sys`` or ``h_sys_ref`` or the largest of any other column; a figure that is
+nan never wins.  Without ``--criterion`` and ``--step`` nothing of this is computed and the output is what it always was.
 
 tune scores the TURNS, not RTTM TEXT.  ``vbhmm --ref-rttm-dir`` scores the text it wrote, whose start and duration are printed
 to six decimals; a figure here can differ from that table by the rounding of the text, at most 1 us per system boundary.
@@ -37,6 +46,7 @@ from .kaldi_formats import read_xvector_timing_dict
 __all__ = ['main', 'tune', 'tune_recordings', 'grid_points', 'best_point', 'format_table', 'build_parser']
 
 FIGURES = ('der', 'miss', 'fa', 'confusion', 'ref_time')
+SMALLER_IS_BETTER = ('der', 'jer', 'h_ref_sys', 'h_sys_ref')        # of metrics.COLUMNS; larger is better for the others
 
 
 def grid_points(Fa, Fb, loopP):
@@ -50,11 +60,23 @@ def grid_points(Fa, Fb, loopP):
     return points
 
 
-def best_point(pooled):
-    """Index of the smallest pooled DER; the first in grid order among equals; a point without scored reference time (nan)
-    is never better than one with."""
-    ders = [p['der'] if p['der'] == p['der'] else float('inf') for p in pooled]
-    return int(np.argmin(ders))                                      # (argmin: the first of the smallest)
+def best_point(pooled, criterion='der'):
+    """Index of the best pooled figure of ``criterion``: the smallest DER, JER or conditional entropy, the largest of any
+    other column; the first in grid order among equals; a figure that is nan (a DER without scored reference time) is never
+    better than one that is not."""
+    sign = 1.0 if criterion in SMALLER_IS_BETTER else -1.0
+    cost = [sign * p[criterion] if p[criterion] == p[criterion] else float('inf') for p in pooled]
+    return int(np.argmin(cost))                                      # (argmin: the first of the smallest)
+
+
+def check_criterion(criterion, step):
+    """(criterion, step) as given, or ValueError.  ``step`` None: the default of ``vbx_amd.metrics`` where a criterion needs one."""
+    from .metrics import COLUMNS
+    if criterion not in COLUMNS:
+        raise ValueError(f'--criterion {criterion}: not one of ' + ', '.join(COLUMNS))
+    if step is not None and not (float(step) > 0.0 and float(step) != float('inf')):
+        raise ValueError('--step must be > 0')
+    return criterion, (None if step is None else float(step))
 
 
 def check_one_rank(world=None):
@@ -83,16 +105,23 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
                     t_start=None, t_read=None):
     """The grid search for recordings in memory: ``recordings`` = ``[(name, seg_names, x)]``, ``segs_dict``, ``models`` and
     ``args`` (threshold, lda_dim, init_smoothing and, optionally, precision, ahc_scores, target_energy, collar,
-    ignore_overlaps) as ``vbhmm.diarize_recordings`` takes them, ``grid`` = ``[(Fa, Fb, loopP)]``, ``ref_turns`` =
+    ignore_overlaps, criterion, step) as ``vbhmm.diarize_recordings`` takes them, ``grid`` = ``[(Fa, Fb, loopP)]``, ``ref_turns`` =
     ``{name: [(start, end, speaker)]}``.  ``stages`` defaults to ``DeviceStages()``; with injected host stages (an object
     without a device context) the scoring runs in numpy.
 
     -> dict: ``grid``, ``names``, ``labels`` [point][recording] (first speaker per segment: what ``diarize_recordings`` gives
     at that point), ``records`` [point][recording] (records of ``score.score_labels``), ``pooled`` [point], ``best`` (index
-    into the grid) and ``timing`` (seconds: read, project, ahc, vb, score_prepare, score_device, score_mapping, total)."""
+    into the grid) and ``timing`` (seconds: read, project, ahc, vb, score_prepare, score_device, score_mapping, total).
+
+    ``args.criterion`` (default ``'der'``) names the column of ``metrics.COLUMNS`` that ``best`` follows, ``args.step`` (default
+    None) the frame step.  With anything but the two defaults the records are those of ``metrics.score_labels`` (all eleven
+    columns and their integers), ``pooled`` the OVERALL rows of ``metrics._overall``, and the dict also holds ``criterion`` and
+    ``step``."""
     from concurrent.futures import ThreadPoolExecutor
     from ._capi import MAX_SPEAKERS
     from .vbhmm import DeviceStages, _ahc_kw, tune_host_process
+    criterion, step = check_criterion(getattr(args, 'criterion', 'der'), getattr(args, 'step', None))
+    extended = criterion != 'der' or step is not None
     grid = [tuple(float(v) for v in g) for g in grid]
     if not grid:
         raise ValueError('the grid is empty: Fa, Fb and loopP need at least one value each')
@@ -139,18 +168,27 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
             start, end = segs_dict[name][1].T
             items.append((ref_turns[name], start, end, [labels[g][k] for g in range(len(grid))]))
         split = {}
-        per_rec = score.score_labels(items, getattr(args, 'collar', 0.25), getattr(args, 'ignore_overlaps', False), device, timing=split)
+        collar, ignore_overlaps = getattr(args, 'collar', 0.25), getattr(args, 'ignore_overlaps', False)
+        if extended:
+            from . import metrics
+            step = 0.010 if step is None else step
+            per_rec = metrics.score_labels(items, collar, ignore_overlaps, step, device, timing=split)
+        else:
+            per_rec = score.score_labels(items, collar, ignore_overlaps, device, timing=split)
         t_score = time.perf_counter()
     finally:
         if own_stages:
             stages.close()
     records = [[per_rec[k][g] for k in range(len(names))] for g in range(len(grid))]
-    pooled = [score._pool(rs) for rs in records]
+    pooled = [metrics._overall(rs) if extended else score._pool(rs) for rs in records]
     timing = dict(read=t_read - t_start, project=t_proj - t_read, ahc=t_ahc - t_proj, vb=t_vb - t_ahc,
                   score_prepare=split.get('prepare', 0.0), score_device=split.get('device', 0.0),
                   score_mapping=split.get('mapping', 0.0), score=t_score - t_vb, total=time.perf_counter() - t_start,
                   recordings=len(names), points=len(grid), xvectors=int(sum(len(r[1]) for r in recordings)))
-    return dict(grid=grid, names=names, labels=labels, records=records, pooled=pooled, best=best_point(pooled), timing=timing)
+    result = dict(grid=grid, names=names, labels=labels, records=records, pooled=pooled, best=best_point(pooled, criterion), timing=timing)
+    if extended:
+        result.update(criterion=criterion, step=step)
+    return result
 
 
 def write_best_rttm(result, out_dir, recordings, segs_dict):
@@ -167,29 +205,49 @@ def _percent(r):
     return [f"{r['der']:.2f}"] + [f"{100.0 * r[k] / r['ref_time']:.2f}" for k in ('miss', 'fa', 'confusion')]
 
 
+def _columns(r):
+    from .metrics import COLUMNS
+    return ['nan' if r[k] != r[k] else f'{r[k]:.2f}' for k in COLUMNS]                   # (metrics.format_table's numbers)
+
+
 def format_table(result):
-    """One line per grid point, in grid order: Fa Fb loopP DER Miss FA Conf (pooled, percent); then the best point."""
-    rows = [['Fa', 'Fb', 'loopP', 'DER', 'Miss', 'FA', 'Conf']]
-    rows += [[f'{v:g}' for v in g] + _percent(p) for g, p in zip(result['grid'], result['pooled'])]
-    width = [max(len(r[c]) for r in rows) for c in range(7)]
-    lines = ['  '.join(r[c].rjust(width[c]) for c in range(7)) for r in rows]
-    b = result['best']
-    Fa, Fb, loopP = result['grid'][b]
-    lines.append(f'best: Fa={Fa:g} Fb={Fb:g} loopP={loopP:g} DER={_percent(result["pooled"][b])[0]}')
+    """One line per grid point, in grid order: Fa Fb loopP DER Miss FA Conf (pooled, percent); then the best point.  A
+    result judged by ``--criterion`` or counted with ``--step``: Fa Fb loopP and the eleven columns of ``vbx_amd.metrics``
+    (the pooled OVERALL row of the point), then the best point with the column it was chosen by."""
+    if 'criterion' in result:
+        from .metrics import COLUMNS, HEADER
+        rows = [['Fa', 'Fb', 'loopP'] + HEADER[1:]] + [[f'{v:g}' for v in g] + _columns(p) for g, p in zip(result['grid'], result['pooled'])]
+        best = f'{HEADER[1 + COLUMNS.index(result["criterion"])]}={_columns(result["pooled"][result["best"]])[COLUMNS.index(result["criterion"])]}'
+    else:
+        rows = [['Fa', 'Fb', 'loopP', 'DER', 'Miss', 'FA', 'Conf']]
+        rows += [[f'{v:g}' for v in g] + _percent(p) for g, p in zip(result['grid'], result['pooled'])]
+        best = f'DER={_percent(result["pooled"][result["best"]])[0]}'
+    width = [max(len(r[c]) for r in rows) for c in range(len(rows[0]))]
+    lines = ['  '.join(r[c].rjust(width[c]) for c in range(len(rows[0]))) for r in rows]
+    Fa, Fb, loopP = result['grid'][result['best']]
+    lines.append(f'best: Fa={Fa:g} Fb={Fb:g} loopP={loopP:g} {best}')
     return '\n'.join(lines)
 
 
 def to_json(result, args=None):
+    keys = FIGURES
+    if 'criterion' in result:
+        from .metrics import COLUMNS
+        keys = tuple(COLUMNS) + FIGURES[1:]
+
     def figures(r):
-        return {k: (None if r[k] != r[k] else float(r[k])) for k in FIGURES}
+        return {k: (None if r[k] != r[k] else float(r[k])) for k in keys}
     points = []
     for g, pooled, recs in zip(result['grid'], result['pooled'], result['records']):
         points.append(dict(Fa=g[0], Fb=g[1], loopP=g[2], pooled=figures(pooled),
                            recordings={n: figures(r) for n, r in zip(result['names'], recs)}))
     b = result['best']
-    return dict(collar=getattr(args, 'collar', None), ignore_overlaps=getattr(args, 'ignore_overlaps', None), points=points,
-                best=dict(index=b, Fa=result['grid'][b][0], Fb=result['grid'][b][1], loopP=result['grid'][b][2],
-                          pooled=figures(result['pooled'][b])), timing=result['timing'])
+    out = dict(collar=getattr(args, 'collar', None), ignore_overlaps=getattr(args, 'ignore_overlaps', None), points=points,
+               best=dict(index=b, Fa=result['grid'][b][0], Fb=result['grid'][b][1], loopP=result['grid'][b][2],
+                         pooled=figures(result['pooled'][b])), timing=result['timing'])
+    if 'criterion' in result:
+        out.update(criterion=result['criterion'], step=result['step'])
+    return out
 
 
 def tune(args, stages=None, log=print):
@@ -198,6 +256,7 @@ def tune(args, stages=None, log=print):
     from .vbhmm import _ahc_kw, _read_recordings, load_models
     check_one_rank()
     grid = grid_points(args.Fa, args.Fb, args.loopP)
+    check_criterion(getattr(args, 'criterion', 'der'), getattr(args, 'step', None))
     _ahc_kw(args, None)
     if not os.path.isdir(args.ref_rttm_dir):                          # (found before the run, not after it)
         raise ValueError(f'--ref-rttm-dir {args.ref_rttm_dir}: no such directory')
@@ -237,6 +296,11 @@ def build_parser():
     p.add_argument('--collar', required=False, type=float, default=0.25,
                    help='no-score zone round every reference turn boundary, seconds (default: %(default)s)')
     p.add_argument('--ignore_overlaps', action='store_true', help='do not score where two or more reference speakers speak')
+    p.add_argument('--criterion', required=False, type=str, default='der', metavar='COLUMN',
+                   help='the column the best point is chosen by: der (default), jer, b3_precision, b3_recall, b3_f1, gkt_ref_sys, '
+                        'gkt_sys_ref, h_ref_sys, h_sys_ref, mi or nmi; anything but der prints all eleven columns per point')
+    p.add_argument('--step', required=False, type=float, default=None, metavar='DUR',
+                   help='frame step of the columns other than DER in seconds (default: 0.010); given, it prints all eleven columns')
     p.add_argument('--out-json', required=False, type=str, default=None, metavar='FILE',
                    help='write the points, the per-recording and pooled figures, the best point and the stage timings')
     p.add_argument('--best-rttm-dir', required=False, type=str, default=None, metavar='DIR',
@@ -254,6 +318,7 @@ def main(argv=None):
             raise ValueError(f'--ref-rttm-dir {args.ref_rttm_dir}: no such directory')
         if not args.collar >= 0.0:
             raise ValueError('--collar must be >= 0')
+        check_criterion(args.criterion, args.step)
     except ValueError as exc:
         parser.error(str(exc))
     try:
