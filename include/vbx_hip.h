@@ -356,6 +356,22 @@ int vbx_cos_similarity_resident(vbx_ctx* ctx, vbx_xvectors* xv, int64_t row0, in
  * softmax(init_smoothing * onehot(labels)) of vbhmm.py:150-152 are built on the device, pi0 = 1/S (VBx.py:76). */
 int vbx_batch_set_recording_resident(vbx_batch* batch, int b, const vbx_xvectors* xv, int64_t row0, const int32_t* labels,
                                      double init_smoothing, const double* Phi, double loopProb, double Fa, double Fb);
+/* ---- --init random_N (the reference's README.md:24: random speaker labels instead of AHC's, then VBx) ----------------
+ * labels_host[t] = (w[t] * N) >> 64, t < T, where w is the stream of 64-bit words Philox4x64-10 gives under the key
+ * {seed, name_hash} from the counter {0, restart, 0, 0}: numpy's np.random.Philox(key=[seed, name_hash],
+ * counter=[0, restart, 0, 0]).random_raw(T), i.e. word t % 4 of the block with counter {t / 4 + 1, restart, 0, 0}.  Drawn on
+ * the device; N >= 1, restart >= 0.  name_hash is FNV-1a-64 of the recording's name in the driver (vbx_amd.vbhmm.name_hash). */
+int vbx_random_labels(vbx_ctx* ctx, uint64_t seed, uint64_t name_hash, int64_t restart, int64_t T, int32_t N, int32_t* labels_host);
+/* Recording b of a batch from those labels with N = S[b]: drawn on the device into scratch and turned into the initial
+ * responsibilities softmax(init_smoothing * onehot(labels)) there, pi0 = 1/S -- what vbx_batch_set_recording_resident does with
+ * labels from the host, bit for bit; no label and no responsibility crosses the bus.
+ *   src_b < 0:  b owns a rho built from the resident rows [row0, row0 + T) of fea with Phi, as _resident builds it.
+ *   src_b >= 0: b runs on the rho (and Phi) of recording src_b, under the rules of vbx_batch_set_recording_shared: same T,
+ *               src_b set before (by any of the setters), one copy of the rows per stream sub-batch; xv, row0 and Phi are
+ *               not read and may be 0 / NULL.  The restarts of a recording: restart 0 owns, the others share with it. */
+int vbx_batch_set_recording_random(vbx_batch* batch, int b, const vbx_xvectors* xv, int64_t row0, int src_b, uint64_t seed,
+                                   uint64_t name_hash, int64_t restart, double init_smoothing, const double* Phi,
+                                   double loopProb, double Fa, double Fb);
 /* vbhmm.py:160-162: np.argsort(-gamma, axis=1)[:, 0] and [:, 1] of recording b, [T] each (second: -1 when S == 1);
  * equal responsibilities keep their index order (numpy leaves the order of ties unspecified).  Either may be NULL. */
 int vbx_batch_get_labels(vbx_batch* batch, int b, int32_t* first, int32_t* second);

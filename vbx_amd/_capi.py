@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     'vbx_vad_energy',
     'vbx_frame_counts', 'vbx_labels_frame_counts',
     'vbx_resample_pcm',
+    'vbx_random_labels', 'vbx_batch_set_recording_random',
 ]
 
 
@@ -198,6 +199,8 @@ def load():
     lib.vbx_frame_counts.argtypes = [vp, i32, vp, vp, vp, vp, dbl, vp, vp, vp, i64]
     lib.vbx_labels_frame_counts.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, vp, dbl, vp, vp, vp, i64, vp]
     lib.vbx_resample_pcm.argtypes = [vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.vbx_random_labels.argtypes = [vp, C.c_uint64, C.c_uint64, i64, i64, i32, vp]
+    lib.vbx_batch_set_recording_random.argtypes = [vp, C.c_int, vp, i64, C.c_int, C.c_uint64, C.c_uint64, i64, dbl, vp, dbl, dbl, dbl]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1028,6 +1031,26 @@ class Batch:
             self._h, int(b), xv._h, int(row0), _ptr(labels), float(init_smoothing), _ptr(Phi), float(loopProb),
             float(Fa), float(Fb)), 'vbx_batch_set_recording_resident')
 
+    def set_recording_random(self, b, xv, row0, src, seed, name_hash, restart, init_smoothing, Phi, loopProb, Fa, Fb):
+        """Recording b from random labels in [0, S[b]) drawn on the device (``random_labels`` with N = S[b]) and smoothed
+        into the initial responsibilities there, uniform priors (vbx_batch_set_recording_random).  ``src`` < 0: b owns a rho
+        built from the resident rows of ``xv.fea`` from ``row0`` on; ``src`` >= 0: b runs on the rho of recording ``src`` of
+        this batch, set before (``xv``, ``row0`` and ``Phi`` are not read then and may be None)."""
+        src = -1 if src is None or int(src) < 0 else int(src)
+        Phi = _f64(Phi)
+        if src < 0:
+            assert xv is not None and Phi is not None and Phi.shape == (self.D,)
+        self.ctx.check(self._lib.vbx_batch_set_recording_random(
+            self._h, int(b), xv._h if src < 0 else None, int(row0 or 0), src, _u64(seed), _u64(name_hash), int(restart),
+            float(init_smoothing), _ptr(Phi) if src < 0 else None, float(loopProb), float(Fa), float(Fb)),
+            'vbx_batch_set_recording_random')
+
+    def final_elbos(self, recs=None):
+        """The last ELBO of every recording of ``recs`` (default: all) after a run, nan for one that has not iterated: the
+        small arrays only, one synchronize per stream (vbx_batch_get_results without responsibilities or models)."""
+        res = self.results(recs, want_gamma=False, want_model=False, pinned=False)
+        return [float(r['Li'][-1]) if len(r['Li']) else float('nan') for r in res]
+
     def labels(self, b):
         """(first, second) speaker of every frame of recording b: np.argsort(-gamma, axis=1)[:, 0 / 1] computed on the
         device (vbhmm.py:160-162); second is None for a single speaker."""
@@ -1174,6 +1197,28 @@ class Batch:
 
 
 _default_ctx = {}
+
+
+def _u64(v) -> int:
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise ValueError(f'{v} is not an unsigned 64-bit integer')
+    return v
+
+
+def random_labels(ctx: Context, seed, name_hash, restart, T, N, out=None) -> np.ndarray:
+    """int32 [T]: the labels --init random_N starts restart ``restart`` of a recording from, drawn on the device
+    (vbx_random_labels): ``(np.random.Philox(key=[seed, name_hash], counter=[0, restart, 0, 0]).random_raw(T) * N) >> 64``.
+    ``out``: a contiguous int32 array of T elements to fill (default: a new one)."""
+    T, N, seed, name_hash = int(T), int(N), _u64(seed), _u64(name_hash)
+    if T < 1 or N < 1 or int(restart) < 0:
+        raise ValueError(f'random_labels: T={T}, N={N}, restart={restart}: T and N must be >= 1, restart >= 0')
+    if out is None:
+        out = np.empty(T, dtype=np.int32)
+    if out.dtype != np.int32 or out.shape != (T,) or not out.flags.c_contiguous:
+        raise ValueError('random_labels: out must be a contiguous int32 array of T elements')
+    ctx.check(ctx._lib.vbx_random_labels(ctx._h, _u64(seed), _u64(name_hash), int(restart), T, N, _ptr(out)), 'vbx_random_labels')
+    return out
 
 
 def nan_rows(ctx: Context, x_ptr, n, D) -> np.ndarray:

@@ -5,6 +5,7 @@
 //   vbhmm.py:153       fea   = (xproj - plda_mu) plda_tr^T [:, :lda_dim]          xv_gemm (the mean goes through the
 //                                                                                 product: - plda_mu plda_tr^T)
 //   vbhmm.py:150-152   qinit = softmax(init_smoothing * onehot(AHC labels))       qinit_kernel, straight into gamma
+//   README.md:24       --init random_N: random speaker labels instead of AHC's        random_labels_kernel, into qinit_kernel
 //   vbhmm.py:160-162   first / second speaker = argsort(-q, axis=1)[:, 0 / 1]     top2_kernel
 //   predict.py:185     np.isnan(embedding).any() per x-vector                     rows_nan_flags
 //
@@ -105,6 +106,41 @@ __global__ __launch_bounds__(256) void qinit_kernel(const int* __restrict__ labe
     const long long t = idx / Sp;
     const int s = (int)(idx - t * Sp);
     gamma[idx] = s >= S ? (R)0 : (s == labels[t] ? (R)hi : (R)lo);
+}
+
+// labels[t] = (w[t] * N) >> 64 in [0, N), w[t] = word t % 4 of the Philox4x64-10 block with counter {t / 4 + 1, restart, 0, 0}
+// under the key {seed, name_hash}: np.random.Philox(key=[seed, name_hash], counter=[0, restart, 0, 0]).random_raw(T)[t]
+// (numpy steps the counter before its first block and hands the four words out in order).  The labels of --init random_N
+// (DESIGN section 23): a function of (seed, name, restart, T, N) and of nothing else.  One thread per block: ten rounds, four
+// labels in one 16-byte store (labels is 16-byte aligned), single stores where the recording ends inside the block.
+__global__ __launch_bounds__(256) void random_labels_kernel(int* __restrict__ labels, long long T, unsigned long long seed,
+                                                             unsigned long long name_hash, unsigned long long restart,
+                                                             unsigned long long N) {
+    constexpr unsigned long long M0 = 0xD2E7470EE14C6C93ull, M1 = 0xCA5A826395121157ull;       // the round multipliers
+    constexpr unsigned long long W0 = 0x9E3779B97F4A7C15ull, W1 = 0xBB67AE8584CAA73Bull;       // the key schedule (Weyl)
+    const long long blk = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long t0 = 4 * blk;
+    if (t0 >= T) return;
+    unsigned long long c0 = (unsigned long long)blk + 1, c1 = restart, c2 = 0, c3 = 0, k0 = seed, k1 = name_hash;
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned long long hi0 = __umul64hi(M0, c0), lo0 = M0 * c0;
+        const unsigned long long hi1 = __umul64hi(M1, c2), lo1 = M1 * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += W0;
+        k1 += W1;
+    }
+    const int4 lab = make_int4((int)__umul64hi(c0, N), (int)__umul64hi(c1, N), (int)__umul64hi(c2, N), (int)__umul64hi(c3, N));
+    if (t0 + 4 <= T) {
+        *reinterpret_cast<int4*>(labels + t0) = lab;
+    } else {
+        labels[t0] = lab.x;
+        if (t0 + 1 < T) labels[t0 + 1] = lab.y;
+        if (t0 + 2 < T) labels[t0 + 2] = lab.z;
+    }
 }
 
 // out[t][s] = (double)gamma[t][s], s < S: the responsibilities a caller asks for (VBx.py:126: gamma[T][S] float64) unpadded and

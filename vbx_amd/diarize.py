@@ -77,8 +77,7 @@ def build_parser():
                    help="where the dither is drawn: by numpy on the host (default), or by the front end's MT19937 kernel on "
                         'the device, to the same bits')
     # ---- vbhmm
-    p.add_argument('--init', required=True, type=str, choices=['AHC', 'AHC+VB'],
-                   help='AHC for using only AHC or AHC+VB for VB-HMM after AHC initilization')
+    vbhmm.add_init_arguments(p)
     p.add_argument('--out-rttm-dir', required=True, type=str, help='Directory to store output rttm files')
     p.add_argument('--xvec-transform', required=True, type=str, help='x-vector transformation: h5 (or npz) file')
     p.add_argument('--plda-file', required=True, type=str, help='PLDA model in Kaldi format')
@@ -137,6 +136,7 @@ def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
     _check(args, p.error)
+    vbhmm.check_init_arguments(args, p.error)
     return args
 
 
@@ -303,7 +303,8 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
                   init='AHC+VB', threshold=-0.015, lda_dim=128, Fa=0.3, Fb=17.0, loopP=0.99, target_energy=1.0,
                   ahc_scores='cos', init_smoothing=5.0, output_2nd=False, precision='fp64', gemm='exact', embed_dim=256,
                   seg_len=144, seg_jump=24, batch_size=128, no_dither=False, dither='host', out_ark_fn=None, out_seg_fn=None,
-                  log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False, resample_to=None):
+                  log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False, resample_to=None, random_restarts=None,
+                  seed=None):
     """Diarize ``wav_dir/<name>.wav`` with the VAD labels ``lab_dir/<name>.lab`` for every name of ``file_names``.
 
     -> ``({recording: dict(labels1st, labels2nd, n_iters, thr, starts, ends)}, timing)``: per x-vector of the recording its
@@ -318,22 +319,30 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
     gets its ``der``.  Without it nothing is scored, printed or added.
 
     ``resample_to`` (8000 or 16000): the wav files may be of any format ``vbx_amd.audio`` reads and are converted on the
-    device to mono int16 at that rate first.  Without it only mono 16-bit files at 8 or 16 kHz are taken."""
+    device to mono int16 at that rate first.  Without it only mono 16-bit files at 8 or 16 kHz are taken.
+
+    ``init='random_<N>'``: no AHC; the VB-HMM starts from random labels over N speakers, ``random_restarts`` times (default 1),
+    drawn from ``seed`` (default 0) and the recording's name (``vbhmm.DeviceStages.vb_random``); an entry then also holds the
+    winning ``restart`` and the final ``elbos`` of all of them, and ``thr`` is nan."""
     args = argparse.Namespace(
         gpus=str(device), checkpoint=checkpoint, gemm=gemm, model=None, weights=None, model_file=None, backend='pytorch',
         ndim=fbank.N_MEL, embed_dim=embed_dim, seg_len=seg_len, seg_jump=seg_jump, in_file_list=None, in_lab_dir=lab_dir,
         in_wav_dir=wav_dir, out_ark_fn=out_ark_fn, out_seg_fn=out_seg_fn, batch_size=batch_size, no_dither=no_dither,
         dither=dither, init=init, out_rttm_dir=out_rttm_dir, xvec_transform=xvec_transform, plda_file=plda_file,
         threshold=threshold, lda_dim=lda_dim, Fa=Fa, Fb=Fb, loopP=loopP, target_energy=target_energy, ahc_scores=ahc_scores,
-        init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False, resample_to=resample_to)
+        init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False, resample_to=resample_to,
+        random_restarts=random_restarts, seed=seed)
     if ref_rttm_dir is not None:
         args.ref_rttm_dir, args.collar, args.ignore_overlaps = ref_rttm_dir, collar, ignore_overlaps
-    if init not in ('AHC', 'AHC+VB'):
-        raise ValueError(f"init must be 'AHC' or 'AHC+VB', not {init!r}")
+    try:
+        vbhmm.random_init_states(init)
+    except ValueError:
+        raise ValueError(f"init must be 'AHC', 'AHC+VB' or 'random_<N>', not {init!r}") from None
 
     def error(msg):
         raise ValueError(msg)
     _check(args, error)
+    vbhmm.check_init_arguments(args, error, warn=lambda _message: None)       # (a library call has said what it wants)
     return _run(args, [str(f) for f in file_names], log=log or (lambda *a: None))
 
 

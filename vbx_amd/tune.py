@@ -26,6 +26,10 @@ tune scores the TURNS, not RTTM TEXT.  ``vbhmm --ref-rttm-dir`` scores the text 
 to six decimals; a figure here can differ from that table by the rounding of the text, at most 1 us per system boundary.
 Nothing else differs.
 
+``--init random_N`` (default ``AHC+VB``) runs no AHC: every grid point runs ``--random-restarts`` restarts per recording from
+random labels over N speakers (``--seed``; ``vbhmm.DeviceStages.vb_random``) and scores the winner by final ELBO -- again the
+labels ``python -m vbx_amd.vbhmm --init random_N`` writes at that point.
+
 One process: refused under ``torchrun`` with several ranks, as ``--ref-rttm-dir`` is, because every rank would see only its
 share of the recordings.  As a library: ``tune`` (reads the files), ``tune_recordings`` (data in memory), ``format_table``.
 """
@@ -88,6 +92,23 @@ def check_one_rank(world=None):
                          'the recordings, and a grid point is judged on all of them')
 
 
+def check_init(args):
+    """(N or None, restarts, seed) of ``args.init`` (default ``'AHC+VB'``), ``args.random_restarts`` and ``args.seed``, or
+    ValueError: the grid is one of VB-HMM parameters, so ``AHC`` alone is refused; restarts and seed need ``random_<N>``."""
+    from .vbhmm import random_init_states
+    init = getattr(args, 'init', 'AHC+VB')
+    n_random = random_init_states(init)
+    restarts, seed = getattr(args, 'random_restarts', None), getattr(args, 'seed', None)
+    if init == 'AHC':
+        raise ValueError('--init AHC runs no VB-HMM: Fa, Fb and loopP change nothing; use AHC+VB or random_<N>')
+    if n_random is None and (restarts is not None or seed is not None):
+        raise ValueError(f'--random-restarts and --seed need --init random_<N>: --init {init} draws nothing')
+    restarts, seed = (1 if restarts is None else int(restarts)), (0 if seed is None else int(seed))
+    if restarts < 1 or not 0 <= seed < 1 << 64:
+        raise ValueError(f'--random-restarts {restarts} must be >= 1 and --seed {seed} in 0 .. 2^64 - 1')
+    return n_random, restarts, seed
+
+
 def read_reference(ref_rttm_dir, names):
     """{recording: turns} from ``<ref_rttm_dir>/<recording>.rttm``."""
     if not os.path.isdir(ref_rttm_dir):
@@ -132,6 +153,7 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
     if missing:
         raise ValueError('no reference turns for: ' + ', '.join(missing))
     ahc_kw = _ahc_kw(args, ahc_scores)
+    n_random, restarts, seed = check_init(args)
     if t_read is None:
         t_read = time.perf_counter()
     if t_start is None:
@@ -147,20 +169,31 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
             log(name)
         # the AHC initialisation does not depend on the grid: once per recording, a few recordings side by side as in the driver
         n_workers = max(1, min(int(os.environ.get('VBX_AMD_DRIVER_THREADS', '6')), (os.cpu_count() or 2) - 1))
-        with tune_host_process(), ThreadPoolExecutor(max_workers=n_workers) as pool:
-            ahc = list(pool.map(lambda k: stages.ahc(k, args.threshold, **ahc_kw)[0], range(len(recordings))))
-        if hasattr(stages, 'close_thread_contexts'):
-            stages.close_thread_contexts()
+        if n_random is None:
+            with tune_host_process(), ThreadPoolExecutor(max_workers=n_workers) as pool:
+                ahc = list(pool.map(lambda k: stages.ahc(k, args.threshold, **ahc_kw)[0], range(len(recordings))))
+            if hasattr(stages, 'close_thread_contexts'):
+                stages.close_thread_contexts()
+        else:                                                        # --init random_N: no AHC at all
+            ahc = [None] * len(recordings)
+            if n_random > MAX_SPEAKERS:
+                raise ValueError(f'--init {args.init}: the device path takes at most {MAX_SPEAKERS} states')
         for (name, seg_names, _x), lab in zip(recordings, ahc):
             assert np.all(segs_dict[name][0] == seg_names)                                # vbhmm.py:166
-            if int(np.max(lab)) + 1 > MAX_SPEAKERS:
+            if lab is not None and int(np.max(lab)) + 1 > MAX_SPEAKERS:
                 raise ValueError(f'{name}: AHC left {int(np.max(lab)) + 1} clusters, the device path takes at most {MAX_SPEAKERS}')
         t_ahc = time.perf_counter()
         ks = list(range(len(recordings)))
         labels = []
         for Fa, Fb, loopP in grid:                                   # the call diarize_recordings makes at this point
-            res = stages.vb(ks, [ahc[k] for k in ks], init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6,
-                            precision=getattr(args, 'precision', 'fp64'), loopProb=loopP, Fa=Fa, Fb=Fb) if ks else []
+            common = dict(init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6, precision=getattr(args, 'precision', 'fp64'),
+                          loopProb=loopP, Fa=Fa, Fb=Fb)
+            if not ks:
+                res = []
+            elif n_random is None:
+                res = stages.vb(ks, [ahc[k] for k in ks], **common)
+            else:                                                    # R restarts per point and recording, the winner's labels
+                res = stages.vb_random(ks, n_random, restarts, seed, [names[k] for k in ks], **common)
             labels.append([np.asarray(r[0]) for r in res])
         t_vb = time.perf_counter()
         items = []
@@ -258,6 +291,7 @@ def tune(args, stages=None, log=print):
     grid = grid_points(args.Fa, args.Fb, args.loopP)
     check_criterion(getattr(args, 'criterion', 'der'), getattr(args, 'step', None))
     _ahc_kw(args, None)
+    check_init(args)
     if not os.path.isdir(args.ref_rttm_dir):                          # (found before the run, not after it)
         raise ValueError(f'--ref-rttm-dir {args.ref_rttm_dir}: no such directory')
     t_start = time.perf_counter()
@@ -276,6 +310,7 @@ def tune(args, stages=None, log=print):
 
 
 def build_parser():
+    from .vbhmm import add_init_arguments
     p = argparse.ArgumentParser(prog='python -m vbx_amd.tune', description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--xvec-ark-file', required=True, type=str,
                    help='Kaldi ark file with x-vectors from one or more input recordings (all x-vectors of one recording consecutive)')
@@ -283,6 +318,7 @@ def build_parser():
     p.add_argument('--xvec-transform', required=True, type=str, help='x-vector transformation: h5 (or npz) file')
     p.add_argument('--plda-file', required=True, type=str, help='PLDA model in Kaldi format')
     p.add_argument('--threshold', required=True, type=float, help='threshold (bias) used for AHC')
+    add_init_arguments(p, default='AHC+VB')
     p.add_argument('--lda-dim', required=True, type=int, help='x-vectors are reduced to this dimensionality for VB-HMM')
     p.add_argument('--Fa', required=True, type=float, nargs='+', help='grid values of Fa (outermost)')
     p.add_argument('--Fb', required=True, type=float, nargs='+', help='grid values of Fb')
@@ -319,6 +355,8 @@ def main(argv=None):
         if not args.collar >= 0.0:
             raise ValueError('--collar must be >= 0')
         check_criterion(args.criterion, args.step)
+        if check_init(args)[0] is not None:
+            print(f'warning: --init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored', file=sys.stderr)
     except ValueError as exc:
         parser.error(str(exc))
     try:

@@ -21,6 +21,10 @@ CPU thread.  Here the loop is split into stages:
 Under ``torchrun`` (one process per GPU) the recordings are dealt to the ranks by cost; every rank writes the
 RTTM files of its own recordings and the ranks only meet in a barrier at the end.  Same flags, same files, same
 RTTM bytes as the reference driver.
+
+``--init random_N`` (the reference's README.md:24) skips stage 1: stage 2 starts every recording from random
+labels over N speakers drawn on the device from (``--seed``, the recording's name, the restart), ``--random-restarts R`` times
+side by side in the one batch, and keeps the restart with the largest final ELBO.  No T x T matrix is ever held.
 """
 from __future__ import annotations
 
@@ -34,7 +38,8 @@ import numpy as np
 from .kaldi_formats import (read_plda, read_vec_flt_ark_grouped, read_xvec_transform, read_xvector_timing_dict,
                             write_rttm)
 
-__all__ = ['main', 'diarize', 'diarize_recordings', 'DeviceStages', 'tune_host_process', 'load_models', 'cluster', 'cut_linkage', 'merge_adjacent_labels', 'l2_norm']
+__all__ = ['main', 'diarize', 'diarize_recordings', 'DeviceStages', 'tune_host_process', 'load_models', 'cluster', 'cut_linkage', 'merge_adjacent_labels', 'l2_norm',
+           'random_init_states', 'name_hash', 'best_restart', 'add_init_arguments', 'check_init_arguments']
 
 
 def l2_norm(vec_or_matrix):
@@ -59,6 +64,39 @@ def merge_adjacent_labels(starts, ends, labels):
     over = np.nonzero(starts[1:] < ends[:-1])[0]
     ends[over] = starts[over + 1] = (ends[over] + starts[over + 1]) / 2.0
     return starts, ends, labels
+
+
+def random_init_states(init):
+    """N for ``--init random_N`` (N a decimal integer >= 1), None for ``AHC`` and ``AHC+VB``; ValueError for anything else."""
+    if init in ('AHC', 'AHC+VB'):
+        return None
+    head, sep, digits = str(init).partition('_')
+    if head != 'random' or not sep or not digits.isascii() or not digits.isdigit() or int(digits) < 1:
+        raise ValueError(f"invalid choice: {init!r} (choose from 'AHC', 'AHC+VB', 'random_<N>' with N a decimal integer >= 1)")
+    return int(digits)
+
+
+def runs_vb(init):
+    """Does this ``--init`` run the VB-HMM?  AHC+VB and random_N do (README.md:24: 'and run VBx')."""
+    return init.endswith('VB') or random_init_states(init) is not None
+
+
+def name_hash(name):
+    """FNV-1a-64 of the recording's name (UTF-8): the half of the Philox key that makes a recording's random labels its own,
+    wherever it stands in the archive and whichever rank it is dealt to."""
+    h = 0xcbf29ce484222325
+    for byte in name.encode('utf-8'):
+        h = ((h ^ byte) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def best_restart(final_elbos):
+    """Index of the restart with the largest final ELBO: the lowest among equals, never one whose ELBO is nan; 0 if all are."""
+    best = 0
+    for r, v in enumerate(final_elbos):
+        if v == v and (final_elbos[best] != final_elbos[best] or v > final_elbos[best]):
+            best = r
+    return best
 
 
 def load_models(xvec_transform, plda_file):
@@ -108,6 +146,8 @@ class DeviceStages:
               (vbhmm.py:150-152), one launch sequence per EM iteration for the whole archive, convergence per recording
               on the device (vbhmm.py:154-158), first / second speaker by a device arg-sort (vbhmm.py:160-162): only
               labels come back
+    vb_random ``--init random_N``: no AHC; the restarts of ALL recordings in one ``vbx_batch``, every restart from labels drawn
+              on the device, the restarts of a recording around one rho; the winner by final ELBO, only its labels come back
     """
 
     def __init__(self, device=None):
@@ -228,6 +268,38 @@ class DeviceStages:
                 batch.close()
         return out
 
+    def vb_random(self, ks, N, restarts, seed, names, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
+        """-> [(labels1st, labels2nd or None, iterations, winning restart, [final ELBO of every restart])] for the recordings
+        ``ks`` (``names[j]`` names ``ks[j]``) started from random labels over N states, ``--init random_N``.
+
+        ONE ``vbx_batch`` of len(ks) x restarts slots, since every slot has N states: restart 0 of a recording owns its rho,
+        the others share it.  The labels are drawn on the device from (seed, name, restart); after the run only the ELBOs come
+        back, the winner is picked here (``best_restart``) and only the winners' labels follow."""
+        R = int(restarts)
+        if R < 1 or int(N) < 1:
+            raise ValueError(f'vb_random: restarts={restarts}, N={N}: both must be >= 1')
+        if not ks:
+            return []
+        batch = self._capi.Batch(self.ctx, [self.T[k] for k in ks for _r in range(R)], [int(N)] * (len(ks) * R), self.lda_dim,
+                                 precision=precision, max_iters=maxIters)
+        try:
+            for j, k in enumerate(ks):
+                h = name_hash(names[j])
+                for r in range(R):
+                    batch.set_recording_random(j * R + r, self.xv, self.row0[k], -1 if r == 0 else j * R, seed, h, r,
+                                               init_smoothing, self.Phi, loopProb, Fa, Fb)
+            batch.run(maxIters, epsilon)
+            elbos = batch.final_elbos()
+            out = []
+            for j in range(len(ks)):
+                mine = elbos[j * R:(j + 1) * R]
+                win = best_restart(mine)
+                first, second = batch.labels(j * R + win)
+                out.append((first, second, batch.n_iters(j * R + win), win, mine))
+        finally:
+            batch.close()
+        return out
+
     def close_thread_contexts(self):
         """The per-thread contexts (a HIP stream each) of the AHC stage: closed before the VB batch creates its stream
         group, so that the group's streams do not share hardware queues with idle ones (8 queues per process)."""
@@ -310,7 +382,7 @@ def _write_rttm_files(args, file_name, st, segs_dict):
     os.makedirs(args.out_rttm_dir, exist_ok=True)
     with open(os.path.join(args.out_rttm_dir, f'{file_name}.rttm'), 'w') as fp:
         write_rttm(fp, file_name, out_labels, starts, ends)
-    if args.output_2nd and args.init.endswith('VB') and st['labels2nd'] is not None:
+    if args.output_2nd and runs_vb(args.init) and st['labels2nd'] is not None:
         starts, ends, out_labels2 = merge_adjacent_labels(start, end, st['labels2nd'])
         second = f'{args.out_rttm_dir}2nd'
         os.makedirs(second, exist_ok=True)
@@ -338,7 +410,8 @@ def diarize(args, stages=None, log=print, ahc_scores=None):
     recordings = _read_recordings(args.xvec_ark_file)
     rank, world = _rank_world()
     if world > 1:                                                 # AHC is O(T^2), the VB loop O(T S): deal by T^2
-        assignment = shard_recordings([float(len(r[1])) ** 2 for r in recordings], world)
+        power = 2 if random_init_states(args.init) is None else 1        # (random_N: no AHC; the labels do not depend on the deal)
+        assignment = shard_recordings([float(len(r[1])) ** power for r in recordings], world)
         recordings = [r for k, r in enumerate(recordings) if assignment[k] == rank]
     t_read = time.perf_counter()
     ref_rttm_dir = getattr(args, 'ref_rttm_dir', None)
@@ -409,7 +482,13 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
         t_read = time.perf_counter()
     if t_start is None:
         t_start = t_read
-    want_vb = args.init.endswith('VB')
+    n_random = random_init_states(args.init)                     # --init random_N: N states, no AHC stage at all
+    restarts, seed = int(getattr(args, 'random_restarts', None) or 1), int(getattr(args, 'seed', None) or 0)
+    if n_random is None and (getattr(args, 'random_restarts', None) is not None or getattr(args, 'seed', None) is not None):
+        raise ValueError('random_restarts and seed need init = random_N')
+    if restarts < 1 or seed < 0 or seed >= 1 << 64:
+        raise ValueError(f'random_restarts={restarts} must be >= 1, seed={seed} in [0, 2^64)')
+    want_vb = runs_vb(args.init)
     own_stages = stages is None
     if own_stages:
         stages = DeviceStages()
@@ -429,6 +508,8 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
 
         def prepare(k):
             file_name, seg_names, _ = recordings[k]
+            if n_random is not None:                                  # (no score matrix, no calibration: thr is nan)
+                return file_name, dict(labels1st=None, labels2nd=None, thr=float('nan'), n_iters=0, seg_names=seg_names)
             labels1st, thr = stages.ahc(k, args.threshold, **ahc_kw)
             st = dict(labels1st=labels1st, labels2nd=None, thr=thr, n_iters=0, seg_names=seg_names)
             if not want_vb:
@@ -457,6 +538,12 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
             names = [r[0] for r in recordings]
             ks = []
             for k, name in enumerate(names):
+                if n_random is not None:
+                    if n_random > MAX_SPEAKERS:
+                        failed[name] = f'--init {args.init}: the device path takes at most {MAX_SPEAKERS} states'
+                    else:
+                        ks.append(k)
+                    continue
                 n_clusters = int(np.max(state[name]['labels1st'])) + 1
                 if n_clusters > MAX_SPEAKERS:
                     failed[name] = f'AHC left {n_clusters} clusters, the device path takes at most {MAX_SPEAKERS}'
@@ -465,17 +552,24 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
 
             def finish(k, result):
                 st = state[names[k]]
-                st['labels1st'], st['labels2nd'], st['n_iters'] = result
+                st['labels1st'], st['labels2nd'], st['n_iters'] = result[:3]
+                if n_random is not None:                              # the winning restart and every restart's final ELBO
+                    st['restart'], st['elbos'] = result[3], result[4]
                 _write_rttm_files(args, names[k], st, segs_dict)
 
+            def run_vb(some):
+                if n_random is not None:
+                    return stages.vb_random(some, n_random, restarts, seed, [names[k] for k in some], **common)
+                return stages.vb(some, [state[names[k]]['labels1st'] for k in some], **common)
+
             try:
-                for k, result in zip(ks, stages.vb(ks, [state[names[k]]['labels1st'] for k in ks], **common)):
+                for k, result in zip(ks, run_vb(ks)):
                     finish(k, result)
             except VbxError as exc:          # one recording at a time, so that a bad one only costs itself
                 log(f'batched VB-HMM failed ({exc}); retrying the recordings one by one')
                 for k in ks:
                     try:
-                        finish(k, stages.vb([k], [state[names[k]]['labels1st']], **common)[0])
+                        finish(k, run_vb([k])[0])
                     except VbxError as exc_k:
                         failed[names[k]] = str(exc_k)
         t_vb = time.perf_counter()
@@ -498,8 +592,7 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
 def build_parser():
     """The arguments of vbhmm.py:54-101, plus the knobs of this implementation."""
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument('--init', required=True, type=str, choices=['AHC', 'AHC+VB'],
-                   help='AHC for using only AHC or AHC+VB for VB-HMM after AHC initilization')
+    add_init_arguments(p)
     p.add_argument('--out-rttm-dir', required=True, type=str, help='Directory to store output rttm files')
     p.add_argument('--xvec-ark-file', required=True, type=str,
                    help='Kaldi ark file with x-vectors from one or more input recordings (all x-vectors of one '
@@ -529,6 +622,49 @@ def build_parser():
     return p
 
 
+def _init_argument(value):
+    try:
+        random_init_states(value)
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc)) from None
+    return value
+
+
+def add_init_arguments(p, default=None):
+    """``--init``, ``--random-restarts`` and ``--seed`` of vbhmm, diarize and tune.  ``default`` None: ``--init`` is required."""
+    p.add_argument('--init', required=default is None, default=default, type=_init_argument, metavar='{AHC,AHC+VB,random_<N>}',
+                   help='AHC for using only AHC, AHC+VB for VB-HMM after AHC initilization, random_<N> for VB-HMM from random '
+                        'labels over N speakers without any AHC (long recordings: AHC holds a T x T matrix)')
+    p.add_argument('--random-restarts', required=False, type=int, default=None, metavar='R',
+                   help='with --init random_<N>: runs from R different random labellings, the one with the largest final ELBO '
+                        'wins (default: 1)')
+    p.add_argument('--seed', required=False, type=int, default=None,
+                   help='with --init random_<N>: seed of the random labels, 0 .. 2^64 - 1 (default: 0; a run is reproducible)')
+
+
+def check_init_arguments(args, error, warn=None):
+    """After parsing: ``--random-restarts`` and ``--seed`` are refused (``error(message)``) unless ``--init`` is random_N and get
+    their defaults 1 and 0; with random_N one line goes to ``warn`` (default: stderr) about the AHC options that are ignored."""
+    if random_init_states(args.init) is None:
+        for flag, value in (('--random-restarts', args.random_restarts), ('--seed', args.seed)):
+            if value is not None:
+                error(f'{flag} needs --init random_<N>: --init {args.init} draws nothing')
+        return
+    if args.random_restarts is None:
+        args.random_restarts = 1
+    if args.seed is None:
+        args.seed = 0
+    if args.random_restarts < 1:
+        error(f'--random-restarts {args.random_restarts}: must be >= 1')
+    if not 0 <= args.seed < 1 << 64:
+        error(f'--seed {args.seed}: must be in 0 .. 2^64 - 1')
+    message = f'--init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored'
+    if warn is None:
+        print(f'warning: {message}', file=sys.stderr)
+    else:
+        warn(message)
+
+
 def add_score_arguments(p):
     """The scoring step the reference's recipes run after this program (dscore/score.py), as an option of it."""
     p.add_argument('--ref-rttm-dir', required=False, type=str, default=None,
@@ -543,6 +679,7 @@ def add_score_arguments(p):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_init_arguments(args, parser.error)
     if args.ref_rttm_dir is not None:
         try:
             check_ref_rttm_dir(args, int(os.environ.get('WORLD_SIZE', 1)))
