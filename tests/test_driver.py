@@ -482,8 +482,9 @@ def test_device_linkage_is_the_host_linkage_bit_for_bit(kind, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind', ['cosine', 'clustered', 'ties', 'es2005a'])
 def test_device_linkage_in_rounds_of_reciprocal_pairs(kind, monkeypatch):
-    """The default device linkage from 1024 clusters on: ALL reciprocal nearest-neighbour pairs merged per round by the whole
-    chip (vbx_ahc.hpp, rnn_*), the chain finishing the last few hundred clusters.  Average linkage is reducible, so the
+    """The default device linkage from 256 clusters on: ALL reciprocal nearest-neighbour pairs merged per round by the whole
+    chip (vbx_ahc.hpp, rnn_*), the chain finishing the last 48 clusters (256 to 1023 clusters, the hand-over and the stalled
+    exit: tests/test_gpu_linkage.py).  Average linkage is reducible, so the
     merges are the chain's; only the order in which a cluster's updates meet differs.  Against the chain form (= the host
     routine = SciPy, bit for bit):
       * distinct distances (cosine, clustered speakers, the example recording): the SAME tree -- identical children and

@@ -119,3 +119,99 @@ def test_condensed_negated_matrix_is_squareform_of_the_device_matrix(T):
                 scores.get_condensed(T - 1, -1.0)
     finally:
         scores.close()
+
+
+# ---- the calibration kernels at their edges: score VECTORS of any length, skewed and overlapping mixtures ----------------
+# lengths: one or two workgroups (3, 255, 256, 257); nb = min(2048, ceil(n / 256)) saturating at kGmmPartials
+CALIB_LENGTHS = (3, 255, 256, 257, 2048 * 256 - 1, 2048 * 256, 2048 * 256 + 1)
+# (weight of the upper component, lower mean, upper mean, sd): symmetric; few same-speaker pairs, like a real score matrix;
+# heavily overlapping
+CALIB_MIXTURES = ((0.5, -1.0, 1.0, 0.3), (0.02, 0.0, 0.8, 0.1), (0.3, 0.1, 0.2, 0.2))
+CALIB_NITERS = (1, 20)
+
+
+def calib_scores(n, mix):
+    w1, m0, m1, sd = CALIB_MIXTURES[mix]
+    rng = np.random.default_rng(100 * mix + n % 1000)
+    return np.where(rng.random(n) < w1, m1, m0) + sd * rng.standard_normal(n)
+
+
+def calib_longdouble(s, niters):
+    """oracle/ahc_oracle.twoGMMcalib_lin restated in np.longdouble, same statement order, the softmax done by hand;
+    {k: (threshold, llr)} after each number of iterations k in niters"""
+    s = np.asarray(s, dtype=np.longdouble)
+    one, half = np.longdouble(1), np.longdouble(0.5)
+    weights = np.array([half, half])
+    means = np.mean(s) + np.std(s) * np.array([-one, one])
+    var = np.var(s)
+    out = {}
+    for it in range(1, max(niters) + 1):
+        lls = np.log(weights) - half * np.log(var) - half * (s[:, np.newaxis] - means) ** 2 / var
+        e = np.exp(lls - lls.max(axis=1, keepdims=True))
+        gammas = e / e.sum(axis=1, keepdims=True)
+        cnts = np.sum(gammas, axis=0)
+        weights = cnts / cnts.sum()
+        means = s.dot(gammas) / cnts
+        var = ((s ** 2).dot(gammas) / cnts - means ** 2).dot(weights)
+        threshold = -half * (np.log(weights ** 2 / var) - means ** 2 / var).dot([one, -one]) / (means / var).dot([one, -one])
+        if it in niters:
+            out[it] = (threshold, lls[:, means.argmax()] - lls[:, means.argmin()])
+    return out
+
+
+def device_calib(s, niters, want_llr=True):
+    from vbx_amd import _capi
+    sc = _capi.Scores.upload(_capi.default_context(), s)
+    try:
+        return sc.two_gmm_calib(niters, want_llr)
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize('mix', range(len(CALIB_MIXTURES)))
+@pytest.mark.parametrize('n', CALIB_LENGTHS)
+def test_calibration_of_score_vectors_against_longdouble(n, mix):
+    """gmm_* on vectors through Scores.upload, 1 and 20 passes, against the np.longdouble restatement of the oracle:
+    threshold within 1e-9 std(s) (the project's 1e-9 on the scale of the scores: the symmetric mixture's threshold sits
+    near 0, where a relative bound means nothing), LLRs at rtol = atol = 1e-8.  The float64 oracle is held to 1e-11 std(s)
+    and 1e-10 in the same test, so a failure points at the device.  want_llr=False gives the same threshold bits."""
+    from oracle import ahc_oracle
+    s = calib_scores(n, mix)
+    ref = calib_longdouble(s, CALIB_NITERS)
+    sd = np.std(s)
+    for niters in CALIB_NITERS:
+        thr_ld, llr_ld = ref[niters]
+        thr_o, llr_o = ahc_oracle.twoGMMcalib_lin(s, niters=niters)
+        thr, llr = device_calib(s, niters)
+        err = [abs(float(t - thr_ld)) / sd for t in (thr, thr_o)] + [float(np.max(np.abs(l - llr_ld))) for l in (llr, llr_o)]
+        print(f'n={n} mix={mix} niters={niters}: threshold error / std(s) device {err[0]:.2g} oracle {err[1]:.2g}; '
+              f'largest LLR error device {err[2]:.2g} oracle {err[3]:.2g} (largest |LLR| {float(np.abs(llr_ld).max()):.3g})')
+        assert np.isfinite(float(thr_ld)) and np.all(np.isfinite(llr_ld.astype(np.float64)))
+        assert err[1] <= 1e-11
+        np.testing.assert_allclose(llr_o, llr_ld.astype(np.float64), rtol=1e-10, atol=1e-10)
+        assert err[0] <= 1e-9, (thr, float(thr_ld))
+        np.testing.assert_allclose(llr, llr_ld.astype(np.float64), rtol=1e-8, atol=1e-8)
+        thr_only, none = device_calib(s, niters, want_llr=False)
+        assert none is None and np.array_equal([thr_only], [thr])
+
+
+@pytest.mark.parametrize('case', ['two', 'constant'])
+def test_calibration_of_degenerate_vectors_is_nan_where_the_reference_is(case):
+    """Two scores, and 1000 equal ones (0.25: every sum is exact, the variance exactly 0): the reference divides by a
+    vanishing variance and returns NaN.  That is arithmetic, not a fault -- gmm_* has no data-dependent loop or index -- so
+    the device returns NaN where the np.longdouble reference does, a close threshold where it does not, and no error."""
+    s = calib_scores(2, 0) if case == 'two' else np.full(1000, 0.25)
+    with np.errstate(all='ignore'):
+        ref = calib_longdouble(s, CALIB_NITERS)
+        for niters in CALIB_NITERS:
+            thr_ld, llr_ld = ref[niters]
+            thr, llr = device_calib(s, niters)
+            print(f'{case} niters={niters}: threshold device {thr} reference {float(thr_ld)}')
+            assert np.isnan(thr) == np.isnan(float(thr_ld))
+            assert np.array_equal(np.isnan(llr), np.isnan(llr_ld.astype(np.float64)))
+            if not np.isnan(thr):
+                assert abs(thr - float(thr_ld)) <= 1e-9 * np.std(s)
+                np.testing.assert_allclose(llr, llr_ld.astype(np.float64), rtol=1e-8, atol=1e-8)
+            thr_only, _ = device_calib(s, niters, want_llr=False)
+            assert np.array_equal([thr_only], [thr], equal_nan=True)
+        assert np.isnan(float(ref[20][0]))

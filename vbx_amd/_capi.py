@@ -893,7 +893,12 @@ class Scores:
 
     def linkage_average(self, T):
         """``linkage(squareform(-S), 'average')`` for the T x T similarities held here, computed on the device (the scores
-        are consumed); the linkage matrix [T - 1][4], bit for bit what ``linkage_average`` gives on the host."""
+        are consumed); the linkage matrix [T - 1][4].  Below 256 clusters, and in the chain form
+        (``VBX_AMD_LINKAGE_DEVICE=chain``), bit for bit what ``linkage_average`` gives on the host.  The default from 256
+        clusters on merges in rounds of reciprocal pairs: the same tree (columns 0, 1, 3) wherever the heights are
+        distinct, every height within ``max(16 ulp, 1e-15 max|S|)`` of the host's and within ``4 * 2**-53 * depth * max|S|``
+        of the exact mean pairwise distance (``depth``: the node's height in the tree); with tied heights a valid
+        average-linkage dendrogram."""
         Z = np.empty((max(int(T) - 1, 0), 4))
         self.ctx.check(self._lib.vbx_scores_linkage_average(self._h, int(T), _ptr(Z)), 'vbx_scores_linkage_average')
         return Z

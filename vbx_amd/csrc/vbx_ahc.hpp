@@ -151,6 +151,16 @@ __global__ __launch_bounds__(256) void gmm_pass_kernel(const double* __restrict_
     }
 }
 
+// E[s^2] - mean^2 of one component with the square rounded on its own, as numpy computes it.  Contracted into a fused
+// multiply-add the difference is the rounding error of mean^2 -- of either sign -- where the reference reaches exactly 0
+// (a component that sits on a single score: two scores, tests/test_gpu_ahc.py), and the passes after it go on with a
+// variance of 1e-17 instead of ending in the reference's NaN.
+__device__ __forceinline__ double gmm_component_var(double q, double c, double m) {
+#pragma clang fp contract(off)
+    const double mm = m * m;
+    return q / c - mm;
+}
+
 // M-step of the calibration (diarization_lib.py:26-29); keeps the parameters the pass started with
 __global__ __launch_bounds__(256) void gmm_update_kernel(const double* __restrict__ part, int npart, double* par) {
     __shared__ double lds[16];
@@ -171,7 +181,7 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(const double* __restric
         par[1] = w1;
         par[2] = m0;
         par[3] = m1;
-        par[4] = (tot[4] / c0 - m0 * m0) * w0 + (tot[5] / c1 - m1 * m1) * w1;
+        par[4] = gmm_component_var(tot[4], c0, m0) * w0 + gmm_component_var(tot[5], c1, m1) * w1;
     }
 }
 
