@@ -372,6 +372,28 @@ int vbx_random_labels(vbx_ctx* ctx, uint64_t seed, uint64_t name_hash, int64_t r
 int vbx_batch_set_recording_random(vbx_batch* batch, int b, const vbx_xvectors* xv, int64_t row0, int src_b, uint64_t seed,
                                    uint64_t name_hash, int64_t restart, double init_smoothing, const double* Phi,
                                    double loopProb, double Fa, double Fb);
+/* ---- --init RTTM / RTTM+VB (the VB-HMM as the second stage of a system: it starts from a diarization that exists) -------
+ * All times are integer microseconds.  Window i < T is [seg_a[i], seg_b[i]), seg_a[i] < seg_b[i]; turn j < N is
+ * [turn_u[j], turn_v[j]) of speaker turn_spk[j] in [0, S), turn_u[j] < turn_v[j], and the turns are sorted by (speaker, start).
+ *   d[i][s] = sum over the turns j of s of max(0, min(b_i, v_j) - max(a_i, u_j))   (exact),   D_i = sum_s d[i][s]
+ *   D_i > 0:  w[i][s] = d[i][s] / D_i (one f64 division), label[i] = argmax_s d[i][s], the lowest among equals
+ *   D_i == 0: the turn with the smallest gap g_j = max(u_j - b_i, a_i - v_j) names the speaker, the lowest index among equal
+ *             gaps; w[i] is its one-hot row and label[i] is that speaker
+ *   q[i][s] = exp(x_s - max x) / sum_s' exp(x_s' - max x), x = init_smoothing * w[i]      (summed in speaker order)
+ * labels_host [T], w_host [T][S] and q_host [T][S] are computed on the device; each may be NULL.  A T or N below 1, an S
+ * outside [1, VBX_MAX_SPEAKERS], a speaker outside [0, S), an empty window or turn, and turns out of order are refused with
+ * VBX_ERR_INVALID before the device is touched (with ctx == NULL the message is vbx_last_error(NULL)'s). */
+int vbx_turn_weights(vbx_ctx* ctx, int64_t T, const int64_t* seg_a, const int64_t* seg_b, int64_t N, const int64_t* turn_u,
+                     const int64_t* turn_v, const int32_t* turn_spk, int32_t S, double init_smoothing, int32_t* labels_host,
+                     double* w_host, double* q_host);
+/* Recording b of a batch from those turns, S = S[b] and T = T[b] as the batch was created: rho from the resident rows
+ * [row0, row0 + T) of fea with Phi as vbx_batch_set_recording_resident builds it, the initial responsibilities q by the
+ * kernel of vbx_turn_weights straight into the batch (padded speakers: 0), pi0 = 1/S.  Only the 2 T ticks and the N turns go
+ * up; no weight and no responsibility crosses the bus. */
+int vbx_batch_set_recording_turns(vbx_batch* batch, int b, const vbx_xvectors* xv, int64_t row0, const int64_t* seg_a,
+                                  const int64_t* seg_b, int64_t N, const int64_t* turn_u, const int64_t* turn_v,
+                                  const int32_t* turn_spk, double init_smoothing, const double* Phi, double loopProb, double Fa,
+                                  double Fb);
 /* vbhmm.py:160-162: np.argsort(-gamma, axis=1)[:, 0] and [:, 1] of recording b, [T] each (second: -1 when S == 1);
  * equal responsibilities keep their index order (numpy leaves the order of ties unspecified).  Either may be NULL. */
 int vbx_batch_get_labels(vbx_batch* batch, int b, int32_t* first, int32_t* second);

@@ -70,6 +70,7 @@ ABI_SYMBOLS = [
     'vbx_frame_counts', 'vbx_labels_frame_counts',
     'vbx_resample_pcm',
     'vbx_random_labels', 'vbx_batch_set_recording_random',
+    'vbx_turn_weights', 'vbx_batch_set_recording_turns',
 ]
 
 
@@ -201,6 +202,8 @@ def load():
     lib.vbx_resample_pcm.argtypes = [vp, i64, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.vbx_random_labels.argtypes = [vp, C.c_uint64, C.c_uint64, i64, i64, i32, vp]
     lib.vbx_batch_set_recording_random.argtypes = [vp, C.c_int, vp, i64, C.c_int, C.c_uint64, C.c_uint64, i64, dbl, vp, dbl, dbl, dbl]
+    lib.vbx_turn_weights.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, i32, dbl, vp, vp, vp]
+    lib.vbx_batch_set_recording_turns.argtypes = [vp, C.c_int, vp, i64, vp, vp, i64, vp, vp, vp, dbl, vp, dbl, dbl, dbl]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1050,6 +1053,22 @@ class Batch:
             float(init_smoothing), _ptr(Phi) if src < 0 else None, float(loopProb), float(Fa), float(Fb)),
             'vbx_batch_set_recording_random')
 
+    def set_recording_turns(self, b, xv: 'XVectors', row0, seg_a, seg_b, turn_u, turn_v, turn_spk, init_smoothing, Phi, loopProb,
+                            Fa, Fb):
+        """Recording b from the speaker turns of a diarization that exists (``--init RTTM+VB``): windows ``[seg_a, seg_b)``
+        and turns ``[turn_u, turn_v)`` of the speakers ``turn_spk`` in [0, S[b]), all in integer microseconds, the turns
+        sorted by (speaker, start).  The responsibilities of ``turn_weights`` are built on the device straight into the
+        batch, uniform priors, rho from the resident rows of ``xv.fea`` from ``row0`` on (vbx_batch_set_recording_turns)."""
+        seg_a, seg_b, turn_u, turn_v, turn_spk = _turn_arrays(seg_a, seg_b, turn_u, turn_v, turn_spk)
+        Phi = _f64(Phi)
+        if seg_a.shape != (self.T[b],):
+            raise ValueError(f'set_recording_turns: {seg_a.shape[0]} windows, recording {b} has {self.T[b]} x-vectors')
+        assert Phi.shape == (self.D,)
+        self.ctx.check(self._lib.vbx_batch_set_recording_turns(
+            self._h, int(b), xv._h, int(row0), _ptr(seg_a), _ptr(seg_b), turn_u.shape[0], _ptr(turn_u), _ptr(turn_v),
+            _ptr(turn_spk), float(init_smoothing), _ptr(Phi), float(loopProb), float(Fa), float(Fb)),
+            'vbx_batch_set_recording_turns')
+
     def final_elbos(self, recs=None):
         """The last ELBO of every recording of ``recs`` (default: all) after a run, nan for one that has not iterated: the
         small arrays only, one synchronize per stream (vbx_batch_get_results without responsibilities or models)."""
@@ -1224,6 +1243,37 @@ def random_labels(ctx: Context, seed, name_hash, restart, T, N, out=None) -> np.
         raise ValueError('random_labels: out must be a contiguous int32 array of T elements')
     ctx.check(ctx._lib.vbx_random_labels(ctx._h, _u64(seed), _u64(name_hash), int(restart), T, N, _ptr(out)), 'vbx_random_labels')
     return out
+
+
+def _turn_arrays(seg_a, seg_b, turn_u, turn_v, turn_spk):
+    """The five arrays of the turn entry points, contiguous in the C types; ValueError where their lengths disagree."""
+    seg_a, seg_b, turn_u, turn_v = (np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in (seg_a, seg_b, turn_u, turn_v))
+    turn_spk = np.ascontiguousarray(turn_spk, dtype=np.int32).reshape(-1)
+    if seg_a.shape != seg_b.shape or not turn_u.shape == turn_v.shape == turn_spk.shape:
+        raise ValueError(f'windows: {seg_a.shape[0]} starts and {seg_b.shape[0]} ends; turns: {turn_u.shape[0]} starts, '
+                         f'{turn_v.shape[0]} ends and {turn_spk.shape[0]} speakers')
+    return seg_a, seg_b, turn_u, turn_v, turn_spk
+
+
+def turn_weights(ctx, seg_a, seg_b, turn_u, turn_v, turn_spk, S, init_smoothing, want=('labels', 'w', 'q')):
+    """(labels int32 [T], w f64 [T][S], q f64 [T][S]) of ``--init RTTM+VB`` (vbx_turn_weights), None for
+    what ``want`` leaves out: the speaker turns ``[turn_u, turn_v)`` of ``turn_spk`` in [0, S), sorted by (speaker, start),
+    resampled on the device onto the windows ``[seg_a, seg_b)`` -- all times in integer microseconds.  ``w`` shares a window
+    among the speakers by overlap (the one-hot row of the nearest turn's speaker where nothing overlaps), ``labels`` is its
+    arg-max and ``q = softmax(init_smoothing * w)``.  Bad input is a ``VbxError`` that says what is wrong, raised before
+    the device is touched (``ctx`` None: only that check runs)."""
+    seg_a, seg_b, turn_u, turn_v, turn_spk = _turn_arrays(seg_a, seg_b, turn_u, turn_v, turn_spk)
+    T, S = seg_a.shape[0], int(S)
+    sized = T >= 1 and S >= 1
+    labels = np.empty(T, dtype=np.int32) if 'labels' in want and sized else None
+    w = np.empty((T, S)) if 'w' in want and sized else None
+    q = np.empty((T, S)) if 'q' in want and sized else None
+    lib, handle = (load(), None) if ctx is None else (ctx._lib, ctx._h)
+    rc = lib.vbx_turn_weights(handle, T, _ptr(seg_a), _ptr(seg_b), turn_u.shape[0], _ptr(turn_u), _ptr(turn_v), _ptr(turn_spk), S,
+                              float(init_smoothing), _ptr(labels), _ptr(w), _ptr(q))
+    if rc != 0:
+        raise VbxError(f'vbx_turn_weights failed ({rc}): {lib.vbx_last_error(handle).decode()}')
+    return labels, w, q
 
 
 def nan_rows(ctx: Context, x_ptr, n, D) -> np.ndarray:

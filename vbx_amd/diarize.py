@@ -304,7 +304,7 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
                   ahc_scores='cos', init_smoothing=5.0, output_2nd=False, precision='fp64', gemm='exact', embed_dim=256,
                   seg_len=144, seg_jump=24, batch_size=128, no_dither=False, dither='host', out_ark_fn=None, out_seg_fn=None,
                   log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False, resample_to=None, random_restarts=None,
-                  seed=None):
+                  seed=None, init_rttm_dir=None):
     """Diarize ``wav_dir/<name>.wav`` with the VAD labels ``lab_dir/<name>.lab`` for every name of ``file_names``.
 
     -> ``({recording: dict(labels1st, labels2nd, n_iters, thr, starts, ends)}, timing)``: per x-vector of the recording its
@@ -323,7 +323,11 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
 
     ``init='random_<N>'``: no AHC; the VB-HMM starts from random labels over N speakers, ``random_restarts`` times (default 1),
     drawn from ``seed`` (default 0) and the recording's name (``vbhmm.DeviceStages.vb_random``); an entry then also holds the
-    winning ``restart`` and the final ``elbos`` of all of them, and ``thr`` is nan."""
+    winning ``restart`` and the final ``elbos`` of all of them, and ``thr`` is nan.
+
+    ``init='RTTM+VB'`` with ``init_rttm_dir``: no AHC; the VB-HMM starts from the diarization ``<init_rttm_dir>/<name>.rttm``,
+    resampled on the device onto the windows the extraction left (``vbhmm.DeviceStages.vb_turns``); ``init='RTTM'`` returns and
+    writes that resampling alone.  ``thr`` is nan."""
     args = argparse.Namespace(
         gpus=str(device), checkpoint=checkpoint, gemm=gemm, model=None, weights=None, model_file=None, backend='pytorch',
         ndim=fbank.N_MEL, embed_dim=embed_dim, seg_len=seg_len, seg_jump=seg_jump, in_file_list=None, in_lab_dir=lab_dir,
@@ -331,18 +335,21 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
         dither=dither, init=init, out_rttm_dir=out_rttm_dir, xvec_transform=xvec_transform, plda_file=plda_file,
         threshold=threshold, lda_dim=lda_dim, Fa=Fa, Fb=Fb, loopP=loopP, target_energy=target_energy, ahc_scores=ahc_scores,
         init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False, resample_to=resample_to,
-        random_restarts=random_restarts, seed=seed)
+        random_restarts=random_restarts, seed=seed, init_rttm_dir=init_rttm_dir)
     if ref_rttm_dir is not None:
         args.ref_rttm_dir, args.collar, args.ignore_overlaps = ref_rttm_dir, collar, ignore_overlaps
     try:
         vbhmm.random_init_states(init)
     except ValueError:
-        raise ValueError(f"init must be 'AHC', 'AHC+VB' or 'random_<N>', not {init!r}") from None
+        raise ValueError(f"init must be 'AHC', 'AHC+VB', 'RTTM', 'RTTM+VB' or 'random_<N>', not {init!r}") from None
 
     def error(msg):
         raise ValueError(msg)
     _check(args, error)
     vbhmm.check_init_arguments(args, error, warn=lambda _message: None)       # (a library call has said what it wants)
+    if vbhmm.turn_init(init):                                                 # (a missing directory fails before the extraction)
+        from .turn_init import check_init_rttm_dir
+        check_init_rttm_dir(init_rttm_dir)
     return _run(args, [str(f) for f in file_names], log=log or (lambda *a: None))
 
 

@@ -40,9 +40,10 @@ __all__ = ['read_turns', 'merge_turns', 'score_turns', 'score_labels', 'labels_t
 MAX_DEVICE_SPEAKERS = 64      # speakers per side the device path takes (vbx_rttm_score.hpp: kRttmMaxSpk)
 
 
-def read_turns(path):
+def read_turns(path, durations=False):
     """``{recording: [(start, end, speaker)]}`` of the SPEAKER lines of an RTTM file, in file order; ``end`` is
-    ``start + duration`` in float64.  Other line types and blank lines are skipped."""
+    ``start + duration`` in float64.  Other line types and blank lines are skipped.  ``durations``: the entries are
+    ``(start, end, speaker, duration)``, the duration as the file gives it."""
     out = {}
     with open(path) as fp:
         for n, line in enumerate(fp, 1):
@@ -52,7 +53,7 @@ def read_turns(path):
             if len(f) < 8:
                 raise ValueError(f'{path}:{n}: a SPEAKER line has at least 8 fields')
             start, dur = float(f[3]), float(f[4])
-            out.setdefault(f[1], []).append((start, start + dur, f[7]))
+            out.setdefault(f[1], []).append((start, start + dur, f[7], dur) if durations else (start, start + dur, f[7]))
     return out
 
 

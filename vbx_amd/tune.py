@@ -30,6 +30,10 @@ Nothing else differs.
 random labels over N speakers (``--seed``; ``vbhmm.DeviceStages.vb_random``) and scores the winner by final ELBO -- again the
 labels ``python -m vbx_amd.vbhmm --init random_N`` writes at that point.
 
+``--init RTTM+VB --init-rttm-dir DIR`` runs no AHC either: every grid point starts from the same given diarization,
+``DIR/<recording>.rttm`` resampled onto the x-vector windows on the device (``vbhmm.DeviceStages.vb_turns``; DESIGN section
+24), so no T x T matrix is held and nothing is drawn.  ``RTTM`` alone is refused like ``AHC`` alone: it runs no VB-HMM.
+
 One process: refused under ``torchrun`` with several ranks, as ``--ref-rttm-dir`` is, because every rank would see only its
 share of the recordings.  As a library: ``tune`` (reads the files), ``tune_recordings`` (data in memory), ``format_table``.
 """
@@ -94,13 +98,21 @@ def check_one_rank(world=None):
 
 def check_init(args):
     """(N or None, restarts, seed) of ``args.init`` (default ``'AHC+VB'``), ``args.random_restarts`` and ``args.seed``, or
-    ValueError: the grid is one of VB-HMM parameters, so ``AHC`` alone is refused; restarts and seed need ``random_<N>``."""
-    from .vbhmm import random_init_states
+    ValueError: the grid is one of VB-HMM parameters, so ``AHC`` alone and ``RTTM`` alone are refused; restarts and seed need
+    ``random_<N>``; ``args.init_rttm_dir`` and ``RTTM+VB`` need each other."""
+    from .vbhmm import random_init_states, turn_init
     init = getattr(args, 'init', 'AHC+VB')
     n_random = random_init_states(init)
     restarts, seed = getattr(args, 'random_restarts', None), getattr(args, 'seed', None)
     if init == 'AHC':
         raise ValueError('--init AHC runs no VB-HMM: Fa, Fb and loopP change nothing; use AHC+VB or random_<N>')
+    if init == 'RTTM':
+        raise ValueError('--init RTTM runs no VB-HMM: Fa, Fb and loopP change nothing; use RTTM+VB')
+    rttm_dir = getattr(args, 'init_rttm_dir', None)
+    if turn_init(init) and rttm_dir is None:
+        raise ValueError(f'--init {init} needs --init-rttm-dir: the diarization to start from')
+    if not turn_init(init) and rttm_dir is not None:
+        raise ValueError(f'--init-rttm-dir needs --init RTTM+VB: --init {init} reads no diarization')
     if n_random is None and (restarts is not None or seed is not None):
         raise ValueError(f'--random-restarts and --seed need --init random_<N>: --init {init} draws nothing')
     restarts, seed = (1 if restarts is None else int(restarts)), (0 if seed is None else int(seed))
@@ -140,7 +152,7 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
     ``step``."""
     from concurrent.futures import ThreadPoolExecutor
     from ._capi import MAX_SPEAKERS
-    from .vbhmm import DeviceStages, _ahc_kw, tune_host_process
+    from .vbhmm import DeviceStages, _ahc_kw, tune_host_process, turn_init
     criterion, step = check_criterion(getattr(args, 'criterion', 'der'), getattr(args, 'step', None))
     extended = criterion != 'der' or step is not None
     grid = [tuple(float(v) for v in g) for g in grid]
@@ -154,6 +166,15 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
         raise ValueError('no reference turns for: ' + ', '.join(missing))
     ahc_kw = _ahc_kw(args, ahc_scores)
     n_random, restarts, seed = check_init(args)
+    given = None                                                     # --init RTTM+VB: [((a, b), (u, v, spk, S))] in ticks
+    if turn_init(getattr(args, 'init', 'AHC+VB')):
+        from .turn_init import read_init_turns, window_ticks
+        given = []
+        for name in names:
+            u, v, spk, speakers = read_init_turns(args.init_rttm_dir, name)
+            if len(speakers) > MAX_SPEAKERS:
+                raise ValueError(f'{name}: --init {args.init}: {len(speakers)} speakers, the device path takes at most {MAX_SPEAKERS}')
+            given.append((window_ticks(segs_dict[name][1]), (u, v, spk, len(speakers))))
     if t_read is None:
         t_read = time.perf_counter()
     if t_start is None:
@@ -169,7 +190,9 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
             log(name)
         # the AHC initialisation does not depend on the grid: once per recording, a few recordings side by side as in the driver
         n_workers = max(1, min(int(os.environ.get('VBX_AMD_DRIVER_THREADS', '6')), (os.cpu_count() or 2) - 1))
-        if n_random is None:
+        if given is not None:                                        # --init RTTM+VB: no AHC at all, one start for every point
+            ahc = [None] * len(recordings)
+        elif n_random is None:
             with tune_host_process(), ThreadPoolExecutor(max_workers=n_workers) as pool:
                 ahc = list(pool.map(lambda k: stages.ahc(k, args.threshold, **ahc_kw)[0], range(len(recordings))))
             if hasattr(stages, 'close_thread_contexts'):
@@ -190,6 +213,8 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
                           loopProb=loopP, Fa=Fa, Fb=Fb)
             if not ks:
                 res = []
+            elif given is not None:
+                res = stages.vb_turns(ks, [given[k][1] for k in ks], [given[k][0] for k in ks], **common)
             elif n_random is None:
                 res = stages.vb(ks, [ahc[k] for k in ks], **common)
             else:                                                    # R restarts per point and recording, the winner's labels
@@ -294,6 +319,9 @@ def tune(args, stages=None, log=print):
     check_init(args)
     if not os.path.isdir(args.ref_rttm_dir):                          # (found before the run, not after it)
         raise ValueError(f'--ref-rttm-dir {args.ref_rttm_dir}: no such directory')
+    if getattr(args, 'init_rttm_dir', None) is not None:
+        from .turn_init import check_init_rttm_dir
+        check_init_rttm_dir(args.init_rttm_dir)
     t_start = time.perf_counter()
     segs_dict = read_xvector_timing_dict(args.segments_file)
     models = load_models(args.xvec_transform, args.plda_file)
@@ -355,7 +383,9 @@ def main(argv=None):
         if not args.collar >= 0.0:
             raise ValueError('--collar must be >= 0')
         check_criterion(args.criterion, args.step)
-        if check_init(args)[0] is not None:
+        from .vbhmm import runs_ahc
+        check_init(args)
+        if not runs_ahc(args.init):
             print(f'warning: --init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored', file=sys.stderr)
     except ValueError as exc:
         parser.error(str(exc))

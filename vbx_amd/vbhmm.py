@@ -25,6 +25,10 @@ RTTM bytes as the reference driver.
 ``--init random_N`` (the reference's README.md:24) skips stage 1: stage 2 starts every recording from random
 labels over N speakers drawn on the device from (``--seed``, the recording's name, the restart), ``--random-restarts R`` times
 side by side in the one batch, and keeps the restart with the largest final ELBO.  No T x T matrix is ever held.
+
+``--init RTTM+VB --init-rttm-dir DIR`` skips stage 1 too: stage 2 starts every recording from the speaker
+turns of ``DIR/<recording>.rttm``, a diarization that exists, resampled onto the x-vector windows on the device -- the VB-HMM
+as the second stage of a system.  ``--init RTTM`` only writes that resampling out.
 """
 from __future__ import annotations
 
@@ -39,7 +43,8 @@ from .kaldi_formats import (read_plda, read_vec_flt_ark_grouped, read_xvec_trans
                             write_rttm)
 
 __all__ = ['main', 'diarize', 'diarize_recordings', 'DeviceStages', 'tune_host_process', 'load_models', 'cluster', 'cut_linkage', 'merge_adjacent_labels', 'l2_norm',
-           'random_init_states', 'name_hash', 'best_restart', 'add_init_arguments', 'check_init_arguments']
+           'random_init_states', 'name_hash', 'best_restart', 'add_init_arguments', 'check_init_arguments', 'turn_init', 'runs_vb',
+           'runs_ahc']
 
 
 def l2_norm(vec_or_matrix):
@@ -67,17 +72,29 @@ def merge_adjacent_labels(starts, ends, labels):
 
 
 def random_init_states(init):
-    """N for ``--init random_N`` (N a decimal integer >= 1), None for ``AHC`` and ``AHC+VB``; ValueError for anything else."""
-    if init in ('AHC', 'AHC+VB'):
+    """N for ``--init random_N`` (N a decimal integer >= 1), None for ``AHC``, ``AHC+VB``, ``RTTM`` and ``RTTM+VB``; ValueError
+    for anything else."""
+    if init in ('AHC', 'AHC+VB') or turn_init(init):
         return None
     head, sep, digits = str(init).partition('_')
     if head != 'random' or not sep or not digits.isascii() or not digits.isdigit() or int(digits) < 1:
-        raise ValueError(f"invalid choice: {init!r} (choose from 'AHC', 'AHC+VB', 'random_<N>' with N a decimal integer >= 1)")
+        raise ValueError(f"invalid choice: {init!r} (choose from 'AHC', 'AHC+VB', 'RTTM', 'RTTM+VB', 'random_<N>' with N a decimal "
+                         'integer >= 1)')
     return int(digits)
 
 
+def turn_init(init):
+    """Does this ``--init`` start from the speaker turns of ``--init-rttm-dir``?  RTTM and RTTM+VB do."""
+    return init in ('RTTM', 'RTTM+VB')
+
+
+def runs_ahc(init):
+    """Does this ``--init`` run the AHC stage (and hold its T x T score matrix)?"""
+    return init in ('AHC', 'AHC+VB')
+
+
 def runs_vb(init):
-    """Does this ``--init`` run the VB-HMM?  AHC+VB and random_N do (README.md:24: 'and run VBx')."""
+    """Does this ``--init`` run the VB-HMM?  AHC+VB, RTTM+VB and random_N do (README.md:24: 'and run VBx')."""
     return init.endswith('VB') or random_init_states(init) is not None
 
 
@@ -148,6 +165,9 @@ class DeviceStages:
               labels come back
     vb_random ``--init random_N``: no AHC; the restarts of ALL recordings in one ``vbx_batch``, every restart from labels drawn
               on the device, the restarts of a recording around one rho; the winner by final ELBO, only its labels come back
+    vb_turns  ``--init RTTM+VB``: no AHC; initial responsibilities from the speaker turns of a diarization that exists,
+              resampled onto the x-vector windows on the device: only window edges and turns go up (``turn_labels``: ``--init
+              RTTM``, that resampling alone)
     """
 
     def __init__(self, device=None):
@@ -300,6 +320,41 @@ class DeviceStages:
             batch.close()
         return out
 
+    def turn_labels(self, k, turns, segments):
+        """-> the labels of ``--init RTTM`` for recording k: per window ``segments`` = (a, b) the speaker of ``turns`` =
+        (u, v, spk, S) (``turn_init.turn_ticks``, all in ticks) with the largest overlap, the nearest turn's where none overlaps
+        (``_capi.turn_weights``, on the device)."""
+        (a, b), (u, v, spk, S) = segments, turns
+        if len(a) != self.T[k]:
+            raise ValueError(f'recording {k}: {len(a)} windows in the segments file, {self.T[k]} x-vectors')
+        return self._capi.turn_weights(self._thread_ctx(), a, b, u, v, spk, S, 0.0, want=('labels',))[0].astype(np.int64)
+
+    def vb_turns(self, ks, turns, segments, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
+        """-> [(labels1st, labels2nd or None, iterations)] for the recordings ``ks`` started from given speaker turns, ``--init
+        RTTM+VB``: ``turns[j]`` = (u, v, spk, S) and ``segments[j]`` = (a, b) of ``ks[j]``, all in ticks (``turn_init``).
+
+        One ``vbx_batch`` per padded state count, as in ``vb``; the responsibilities are built on the device from the ticks
+        (``Batch.set_recording_turns``)."""
+        buckets = {}
+        for j, t in enumerate(turns):
+            buckets.setdefault(self.padded_states(int(t[3])), []).append(j)
+        out = [None] * len(ks)
+        for _sp, members in sorted(buckets.items()):
+            batch = self._capi.Batch(self.ctx, [self.T[ks[j]] for j in members], [int(turns[j][3]) for j in members], self.lda_dim,
+                                     precision=precision, max_iters=maxIters)
+            try:
+                for b, j in enumerate(members):
+                    (a, e), (u, v, spk, _S) = segments[j], turns[j]
+                    batch.set_recording_turns(b, self.xv, self.row0[ks[j]], a, e, u, v, spk, init_smoothing, self.Phi, loopProb,
+                                              Fa, Fb)
+                batch.run(maxIters, epsilon)
+                for b, j in enumerate(members):
+                    first, second = batch.labels(b)
+                    out[j] = (first, second, batch.n_iters(b))
+            finally:
+                batch.close()
+        return out
+
     def close_thread_contexts(self):
         """The per-thread contexts (a HIP stream each) of the AHC stage: closed before the VB batch creates its stream
         group, so that the group's streams do not share hardware queues with idle ones (8 queues per process)."""
@@ -410,9 +465,12 @@ def diarize(args, stages=None, log=print, ahc_scores=None):
     recordings = _read_recordings(args.xvec_ark_file)
     rank, world = _rank_world()
     if world > 1:                                                 # AHC is O(T^2), the VB loop O(T S): deal by T^2
-        power = 2 if random_init_states(args.init) is None else 1        # (random_N: no AHC; the labels do not depend on the deal)
+        power = 2 if runs_ahc(args.init) else 1                          # (no AHC: O(T); the labels do not depend on the deal)
         assignment = shard_recordings([float(len(r[1])) ** power for r in recordings], world)
         recordings = [r for k, r in enumerate(recordings) if assignment[k] == rank]
+    if turn_init(args.init):                                      # (a missing directory fails before anything runs)
+        from .turn_init import check_init_rttm_dir
+        check_init_rttm_dir(getattr(args, 'init_rttm_dir', None))
     t_read = time.perf_counter()
     ref_rttm_dir = getattr(args, 'ref_rttm_dir', None)
     if ref_rttm_dir is not None:
@@ -469,7 +527,8 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
     """The stages of ``diarize`` for recordings already in memory: ``[(name, seg_names, x_or_None)]``, ``segs_dict`` as
     ``read_xvector_timing_dict`` gives it, ``models`` from ``load_models``, ``args`` with the hyper-parameters
     (init, threshold, lda_dim, Fa, Fb, loopP, init_smoothing, output_2nd, out_rttm_dir and, optionally, precision,
-    ahc_scores, target_energy).  Returns what ``diarize`` returns.
+    ahc_scores, target_energy; init_rttm_dir with init = RTTM or RTTM+VB: ``<init_rttm_dir>/<name>.rttm`` is read for every
+    recording given, and for no other).  Returns what ``diarize`` returns.
 
     ``xvectors``: the x-vectors of all recordings, in order, projected on the device already (``XVectors.from_device``,
     ``fea_dim`` = ``args.lda_dim``); the third entry of a recording is not read then and nothing is uploaded
@@ -489,6 +548,15 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
     if restarts < 1 or seed < 0 or seed >= 1 << 64:
         raise ValueError(f'random_restarts={restarts} must be >= 1, seed={seed} in [0, 2^64)')
     want_vb = runs_vb(args.init)
+    given = None                                                 # --init RTTM / RTTM+VB: {name: ((a, b), (u, v, spk, S))} in ticks
+    if turn_init(args.init):
+        from .turn_init import read_init_turns, window_ticks
+        given = {}
+        for name, _seg_names, _x in recordings:                  # (only the files of the recordings of this rank)
+            u, v, spk, speakers = read_init_turns(getattr(args, 'init_rttm_dir', None), name)
+            given[name] = (window_ticks(segs_dict[name][1]), (u, v, spk, len(speakers)))
+    elif getattr(args, 'init_rttm_dir', None) is not None:
+        raise ValueError('init_rttm_dir needs init = RTTM or RTTM+VB')
     own_stages = stages is None
     if own_stages:
         stages = DeviceStages()
@@ -510,6 +578,15 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
             file_name, seg_names, _ = recordings[k]
             if n_random is not None:                                  # (no score matrix, no calibration: thr is nan)
                 return file_name, dict(labels1st=None, labels2nd=None, thr=float('nan'), n_iters=0, seg_names=seg_names)
+            if given is not None:
+                st = dict(labels1st=None, labels2nd=None, thr=float('nan'), n_iters=0, seg_names=seg_names)
+                segments, turns = given[file_name]
+                if turns[3] > MAX_SPEAKERS:                           # (reported with the others after the run)
+                    return file_name, st
+                if not want_vb:                                       # RTTM only: the given turns on the windows are final
+                    st['labels1st'] = stages.turn_labels(k, turns, segments)
+                    _write_rttm_files(args, file_name, st, segs_dict)
+                return file_name, st
             labels1st, thr = stages.ahc(k, args.threshold, **ahc_kw)
             st = dict(labels1st=labels1st, labels2nd=None, thr=thr, n_iters=0, seg_names=seg_names)
             if not want_vb:
@@ -544,6 +621,12 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
                     else:
                         ks.append(k)
                     continue
+                if given is not None:
+                    if given[name][1][3] > MAX_SPEAKERS:
+                        failed[name] = f'--init {args.init}: {given[name][1][3]} speakers, the device path takes at most {MAX_SPEAKERS}'
+                    else:
+                        ks.append(k)
+                    continue
                 n_clusters = int(np.max(state[name]['labels1st'])) + 1
                 if n_clusters > MAX_SPEAKERS:
                     failed[name] = f'AHC left {n_clusters} clusters, the device path takes at most {MAX_SPEAKERS}'
@@ -560,6 +643,8 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
             def run_vb(some):
                 if n_random is not None:
                     return stages.vb_random(some, n_random, restarts, seed, [names[k] for k in some], **common)
+                if given is not None:
+                    return stages.vb_turns(some, [given[names[k]][1] for k in some], [given[names[k]][0] for k in some], **common)
                 return stages.vb(some, [state[names[k]]['labels1st'] for k in some], **common)
 
             try:
@@ -572,6 +657,10 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
                         finish(k, run_vb([k])[0])
                     except VbxError as exc_k:
                         failed[names[k]] = str(exc_k)
+        elif given is not None:                                       # RTTM only: too many speakers is reported as above
+            for name, (_segments, turns) in given.items():
+                if turns[3] > MAX_SPEAKERS:
+                    failed[name] = f'--init {args.init}: {turns[3]} speakers, the device path takes at most {MAX_SPEAKERS}'
         t_vb = time.perf_counter()
     finally:
         if own_stages:
@@ -631,10 +720,16 @@ def _init_argument(value):
 
 
 def add_init_arguments(p, default=None):
-    """``--init``, ``--random-restarts`` and ``--seed`` of vbhmm, diarize and tune.  ``default`` None: ``--init`` is required."""
-    p.add_argument('--init', required=default is None, default=default, type=_init_argument, metavar='{AHC,AHC+VB,random_<N>}',
+    """``--init``, ``--random-restarts``, ``--seed`` and ``--init-rttm-dir`` of vbhmm, diarize and tune.  ``default`` None:
+    ``--init`` is required."""
+    p.add_argument('--init', required=default is None, default=default, type=_init_argument,
+                   metavar='{AHC,AHC+VB,RTTM,RTTM+VB,random_<N>}',
                    help='AHC for using only AHC, AHC+VB for VB-HMM after AHC initilization, random_<N> for VB-HMM from random '
-                        'labels over N speakers without any AHC (long recordings: AHC holds a T x T matrix)')
+                        'labels over N speakers without any AHC (long recordings: AHC holds a T x T matrix), RTTM+VB for VB-HMM '
+                        'from the diarization in --init-rttm-dir without any AHC, RTTM for only resampling that diarization '
+                        'onto the x-vector windows')
+    p.add_argument('--init-rttm-dir', required=False, type=str, default=None, metavar='DIR',
+                   help='with --init RTTM or RTTM+VB: the diarization to start from, DIR/<recording>.rttm for every recording')
     p.add_argument('--random-restarts', required=False, type=int, default=None, metavar='R',
                    help='with --init random_<N>: runs from R different random labellings, the one with the largest final ELBO '
                         'wins (default: 1)')
@@ -644,11 +739,23 @@ def add_init_arguments(p, default=None):
 
 def check_init_arguments(args, error, warn=None):
     """After parsing: ``--random-restarts`` and ``--seed`` are refused (``error(message)``) unless ``--init`` is random_N and get
-    their defaults 1 and 0; with random_N one line goes to ``warn`` (default: stderr) about the AHC options that are ignored."""
+    their defaults 1 and 0; ``--init-rttm-dir`` is refused unless ``--init`` is RTTM or RTTM+VB, which in turn need it.  With
+    anything but AHC and AHC+VB one line goes to ``warn`` (default: stderr) about the AHC options that are ignored."""
+    rttm_dir = getattr(args, 'init_rttm_dir', None)
+    if turn_init(args.init) and rttm_dir is None:
+        error(f'--init {args.init} needs --init-rttm-dir: the diarization to start from')
+    if not turn_init(args.init) and rttm_dir is not None:
+        error(f'--init-rttm-dir needs --init RTTM or RTTM+VB: --init {args.init} reads no diarization')
     if random_init_states(args.init) is None:
         for flag, value in (('--random-restarts', args.random_restarts), ('--seed', args.seed)):
             if value is not None:
                 error(f'{flag} needs --init random_<N>: --init {args.init} draws nothing')
+        if turn_init(args.init):
+            message = f'--init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored'
+            if warn is None:
+                print(f'warning: {message}', file=sys.stderr)
+            else:
+                warn(message)
         return
     if args.random_restarts is None:
         args.random_restarts = 1
