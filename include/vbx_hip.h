@@ -727,6 +727,34 @@ int vbx_resnet_pool_ragged(vbx_ctx* ctx, int32_t n, const int32_t* W4, const flo
  * over the W4 frames, [8192 + h 1024 + c] sqrt(mean(x^2) - mean^2 + 1e-10), summed in f64. */
 int vbx_resnet_pool(vbx_ctx* ctx, int32_t n, int32_t W4, const float* x, float* out, int64_t pad);
 
+/* ---- training the x-vector backend: the LDA transform and the Kaldi PLDA the chain reads (vbx_backend.hpp) ------------------
+ * The passes over N labelled x-vectors; the D x D algebra between and after them (a generalised eigenproblem, the PLDA's EM)
+ * stays with the caller (vbx_amd/backend.py).  Everything is float64, summed over fixed chunks of 512 rows in a fixed order:
+ * the same input gives the same bits on every run.
+ * Refused with VBX_ERR_INVALID and a message before the device is touched: a NULL pointer, N, D or K < 1, D > 1024, a class
+ * outside [0, K), a class without a row, offsets that descend or leave the rows.
+ *
+ * sums [K][D] = the sums of the rows x [N][D] (x_dtype VBX_F32 or VBX_F64) of every class, the rows of a class added in
+ * archive order; counts [K] (NULL: not wanted) = its rows. */
+int vbx_backend_class_sums(vbx_ctx* ctx, int64_t N, int32_t D, const void* x, int x_dtype, int32_t K, const int32_t* class_of_row,
+                           double* sums, int64_t* counts);
+/* out [G][D][D], out[g] = sum over the rows t in [offsets[g], offsets[g + 1]) of rows[t] rows[t]^T, rows [R][D]; a segment
+ * without rows gives zero.  Every out[g] is symmetric to the last bit. */
+int vbx_backend_second_moments(vbx_ctx* ctx, int64_t R, int32_t D, const double* rows, int64_t G, const int64_t* offsets, double* out);
+/* The x-vectors x [N][Din] and their classes, resident in HBM across the two stages. */
+typedef struct vbx_backend vbx_backend;
+int vbx_backend_create(vbx_ctx* ctx, int64_t N, int32_t Din, const void* x, int x_dtype, int32_t K, const int32_t* class_of_row,
+                       vbx_backend** out);
+/* mean1 [Din] = the mean of the rows; y = l2norm(x - mean1) stays in HBM; class_sums [K][Din] and moment [Din][Din] =
+ * sum_t y_t y_t^T are those of y.  A row without length after centring is refused with its index (VBX_ERR_INVALID).
+ * kernel_ms (NULL: not wanted): the time of the stage's kernels on the device, between two events. */
+int vbx_backend_stage1(vbx_backend* be, double* mean1, double* class_sums, double* moment, double* kernel_ms);
+/* u = l2norm(y lda - mean2), lda [Din][Dl], mean2 [Dl], 1 <= Dl <= Din: the rows xproj of vbx_xvectors_project.
+ * class_sums [K][Dl] and moment [Dl][Dl] are those of u.  Needs stage 1. */
+int vbx_backend_stage2(vbx_backend* be, int32_t Dl, const double* lda, const double* mean2, double* class_sums, double* moment,
+                       double* kernel_ms);
+int vbx_backend_destroy(vbx_backend* be);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     'vbx_resample_pcm',
     'vbx_random_labels', 'vbx_batch_set_recording_random',
     'vbx_turn_weights', 'vbx_batch_set_recording_turns',
+    'vbx_backend_class_sums', 'vbx_backend_second_moments', 'vbx_backend_create', 'vbx_backend_stage1', 'vbx_backend_stage2',
+    'vbx_backend_destroy',
 ]
 
 
@@ -204,6 +206,12 @@ def load():
     lib.vbx_batch_set_recording_random.argtypes = [vp, C.c_int, vp, i64, C.c_int, C.c_uint64, C.c_uint64, i64, dbl, vp, dbl, dbl, dbl]
     lib.vbx_turn_weights.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, i32, dbl, vp, vp, vp]
     lib.vbx_batch_set_recording_turns.argtypes = [vp, C.c_int, vp, i64, vp, vp, i64, vp, vp, vp, dbl, vp, dbl, dbl, dbl]
+    lib.vbx_backend_class_sums.argtypes = [vp, i64, i32, vp, C.c_int, i32, vp, vp, vp]
+    lib.vbx_backend_second_moments.argtypes = [vp, i64, i32, vp, i64, vp, vp]
+    lib.vbx_backend_create.argtypes = [vp, i64, i32, vp, C.c_int, i32, vp, C.POINTER(vp)]
+    lib.vbx_backend_stage1.argtypes = [vp, vp, vp, vp, C.POINTER(dbl)]
+    lib.vbx_backend_stage2.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(dbl)]
+    lib.vbx_backend_destroy.argtypes = [vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
@@ -1302,6 +1310,86 @@ def plda_covariance_resident(ctx: Context, xv: 'XVectors', row0, T):
     ctx.check(ctx._lib.vbx_plda_covariance_resident(ctx._h, xv._h, int(row0), int(T), _ptr(mean), _ptr(cov)),
               'vbx_plda_covariance_resident')
     return mean, cov
+
+
+BACKEND_MAX_DIM = 1024       # dimensions of a segmented second moment (vbx_backend.hpp: kBackendMaxDim)
+
+
+def _rows_f32_or_f64(x):
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x, dtype=np.float32 if x.dtype == np.float32 else np.float64)
+    assert x.ndim == 2
+    return x, (VBX_F32 if x.dtype == np.float32 else VBX_F64)
+
+
+def backend_class_sums(ctx: Context, x, class_of_row, K):
+    """(sums [K][D] f64, counts [K]) of the rows ``x`` [N][D] (f32 or f64) by class, the rows of a class added in archive
+    order over fixed chunks (vbx_backend_class_sums)."""
+    x, dt = _rows_f32_or_f64(x)
+    cls = np.ascontiguousarray(class_of_row, dtype=np.int32)
+    assert cls.shape == (x.shape[0],)
+    sums, counts = np.empty((max(int(K), 0), x.shape[1])), np.empty(max(int(K), 0), dtype=np.int64)
+    ctx.check(ctx._lib.vbx_backend_class_sums(ctx._h, x.shape[0], x.shape[1], _ptr(x), dt, int(K), _ptr(cls), _ptr(sums), _ptr(counts)),
+              'vbx_backend_class_sums')
+    return sums, counts
+
+
+def backend_second_moments(ctx: Context, rows, offsets):
+    """out [G][D][D], out[g] = sum of r r^T over the rows [offsets[g], offsets[g + 1]) of ``rows`` [R][D]
+    (vbx_backend_second_moments): float64 on the matrix cores, fixed summation order, symmetric to the last bit."""
+    rows = _f64(rows)
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    assert rows.ndim == 2 and off.ndim == 1 and off.size >= 1
+    G, D = off.size - 1, rows.shape[1]
+    out = np.empty((max(G, 0), D, D))
+    ctx.check(ctx._lib.vbx_backend_second_moments(ctx._h, rows.shape[0], D, _ptr(rows), G, _ptr(off), _ptr(out)),
+              'vbx_backend_second_moments')
+    return out
+
+
+class BackendStats:
+    """Labelled x-vectors resident in HBM across the two statistics stages of backend training (vbx_backend)."""
+
+    def __init__(self, ctx: Context, x, class_of_row, K):
+        x, dt = _rows_f32_or_f64(x)
+        cls = np.ascontiguousarray(class_of_row, dtype=np.int32)
+        assert cls.shape == (x.shape[0],)
+        self._ctx, self._lib = ctx, ctx._lib
+        self.n, self.din, self.k = x.shape[0], x.shape[1], int(K)
+        self.kernel_ms = [None, None]
+        h = C.c_void_p()
+        ctx.check(self._lib.vbx_backend_create(ctx._h, self.n, self.din, _ptr(x), dt, self.k, _ptr(cls), C.byref(h)), 'vbx_backend_create')
+        self._h = h
+
+    def stage1(self):
+        """(mean1 [Din], class sums [K][Din] and second moment [Din][Din] of y = l2norm(x - mean1))."""
+        mean1, cs, m2, ms = np.empty(self.din), np.empty((self.k, self.din)), np.empty((self.din, self.din)), C.c_double()
+        self._ctx.check(self._lib.vbx_backend_stage1(self._h, _ptr(mean1), _ptr(cs), _ptr(m2), C.byref(ms)), 'vbx_backend_stage1')
+        self.kernel_ms[0] = ms.value
+        return mean1, cs, m2
+
+    def stage2(self, lda, mean2):
+        """(class sums [K][dl], second moment [dl][dl]) of u = l2norm(y lda - mean2)."""
+        lda, mean2 = _f64(lda), _f64(mean2)
+        assert lda.ndim == 2 and lda.shape[0] == self.din and mean2.shape == (lda.shape[1],)
+        dl = lda.shape[1]
+        cs, m2, ms = np.empty((self.k, dl)), np.empty((dl, dl)), C.c_double()
+        self._ctx.check(self._lib.vbx_backend_stage2(self._h, dl, _ptr(lda), _ptr(mean2), _ptr(cs), _ptr(m2), C.byref(ms)), 'vbx_backend_stage2')
+        self.kernel_ms[1] = ms.value
+        return cs, m2
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.vbx_backend_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def plda_score_lda(ctx: Context, Fe, Ft, diagAC):

@@ -53,6 +53,7 @@ using namespace vbx;
 #include "vbx_labels_frame.hpp"  // ... of label sequences: the turns built on the device, the reference's side once per recording
 #include "vbx_resample.hpp"      // any PCM recording to mono int16 at 8 or 16 kHz: decode, downmix, polyphase filter
 #include "vbx_turn_init.hpp"     // --init RTTM+VB: speaker turns resampled onto the x-vector windows, into a batch's responsibilities
+#include "vbx_backend.hpp"       // training the backend: class sums and segmented second moments of labelled x-vectors
 
 #ifdef VBX_PHASE_CLOCKS
 // instrumentation builds only: the per-tile phase stamps of chunk_post_mid_kernel (tile, {wave 0, wave 2}, 8)
