@@ -263,6 +263,21 @@ int vbx_batch_gemm_in_effect(const vbx_batch* b);
 /* 1 if the per-chunk kernels of the last vbx_batch_run fetched rho with non-temporal loads (VBX_OPT_STREAM_LOADS asks, the
  * batch's size and kernels decide; a batch on several streams: every sub-batch), else 0. */
 int vbx_batch_stream_loads_in_effect(const vbx_batch* b);
+/* The launch plan of the last vbx_batch_run, read-only: which instances of the iteration's kernels it launched.  Writes the
+ * first min(n, VBX_PLAN_FIELDS) of these into out and returns VBX_PLAN_FIELDS (fields are only ever appended), or
+ * VBX_ERR_INVALID:
+ *    0 fused_post    chunk_post ran (gamma stays on the chip)          7 fold         chunk_post walked the last walk level (FOLD)
+ *    1 fused_loglik  ... and chunk_loglik                              8 walk_levels  boundary walk: 1 flat, 2 groups, 3 groups of groups
+ *    2 half_ops      ... with half-tile operators                      9 fin_threads  block size of fin_kernel
+ *    3 split         f16 operand pairs (VBX_OPT_GEMM)                 10 Sp           padded state count
+ *    4 stream        ... in the non-temporal instances                11 use_chunked  chunked scan (else the sequential walk)
+ *    5 small         the batch does not fill the chip                 12 sgroup       chunks per group in effect (1: flat)
+ *    6 lat           LAT wanted (chunk_loglik has an instance of it   13 sgroup2      groups per level-2 group in effect (1: none)
+ *                    in split mode only)
+ * A batch that has never run reports the all-false plan; a batch on several streams the plan of its first sub-batch.  For tests
+ * and diagnostics: nothing is to be decided on it. */
+#define VBX_PLAN_FIELDS 14
+int vbx_batch_plan(const vbx_batch* b, int* out, int n);
 /* The rule of VBX_STREAM_LOADS_AUTO as a function of the bytes of ONE copy of the x-vectors that iterate together (sum of
  * T x padded D x element size over the recordings that own their x-vectors): 1 = non-temporal loads.  Host only. */
 int vbx_stream_loads_auto(int64_t rho_bytes);

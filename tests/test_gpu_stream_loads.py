@@ -63,6 +63,9 @@ def _oracle(T, S, D):
     return _ORACLE[T, S, D]
 
 
+_PLAN = {}                   # the launch plan of the last _run (Batch.plan)
+
+
 def _run(ctx, recs, precision, mode, shared_from=None, iters=3):
     """recs: list of (X, Phi, g0, lp, Fa, Fb) on the chunked kernels (the fused per-chunk kernels at any T) with
     VBX_OPT_STREAM_LOADS = mode -> (results, did the streaming instances run)."""
@@ -81,6 +84,8 @@ def _run(ctx, recs, precision, mode, shared_from=None, iters=3):
             else:
                 batch.set_recording(k, X, Phi, np.ones(S) / S, g0, lp, fa, fb)
         batch.run(iters, -np.inf)
+        _PLAN.clear()
+        _PLAN.update(batch.plan)
         return [batch.result(k) for k in range(len(recs))], batch.stream_loads
     finally:
         batch.close()
@@ -143,7 +148,9 @@ def test_forced_on_where_chunk_post_would_walk_the_last_level_itself(ctx):
     X, Phi, g0 = _inputs(10000, 30, 128)
     rec = (X, Phi, g0, 0.95, 0.3, 17.0)
     (on,), ran_on = _run(ctx, [rec], 'fp32-split', 'on')
+    assert _PLAN['walk_levels'] == 2 and not _PLAN['fold'] and _PLAN['stream']
     (off,), ran_off = _run(ctx, [rec], 'fp32-split', 'off')
+    assert _PLAN['walk_levels'] == 2 and _PLAN['fold'] and not _PLAN['stream']
     assert ran_on and not ran_off
     for k in ('gamma', 'pi', 'Li'):
         assert np.array_equal(on[k], off[k]), (k, float(np.abs(on[k] - off[k]).max()))

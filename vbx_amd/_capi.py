@@ -22,6 +22,10 @@ OPT_ASYNC_UPLOAD = 15        # setters only enqueue; one synchronize when the ne
 OPT_STREAM_LOADS = 16        # non-temporal loads of rho in the per-chunk kernels: auto (by the bytes that iterate together) | on | off
 STREAM_LOADS_AUTO, STREAM_LOADS_ON, STREAM_LOADS_OFF = 0, 1, 2
 STREAM_LOADS_NAMES = {'auto': STREAM_LOADS_AUTO, 'on': STREAM_LOADS_ON, 'off': STREAM_LOADS_OFF}
+# fields of vbx_batch_plan, in its order (include/vbx_hip.h)
+PLAN_FIELDS = ['fused_post', 'fused_loglik', 'half_ops', 'split', 'stream', 'small', 'lat', 'fold', 'walk_levels', 'fin_threads',
+               'Sp', 'use_chunked', 'sgroup', 'sgroup2']
+PLAN_FLAGS = PLAN_FIELDS[:8] + ['use_chunked']
 K_NAMES = ['prep', 'mstep_acc', 'mstep_fin', 'loglik', 'fb', 'fb_aux', 'post', 'iter_fin', 'chunk_loglik',
            'chunk_post']
 MAX_SPEAKERS = 16384
@@ -53,7 +57,7 @@ ABI_SYMBOLS = [
     'vbx_scores_destroy',
     'vbx_xvectors_project', 'vbx_xvectors_get', 'vbx_xvectors_destroy', 'vbx_cos_similarity_resident',
     'vbx_batch_set_recording_resident', 'vbx_batch_get_labels', 'vbx_batch_set_recording_shared',
-    'vbx_batch_gemm_in_effect', 'vbx_batch_stream_loads_in_effect', 'vbx_stream_loads_auto',
+    'vbx_batch_gemm_in_effect', 'vbx_batch_stream_loads_in_effect', 'vbx_stream_loads_auto', 'vbx_batch_plan',
     'vbx_batch_stream_of', 'vbx_batch_sync_uploads', 'vbx_batch_get_results', 'vbx_host_alloc', 'vbx_host_free',
     'vbx_fbank_create', 'vbx_fbank_run', 'vbx_fbank_get', 'vbx_fbank_windows', 'vbx_fbank_times', 'vbx_fbank_destroy',
     'vbx_resnet_create', 'vbx_resnet_input', 'vbx_resnet_run', 'vbx_resnet_times', 'vbx_resnet_destroy',
@@ -126,6 +130,7 @@ def load():
     lib.vbx_batch_gemm_in_effect.argtypes = [vp]
     lib.vbx_batch_stream_loads_in_effect.argtypes = [vp]
     lib.vbx_stream_loads_auto.argtypes = [i64]
+    lib.vbx_batch_plan.argtypes = [vp, vp, C.c_int]
     lib.vbx_run.argtypes = [vp, vp, vp]
     lib.vbx_forward_backward.argtypes = [vp, i64, i32, vp, vp, vp, dbl, C.c_int, C.c_int, vp, C.POINTER(dbl),
                                          vp, vp, vp]
@@ -1154,6 +1159,16 @@ class Batch:
     def stream_loads(self) -> bool:
         """True when the per-chunk kernels of the last run fetched rho with non-temporal loads (VBX_OPT_STREAM_LOADS in effect)."""
         return bool(self._lib.vbx_batch_stream_loads_in_effect(self._h))
+
+    @property
+    def plan(self) -> dict:
+        """The launch plan of the last run (vbx_batch_plan): which kernel instances its iterations launched -- flags as bool,
+        ``walk_levels``, ``fin_threads``, ``Sp``, ``sgroup``, ``sgroup2`` as int.  Several streams: the first sub-batch's."""
+        out = np.zeros(len(PLAN_FIELDS), dtype=np.int32)
+        n = int(self._lib.vbx_batch_plan(self._h, _ptr(out), len(out)))
+        self.ctx.check(min(n, 0), 'vbx_batch_plan')
+        assert n >= len(PLAN_FIELDS), n
+        return {k: bool(v) if k in PLAN_FLAGS else int(v) for k, v in zip(PLAN_FIELDS, out)}
 
     def kernel_times(self):
         ms = np.zeros(len(K_NAMES))

@@ -343,4 +343,17 @@ int vbx_score_posteriors(vbx_ctx* ctx, int64_t T, int32_t S, const double* gamma
     return with_precision(precision, [&](auto r) { return score_posteriors_impl<decltype(r)>(ctx, T, S, gamma, ref, n_ref, conf); });
 }
 
+// The launch plan of the last run, for the tests that must know which instance they ran (tests/test_gpu_onestep.py): a getter
+// beside vbx_batch_gemm_in_effect / vbx_batch_stream_loads_in_effect, kept in this part -- the entry points of the parity tests
+// -- so that the sources an iteration is built from (vbx_amd/build.py: ITERATION_SOURCES) stay what the profiles were taken on.
+int vbx_batch_plan(const vbx_batch* b, int* out, int n) {
+    if (!b || (n > 0 && !out)) return VBX_ERR_INVALID;
+    const vbx_batch* l = b->kids.empty() ? b : b->kids[0];     // (a batch on several streams: its first sub-batch)
+    const IterPlan& p = l->plan;
+    const int f[VBX_PLAN_FIELDS] = {p.fused_post, p.fused_loglik, p.half_ops, p.split, p.stream, p.small, p.lat, p.fold,
+                                    p.walk_levels, p.fin_threads, l->Sp, l->use_chunked, l->sgroup, l->sgroup2};
+    for (int i = 0; i < std::min(n, (int)VBX_PLAN_FIELDS); ++i) out[i] = f[i];
+    return VBX_PLAN_FIELDS;
+}
+
 }  // extern "C"
