@@ -380,7 +380,8 @@ int vbx_random_labels(vbx_ctx* ctx, uint64_t seed, uint64_t name_hash, int64_t r
 /* Recording b of a batch from those labels with N = S[b]: drawn on the device into scratch and turned into the initial
  * responsibilities softmax(init_smoothing * onehot(labels)) there, pi0 = 1/S -- what vbx_batch_set_recording_resident does with
  * labels from the host, bit for bit; no label and no responsibility crosses the bus.
- *   src_b < 0:  b owns a rho built from the resident rows [row0, row0 + T) of fea with Phi, as _resident builds it.
+ *   src_b < 0:  b owns a rho built from the resident rows [row0, row0 + T) of fea with Phi: the one path of every setter that
+ *               reads resident rows (rho_from_resident, vbx_amd/csrc/vbx_host_set.hpp).
  *   src_b >= 0: b runs on the rho (and Phi) of recording src_b, under the rules of vbx_batch_set_recording_shared: same T,
  *               src_b set before (by any of the setters), one copy of the rows per stream sub-batch; xv, row0 and Phi are
  *               not read and may be 0 / NULL.  The restarts of a recording: restart 0 owns, the others share with it. */
@@ -402,7 +403,7 @@ int vbx_turn_weights(vbx_ctx* ctx, int64_t T, const int64_t* seg_a, const int64_
                      const int64_t* turn_v, const int32_t* turn_spk, int32_t S, double init_smoothing, int32_t* labels_host,
                      double* w_host, double* q_host);
 /* Recording b of a batch from those turns, S = S[b] and T = T[b] as the batch was created: rho from the resident rows
- * [row0, row0 + T) of fea with Phi as vbx_batch_set_recording_resident builds it, the initial responsibilities q by the
+ * [row0, row0 + T) of fea with Phi on the path every setter of resident rows takes (rho_from_resident), the initial responsibilities q by the
  * kernel of vbx_turn_weights straight into the batch (padded speakers: 0), pi0 = 1/S.  Only the 2 T ticks and the N turns go
  * up; no weight and no responsibility crosses the bus. */
 int vbx_batch_set_recording_turns(vbx_batch* batch, int b, const vbx_xvectors* xv, int64_t row0, const int64_t* seg_a,

@@ -41,7 +41,7 @@ using namespace vbx;
 #include "vbx_host_launch.hpp"   // launch helpers of an iteration, allocator
 #include "vbx_host_call.hpp"     // the device scratch and error state of a one-shot entry point
 #include "vbx_host_batch.hpp"    // context API; a batch on one stream
-#include "vbx_host_group.hpp"    // stream groups, the public vbx_batch_* entry points, vbx_run
+#include "vbx_host_group.hpp"    // stream groups, the public vbx_batch_* entry points but the setters, vbx_run
 #include "vbx_host_steps.hpp"    // step-level API of the parity tests
 #include "vbx_host_ahc.hpp"      // AHC score stage, x-vector front end, linkage
 #include "vbx_host_fbank.hpp"    // filterbank front end of the x-vector extractor
@@ -52,7 +52,8 @@ using namespace vbx;
 #include "vbx_frame_score.hpp"   // frame counts behind dscore's JER, B-cubed and information-theoretic columns
 #include "vbx_labels_frame.hpp"  // ... of label sequences: the turns built on the device, the reference's side once per recording
 #include "vbx_resample.hpp"      // any PCM recording to mono int16 at 8 or 16 kHz: decode, downmix, polyphase filter
-#include "vbx_turn_init.hpp"     // --init RTTM+VB: speaker turns resampled onto the x-vector windows, into a batch's responsibilities
+#include "vbx_turn_init.hpp"     // --init RTTM+VB: speaker turns resampled onto the x-vector windows
+#include "vbx_host_set.hpp"      // the six ways a batch slot is set: one path (needs the resident x-vectors and the two kernels above)
 #include "vbx_backend.hpp"       // training the backend: class sums and segmented second moments of labelled x-vectors
 
 #ifdef VBX_PHASE_CLOCKS

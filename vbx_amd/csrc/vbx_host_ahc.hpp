@@ -228,194 +228,6 @@ int vbx_random_labels(vbx_ctx* ctx, uint64_t seed, uint64_t name_hash, int64_t r
     return call.finish("vbx_random_labels failed");
 }
 
-// ---- --init random_N: a batch slot from labels drawn on the device.  The leaf setter and the public entry
-// live here, beside the kernel's stand-alone entry, not with the other setters in vbx_host_batch.hpp / vbx_host_group.hpp:
-// they launch nothing of an EM iteration.
-extern "C++" {
-namespace {
-// recording `rec` with random initial labels (--init random_N): d_fea != nullptr: rho, Phi and sum G from the resident rows, as
-// set_recording_resident_impl builds them; d_fea == nullptr: the caller has put them in place (a shared or cloned rho).  Either
-// way the labels are drawn into the staging block, qinit_kernel turns them into gamma, pi0 = 1/S.  Nothing of an upload is
-// left pending: the call ends with a synchronize, like the resident setter.
-template <typename R>
-int set_recording_random_impl(vbx_batch* b, int rec, const double* d_fea, const double* Phi, uint64_t seed, uint64_t name_hash,
-                              uint64_t restart, double hi, double lo) {
-    vbx_ctx* ctx = b->ctx;
-    RecDesc& rd = b->recs[rec];
-    const int D = b->D, Dp = b->Dp, Sp = b->Sp, S = rd.S;
-    const long long T = rd.T;
-    // (whole Philox blocks are never stored past T, but the 16-byte stores want the block's alignment and its size checked)
-    if (b->xstage_bytes < sizeof(int32_t) * (size_t)T) FAIL(ctx, VBX_ERR_STATE, "staging block too small for the labels");
-    std::vector<double> phi(Dp, 0.0), sphi(Dp, 0.0), gt;
-    if (d_fea) {
-        for (int d = 0; d < D; ++d) {
-            if (!(Phi[d] > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Phi[%d] must be positive", d);
-            phi[d] = Phi[d];
-            sphi[d] = std::sqrt(Phi[d]);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * Dp, phi.data(), sizeof(double) * Dp, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(b->d_sqrt_phi, sphi.data(), sizeof(double) * Dp, hipMemcpyHostToDevice, ctx->stream));
-        {
-            LaunchScope ls(b, VBX_K_PREP);
-            hipLaunchKernelGGL((prep_kernel<R, double>), dim3(rd.ntiles), dim3(256), 0, ctx->stream, d_fea, (const double*)b->d_sqrt_phi,
-                               (R*)b->d_rho + rd.row0 * Dp, b->d_gtile + rd.tile0, rd.T, D, Dp);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        gt.resize(rd.ntiles);
-        HIPCHK(ctx, hipMemcpyAsync(gt.data(), b->d_gtile + rd.tile0, sizeof(double) * rd.ntiles, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    hipLaunchKernelGGL(vbx::random_labels_kernel, dim3((unsigned)(((T + 3) / 4 + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (int*)b->d_xstage, T, (unsigned long long)seed, (unsigned long long)name_hash, (unsigned long long)restart,
-                       (unsigned long long)S);
-    hipLaunchKernelGGL((vbx::qinit_kernel<R>), dim3((unsigned)((T * Sp + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const int*)b->d_xstage, (R*)b->d_gamma + rd.row0 * Sp, T, S, Sp, hi, lo);
-    HIPCHK(ctx, hipGetLastError());
-    std::vector<double> pip(Sp, 0.0);
-    for (int s = 0; s < S; ++s) pip[s] = 1.0 / S;
-    HIPCHK(ctx, hipMemcpyAsync(b->d_pi + (size_t)rec * Sp, pip.data(), sizeof(double) * Sp, hipMemcpyHostToDevice, ctx->stream));
-    rd.has_model = 0;
-    RecState st;
-    std::memset(&st, 0, sizeof st);
-    HIPCHK(ctx, hipMemcpyAsync(b->d_state + rec, &st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->d_state + b->n_rec + rec, &st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(b->d_tile_done + rd.tile0, 0, sizeof(int) * rd.ntiles, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    if (d_fea) {
-        double gsum = 0.0;
-        for (double g : gt) gsum += g;
-        rd.gsum = gsum;
-    }
-    if (!b->gsum_pending.empty()) b->gsum_pending[rec] = 0;
-    if (b->h_args) {                                          // (nothing of an earlier upload of this recording may follow)
-        const size_t per = (size_t)2 * Dp + Sp + 2;
-        b->h_args[(size_t)rec * per + per - 2] = b->h_args[(size_t)rec * per + per - 1] = 0.0;
-    }
-    b->mirrors_valid = false;
-    return VBX_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-// recording `rec` from random labels.  src < 0: on its own rho built from the resident rows of xv (leaf_set_recording_resident
-// with the labels drawn on the device).  src >= 0, from == nullptr: on the rho of recording `src` of this batch
-// (leaf_set_recording_shared: the restarts of one recording around one rho).  src >= 0, from != nullptr: on a copy of the rho
-// of recording `src` of `from`, another sub-batch of the stream group (leaf_set_recording_cloned).  Written without the pinned
-// argument block of the host setters, so the owner may have been set by any of the setters.
-static int leaf_set_recording_random(vbx_batch* b, int rec, const vbx_xvectors* xv, int64_t row0, int src, vbx_batch* from,
-                                     uint64_t seed, uint64_t name_hash, int64_t restart, double init_smoothing, const double* Phi,
-                                     double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = b->ctx;
-    const char* fn = "vbx_batch_set_recording_random";
-    if (rec < 0 || rec >= b->n_rec) FAIL(ctx, VBX_ERR_INVALID, "%s: recording index %d out of range", fn, rec);
-    if (restart < 0) FAIL(ctx, VBX_ERR_INVALID, "%s: restart %lld is negative", fn, (long long)restart);
-    if (!(loopProb >= 0.0 && loopProb <= 1.0)) FAIL(ctx, VBX_ERR_INVALID, "loopProb=%g outside [0,1]", loopProb);
-    if (!(Fa > 0.0) || !(Fb > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Fa and Fb must be positive");
-    RecDesc& rd = b->recs[rec];
-    const double* d_fea = nullptr;
-    if (src < 0) {
-        if (!xv || !Phi) FAIL(ctx, VBX_ERR_INVALID, "%s: NULL input", fn);
-        d_fea = xvectors_fea_rows(xv, row0, rd.T, b->D, ctx->device);
-        if (!d_fea) FAIL(ctx, VBX_ERR_INVALID, "rows [%lld, +%d) x %d dims are not in the resident x-vectors", (long long)row0, rd.T, b->D);
-    } else {
-        vbx_batch* sb = from ? from : b;
-        if (src >= sb->n_rec || (!from && src == rec)) FAIL(ctx, VBX_ERR_INVALID, "%s: recording %d / source %d out of range", fn, rec, src);
-        if (!sb->is_set[src]) FAIL(ctx, VBX_ERR_STATE, "recording %d (the source of the x-vectors) has not been set", src);
-        if (sb->recs[src].T != rd.T) FAIL(ctx, VBX_ERR_INVALID, "recording %d has %d frames, its source %d has %d", rec, rd.T, src, sb->recs[src].T);
-        if (!from && b->share_src[src] == rec)
-            FAIL(ctx, VBX_ERR_STATE, "recording %d reads the x-vectors of recording %d: it cannot be that recording's source", src, rec);
-        if (from && (from->precision != b->precision || from->Dp != b->Dp || from->rsize != b->rsize))
-            FAIL(ctx, VBX_ERR_STATE, "sub-batches of one group differ in layout");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (src >= 0) {                                            // the source's rows, Phi and sum G must be complete (an asynchronous upload)
-        vbx_batch* sb = from ? from : b;
-        if (int rc = sync_uploads(sb); rc != VBX_OK) {
-            if (from) ctx->err = from->ctx->err;
-            return rc;
-        }
-    }
-    rd.lp = loopProb;
-    rd.Fa = Fa;
-    rd.Fb = Fb;
-    own_rho(b, rec);
-    if (src >= 0 && !from) {
-        const int owner = b->share_src[src];                  // a source that shares itself: its owner
-        rd.rho_row0 = b->recs[owner].row0;
-        rd.rho_tile0 = b->recs[owner].tile0;
-        rd.rho_rec = owner;
-        b->share_src[rec] = owner;
-        b->order_dirty = true;
-        // (the rows of rho this recording leaves unused must hold finite values: leaf_set_recording_shared)
-        HIPCHK(ctx, hipMemsetAsync((char*)b->d_rho + (size_t)rd.row0 * b->Dp * b->rsize, 0,
-                                   (size_t)std::min(rd.T, kTileFrames) * b->Dp * b->rsize, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * b->Dp, b->d_phi + (size_t)owner * b->Dp, sizeof(double) * b->Dp, hipMemcpyDeviceToDevice, ctx->stream));
-        rd.gsum = b->recs[owner].gsum;
-    } else if (src >= 0) {
-        const RecDesc& sd = from->recs[from->share_src[src]];  // the rows `src` reads
-        HIPCHK(ctx, hipMemcpyAsync((char*)b->d_rho + (size_t)rd.row0 * b->Dp * b->rsize, (const char*)from->d_rho + (size_t)sd.row0 * b->Dp * b->rsize,
-                                   (size_t)rd.T * b->Dp * b->rsize, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * b->Dp, from->d_phi + (size_t)src * b->Dp, sizeof(double) * b->Dp, hipMemcpyDeviceToDevice, ctx->stream));
-        rd.gsum = from->recs[src].gsum;
-    }
-    // softmax(smoothing * onehot) row (vbhmm.py:152), as leaf_set_recording_resident
-    const double z = std::exp(-init_smoothing), den = 1.0 + (rd.S - 1) * z;
-    const double hi = 1.0 / den, lo = z / den;
-    int rc = with_precision(b->precision, [&](auto r) {
-        return set_recording_random_impl<decltype(r)>(b, rec, d_fea, Phi, seed, name_hash, (uint64_t)restart, hi, lo);
-    });
-    if (rc != VBX_OK) return rc;
-    b->is_set[rec] = 1;
-    b->recs_dirty = true;
-    b->mpart_valid = false;
-    return VBX_OK;
-}
-
-
-int vbx_batch_set_recording_random(vbx_batch* b, int rec, const vbx_xvectors* xv, int64_t row0, int src_rec, uint64_t seed,
-                                   uint64_t name_hash, int64_t restart, double init_smoothing, const double* Phi, double loopProb,
-                                   double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    if (src_rec < 0) src_rec = -1;
-    if (b->kids.empty())
-        return leaf_set_recording_random(b, rec, xv, row0, src_rec, nullptr, seed, name_hash, restart, init_smoothing, Phi, loopProb, Fa, Fb);
-    if (rec < 0 || rec >= b->n_rec || src_rec >= b->n_rec)
-        FAIL(b->ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_random: recording index out of range");
-    const int k = b->kid_of[rec];
-    if (src_rec < 0) {                                        // x-vectors of its own: vbx_batch_set_recording_resident
-        b->any_set = true;
-        group_new_rows(b, rec, true);
-        return kid_fail(b, k, leaf_set_recording_random(b->kids[k], b->local_of[rec], xv, row0, -1, nullptr, seed, name_hash, restart,
-                                                        init_smoothing, Phi, loopProb, Fa, Fb));
-    }
-    // another recording's: vbx_batch_set_recording_shared -- sharing proper inside a sub-batch, one copy of the rows per sub-batch
-    if (rec == src_rec) FAIL(b->ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_random: a recording cannot share with itself");
-    const int ks = b->kid_of[src_rec];
-    const int root = b->root_of[src_rec];
-    if (root == rec) FAIL(b->ctx, VBX_ERR_STATE, "recording %d runs on the x-vectors of recording %d: it cannot be that recording's source", src_rec, rec);
-    group_new_rows(b, rec, false);
-    b->any_set = true;
-    int local_src = -1;
-    vbx_batch* from = nullptr;
-    if (ks == k) {
-        local_src = b->local_of[src_rec];
-    } else {
-        for (int i = 0; i < b->n_rec && local_src < 0; ++i)   // a recording of sub-batch k that already holds these x-vectors
-            if (i != rec && b->kid_of[i] == k && b->root_of[i] == root && b->kids[k]->is_set[b->local_of[i]] &&
-                b->kids[k]->share_src[b->local_of[i]] != b->local_of[rec])
-                local_src = b->local_of[i];
-        if (local_src < 0) {
-            from = b->kids[ks];
-            local_src = b->local_of[src_rec];
-        }
-    }
-    const int rc = leaf_set_recording_random(b->kids[k], b->local_of[rec], nullptr, 0, local_src, from, seed, name_hash, restart,
-                                             init_smoothing, nullptr, loopProb, Fa, Fb);
-    if (rc == VBX_OK) b->root_of[rec] = root;
-    return kid_fail(b, k, rc);
-}
-
 int vbx_xvectors_get(vbx_xvectors* xv, int which, int64_t row0, int64_t nrows, double* out) {
     if (!xv || !out || row0 < 0 || nrows < 0 || row0 + nrows > xv->n || (which != 0 && which != 1)) return VBX_ERR_INVALID;
     vbx_ctx* ctx = xv->ctx;

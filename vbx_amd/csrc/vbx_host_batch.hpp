@@ -334,161 +334,6 @@ static int sync_uploads(vbx_batch* b) {
 extern "C++" {
 namespace {
 template <typename R>
-int set_recording_impl(vbx_batch* b, int rec, const void* X, int x_dtype, const double* Phi, const double* pi0,
-                       const void* gamma0, int g_dtype, const double* alpha0, const double* invL0) {
-    vbx_ctx* ctx = b->ctx;
-    RecDesc& rd = b->recs[rec];
-    const int D = b->D, Dp = b->Dp, Sp = b->Sp, S = rd.S;
-    const long long T = rd.T;
-    if (int rc = ensure_host_args(b); rc != VBX_OK) return rc;
-    // (the pinned slot of this recording may still be the source of a copy in flight: the same recording set twice in a row)
-    if (b->args_busy[rec])
-        if (int rc = sync_uploads(b); rc != VBX_OK) return rc;
-    const size_t per = (size_t)2 * Dp + Sp + 2;
-    double* const phi = b->h_args + (size_t)rec * per;
-    double* const sphi = phi + Dp;
-    double* const pip = phi + 2 * Dp;
-    double* const flags = phi + 2 * Dp + Sp;                  // what sync_uploads' scatter_args_kernel takes from this slot
-    bool must_sync = !b->async_upload;
-    if (X) {
-        for (int d = 0; d < Dp; ++d) phi[d] = sphi[d] = 0.0;     // (padded dims: 0)
-        for (int d = 0; d < D; ++d) {
-            if (!(Phi[d] > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Phi[%d] must be positive", d);
-            phi[d] = Phi[d];
-            sphi[d] = std::sqrt(Phi[d]);
-        }
-        flags[0] = 1.0;                                       // (Phi goes to the device with the scatter of sync_uploads)
-        // X -> staging -> rho, G; prep_kernel reads sqrt(Phi) from the pinned slot itself
-        const size_t xbytes = (size_t)T * D * (x_dtype == VBX_F64 ? 8 : 4);
-        HIPCHK(ctx, hipMemcpyAsync(b->d_xstage, X, xbytes, hipMemcpyHostToDevice, ctx->stream));
-        if (x_dtype == VBX_F64) launch_prep<R, double>(b, rd, sphi); else launch_prep<R, float>(b, rd, sphi);
-        HIPCHK(ctx, hipGetLastError());
-        b->gsum_pending[rec] = 1;
-    } else {
-        // shared rho: Phi (and with it sum_t G_t) of the recording this one shares its x-vectors with
-        // (src == rec: a clone from another stream group's arena, leaf_set_recording_cloned has put Phi, rho and sum G in place)
-        const int src = b->share_src[rec];
-        flags[0] = 0.0;
-        if (src != rec) {
-            const double* sphi_src = b->h_args + (size_t)src * per;
-            if (sphi_src[per - 2] != 0.0) {                   // (the source's Phi is itself still on its way: take it from its slot)
-                std::memcpy(phi, sphi_src, sizeof(double) * 2 * Dp);
-                flags[0] = 1.0;
-            } else {
-                HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * Dp, b->d_phi + (size_t)src * Dp, sizeof(double) * Dp, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-        }
-        if (src != rec) rd.gsum = b->recs[src].gsum;              // (if the source's is still on its way: sync_uploads copies it again)
-        b->gsum_pending[rec] = 0;
-    }
-    // gamma0 (padded speakers: 0): the rows as the caller holds them -> staging (free again: prep_kernel is ahead in the
-    // stream) -> padded and converted on the device
-    std::vector<R> gp;
-    const size_t gbytes = (size_t)T * S * (g_dtype == VBX_F64 ? 8 : 4);
-    if (gbytes <= b->xstage_bytes) {
-        HIPCHK(ctx, hipMemcpyAsync(b->d_xstage, gamma0, gbytes, hipMemcpyHostToDevice, ctx->stream));
-        const unsigned blocks = (unsigned)(((size_t)T * Sp + 255) / 256);
-        if (g_dtype == VBX_F64)
-            hipLaunchKernelGGL((vbx::pad_gamma_kernel<R, double>), dim3(blocks), dim3(256), 0, ctx->stream, (const double*)b->d_xstage,
-                               (R*)b->d_gamma + rd.row0 * Sp, T, S, Sp);
-        else
-            hipLaunchKernelGGL((vbx::pad_gamma_kernel<R, float>), dim3(blocks), dim3(256), 0, ctx->stream, (const float*)b->d_xstage,
-                               (R*)b->d_gamma + rd.row0 * Sp, T, S, Sp);
-        HIPCHK(ctx, hipGetLastError());
-    } else {                                                   // (more speakers than feature dims: the staging block is too small)
-        if (g_dtype == VBX_F64) pack_matrix<R, double>(gp, (const double*)gamma0, T, S, Sp, (R)0);
-        else pack_matrix<R, float>(gp, (const float*)gamma0, T, S, Sp, (R)0);
-        HIPCHK(ctx, hipMemcpyAsync((R*)b->d_gamma + rd.row0 * Sp, gp.data(), sizeof(R) * gp.size(), hipMemcpyHostToDevice, ctx->stream));
-        must_sync = true;
-    }
-    for (int s = 0; s < Sp; ++s) pip[s] = s < S ? pi0[s] : 0.0;
-    flags[1] = 1.0;
-    std::vector<R> ap, ip;
-    rd.has_model = (alpha0 && invL0) ? 1 : 0;
-    if (rd.has_model) {
-        ap.assign((size_t)Sp * Dp, (R)0);
-        ip.assign((size_t)Sp * Dp, (R)1);
-        for (int s = 0; s < S; ++s)
-            for (int d = 0; d < D; ++d) {
-                ap[(size_t)s * Dp + d] = (R)alpha0[(size_t)s * D + d];
-                ip[(size_t)s * Dp + d] = (R)invL0[(size_t)s * D + d];
-            }
-        HIPCHK(ctx, hipMemcpyAsync((R*)b->d_alpha + (size_t)rec * Sp * Dp, ap.data(), sizeof(R) * ap.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync((R*)b->d_invL + (size_t)rec * Sp * Dp, ip.data(), sizeof(R) * ip.size(), hipMemcpyHostToDevice, ctx->stream));
-        must_sync = true;
-    }
-    if (b->has_run) {                                         // (a fresh batch: leaf_create has zeroed the states and the flags)
-        HIPCHK(ctx, hipMemsetAsync(b->d_state + rec, 0, sizeof(RecState), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(b->d_state + b->n_rec + rec, 0, sizeof(RecState), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(b->d_tile_done + rd.tile0, 0, sizeof(int) * rd.ntiles, ctx->stream));
-    }
-    b->args_busy[rec] = 1;
-    b->uploads_in_flight = true;
-    b->mirrors_valid = false;
-    if (must_sync) return sync_uploads(b);                     // (host vectors go out of scope below)
-    return VBX_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-extern "C++" {
-namespace {
-// recording `rec` from rows already in HBM: fea [T][D] f64 (vbx_xvectors) and the AHC labels; the initial
-// responsibilities are built on the device (vbhmm.py:150-152), pi0 = 1/S (VBx.py:76: pi given as an int)
-template <typename R>
-int set_recording_resident_impl(vbx_batch* b, int rec, const double* d_fea, const int32_t* labels, double hi, double lo,
-                                const double* Phi) {
-    vbx_ctx* ctx = b->ctx;
-    RecDesc& rd = b->recs[rec];
-    const int D = b->D, Dp = b->Dp, Sp = b->Sp, S = rd.S;
-    const long long T = rd.T;
-    std::vector<double> phi(Dp, 0.0), sphi(Dp, 0.0);
-    for (int d = 0; d < D; ++d) {
-        if (!(Phi[d] > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Phi[%d] must be positive", d);
-        phi[d] = Phi[d];
-        sphi[d] = std::sqrt(Phi[d]);
-    }
-    for (long long t = 0; t < T; ++t)
-        if (labels[t] < 0 || labels[t] >= S) FAIL(ctx, VBX_ERR_INVALID, "label %d of frame %lld outside [0, %d)", labels[t], t, S);
-    HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * Dp, phi.data(), sizeof(double) * Dp, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->d_sqrt_phi, sphi.data(), sizeof(double) * Dp, hipMemcpyHostToDevice, ctx->stream));
-    {
-        LaunchScope ls(b, VBX_K_PREP);
-        hipLaunchKernelGGL((prep_kernel<R, double>), dim3(rd.ntiles), dim3(256), 0, ctx->stream, d_fea, (const double*)b->d_sqrt_phi,
-                           (R*)b->d_rho + rd.row0 * Dp, b->d_gtile + rd.tile0, rd.T, D, Dp);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    std::vector<double> gt(rd.ntiles);
-    HIPCHK(ctx, hipMemcpyAsync(gt.data(), b->d_gtile + rd.tile0, sizeof(double) * rd.ntiles, hipMemcpyDeviceToHost, ctx->stream));
-    // labels -> staging (the x staging block is free: fea is already on the device) -> gamma
-    if (b->xstage_bytes < sizeof(int32_t) * (size_t)T) FAIL(ctx, VBX_ERR_STATE, "staging block too small for the labels");
-    HIPCHK(ctx, hipMemcpyAsync(b->d_xstage, labels, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL((vbx::qinit_kernel<R>), dim3((unsigned)((T * Sp + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const int*)b->d_xstage, (R*)b->d_gamma + rd.row0 * Sp, T, S, Sp, hi, lo);
-    std::vector<double> pip(Sp, 0.0);
-    for (int s = 0; s < S; ++s) pip[s] = 1.0 / S;
-    HIPCHK(ctx, hipMemcpyAsync(b->d_pi + (size_t)rec * Sp, pip.data(), sizeof(double) * Sp, hipMemcpyHostToDevice, ctx->stream));
-    rd.has_model = 0;
-    RecState st;
-    std::memset(&st, 0, sizeof st);
-    HIPCHK(ctx, hipMemcpyAsync(b->d_state + rec, &st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->d_state + b->n_rec + rec, &st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(b->d_tile_done + rd.tile0, 0, sizeof(int) * rd.ntiles, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    double gsum = 0.0;
-    for (double g : gt) gsum += g;
-    rd.gsum = gsum;
-    if (!b->gsum_pending.empty()) b->gsum_pending[rec] = 0;
-    if (b->h_args) {                                          // (nothing of an earlier upload of this recording may follow)
-        const size_t per = (size_t)2 * Dp + Sp + 2;
-        b->h_args[(size_t)rec * per + per - 2] = b->h_args[(size_t)rec * per + per - 1] = 0.0;
-    }
-    b->mirrors_valid = false;
-    return VBX_OK;
-}
-
-template <typename R>
 int get_labels_impl(vbx_batch* b, int rec, int32_t* first, int32_t* second) {
     vbx_ctx* ctx = b->ctx;
     const RecDesc& rd = b->recs[rec];
@@ -509,173 +354,11 @@ int get_labels_impl(vbx_batch* b, int rec, int32_t* first, int32_t* second) {
 }  // namespace
 }  // extern "C++"
 
-struct vbx_xvectors;
-static void own_rho(vbx_batch* b, int rec);
-static const double* xvectors_fea_rows(const vbx_xvectors* xv, int64_t row0, int64_t T, int D, int device);
-
-static int leaf_set_recording_resident(vbx_batch* b, int rec, const vbx_xvectors* xv, int64_t row0, const int32_t* labels,
-                                       double init_smoothing, const double* Phi, double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = b->ctx;
-    if (rec < 0 || rec >= b->n_rec) FAIL(ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
-    if (!xv || !labels || !Phi) FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_resident: NULL input");
-    if (!(loopProb >= 0.0 && loopProb <= 1.0)) FAIL(ctx, VBX_ERR_INVALID, "loopProb=%g outside [0,1]", loopProb);
-    if (!(Fa > 0.0) || !(Fb > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Fa and Fb must be positive");
-    RecDesc& rd = b->recs[rec];
-    const double* d_fea = xvectors_fea_rows(xv, row0, rd.T, b->D, ctx->device);
-    if (!d_fea) FAIL(ctx, VBX_ERR_INVALID, "rows [%lld, +%d) x %d dims are not in the resident x-vectors", (long long)row0, rd.T, b->D);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    rd.lp = loopProb;
-    rd.Fa = Fa;
-    rd.Fb = Fb;
-    own_rho(b, rec);
-    // softmax(smoothing * onehot) row (vbhmm.py:152, scipy.special.softmax: exp(x - max) / sum)
-    const double z = std::exp(-init_smoothing), den = 1.0 + (rd.S - 1) * z;
-    const double hi = 1.0 / den, lo = z / den;
-    int rc = with_precision(b->precision, [&](auto r) { return set_recording_resident_impl<decltype(r)>(b, rec, d_fea, labels, hi, lo, Phi); });
-    if (rc != VBX_OK) return rc;
-    b->is_set[rec] = 1;
-    b->recs_dirty = true;
-    b->mpart_valid = false;
-    return VBX_OK;
-}
-
 static int leaf_get_labels(vbx_batch* b, int rec, int32_t* first, int32_t* second) {
     if (!b) return VBX_ERR_INVALID;
     if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
     HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
     return with_precision(b->precision, [&](auto r) { return get_labels_impl<decltype(r)>(b, rec, first, second); });
-}
-
-// `rec` gets (back) a rho of its own: recordings that read its rows so far are unset, and it leaves the group it was in
-static void own_rho(vbx_batch* b, int rec) {
-    for (int i = 0; i < b->n_rec; ++i)
-        if (i != rec && b->share_src[i] == rec) {
-            b->share_src[i] = i;
-            b->recs[i].rho_row0 = b->recs[i].row0;
-            b->recs[i].rho_tile0 = b->recs[i].tile0;
-            b->recs[i].rho_rec = i;
-            b->is_set[i] = 0;
-            b->order_dirty = true;
-        }
-    if (b->share_src[rec] != rec) b->order_dirty = true;
-    b->share_src[rec] = rec;
-    b->recs[rec].rho_row0 = b->recs[rec].row0;
-    b->recs[rec].rho_tile0 = b->recs[rec].tile0;
-    b->recs[rec].rho_rec = rec;
-    b->split_dirty[rec] = 1;                                  // (every caller is about to give `rec` new x-vectors)
-}
-
-static int leaf_set_recording(vbx_batch* b, int rec, const void* X, int x_dtype, const double* Phi, const double* pi0,
-                            const void* gamma0, int g_dtype, const double* alpha0, const double* invL0,
-                            double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = b->ctx;
-    if (rec < 0 || rec >= b->n_rec) FAIL(ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
-    if (!X || !Phi || !pi0 || !gamma0) FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_recording: NULL input");
-    if ((x_dtype != VBX_F32 && x_dtype != VBX_F64) || (g_dtype != VBX_F32 && g_dtype != VBX_F64))
-        FAIL(ctx, VBX_ERR_INVALID, "bad element type");
-    if ((alpha0 == nullptr) != (invL0 == nullptr)) { alpha0 = nullptr; invL0 = nullptr; }   // VBx.py:94 needs both
-    if (!(loopProb >= 0.0 && loopProb <= 1.0)) FAIL(ctx, VBX_ERR_INVALID, "loopProb=%g outside [0,1]", loopProb);
-    if (!(Fa > 0.0) || !(Fb > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Fa and Fb must be positive");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    RecDesc& rd = b->recs[rec];
-    rd.lp = loopProb;
-    rd.Fa = Fa;
-    rd.Fb = Fb;
-    own_rho(b, rec);
-    int rc = with_precision(b->precision, [&](auto r) { return set_recording_impl<decltype(r)>(b, rec, X, x_dtype, Phi, pi0, gamma0, g_dtype, alpha0, invL0); });
-    if (rc != VBX_OK) return rc;
-    b->is_set[rec] = 1;
-    b->recs_dirty = true;
-    b->mpart_valid = false;
-    return VBX_OK;
-}
-
-// recording `rec` on the x-vectors (rho, Phi, sum G) of recording `src` of the same batch: an Fa / Fb / loopProb sweep
-// over one recording keeps one rho in HBM
-static int leaf_set_recording_shared(vbx_batch* b, int rec, int src, const double* pi0, const void* gamma0, int g_dtype,
-                                     const double* alpha0, const double* invL0, double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = b->ctx;
-    if (rec < 0 || rec >= b->n_rec || src < 0 || src >= b->n_rec || src == rec)
-        FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_shared: recording %d / source %d out of range", rec, src);
-    if (!pi0 || !gamma0) FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_shared: NULL input");
-    if (g_dtype != VBX_F32 && g_dtype != VBX_F64) FAIL(ctx, VBX_ERR_INVALID, "bad element type");
-    if (!b->is_set[src]) FAIL(ctx, VBX_ERR_STATE, "recording %d (the source of the x-vectors) has not been set", src);
-    if (b->recs[src].T != b->recs[rec].T)
-        FAIL(ctx, VBX_ERR_INVALID, "recording %d has %d frames, its source %d has %d", rec, b->recs[rec].T, src, b->recs[src].T);
-    if ((alpha0 == nullptr) != (invL0 == nullptr)) { alpha0 = nullptr; invL0 = nullptr; }
-    if (!(loopProb >= 0.0 && loopProb <= 1.0)) FAIL(ctx, VBX_ERR_INVALID, "loopProb=%g outside [0,1]", loopProb);
-    if (!(Fa > 0.0) || !(Fb > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Fa and Fb must be positive");
-    // (a source that reads the rows of `rec` itself would be unset by own_rho below and leave `rec` pointing at rows that
-    //  hold nothing: round-3 advisor finding)
-    if (b->share_src[src] == rec)
-        FAIL(ctx, VBX_ERR_STATE, "recording %d reads the x-vectors of recording %d: it cannot be that recording's source", src, rec);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    own_rho(b, rec);                                          // (whoever shared with `rec` must be set again)
-    const int owner = b->share_src[src];                      // a source that shares itself: its owner
-    RecDesc& rd = b->recs[rec];
-    rd.lp = loopProb;
-    rd.Fa = Fa;
-    rd.Fb = Fb;
-    rd.rho_row0 = b->recs[owner].row0;
-    rd.rho_tile0 = b->recs[owner].tile0;
-    rd.rho_rec = owner;
-    b->share_src[rec] = owner;
-    b->order_dirty = true;
-    // the rows of rho this recording leaves unused lie behind another recording's: the last chunk of that one reads a whole
-    // tile (finite values that meet gamma = 0, vbx_chunk_post.hpp), so they must not hold whatever the block held before
-    HIPCHK(ctx, hipMemsetAsync((char*)b->d_rho + (size_t)rd.row0 * b->Dp * b->rsize, 0,
-                               (size_t)std::min(rd.T, kTileFrames) * b->Dp * b->rsize, ctx->stream));
-    int rc = with_precision(b->precision, [&](auto r) { return set_recording_impl<decltype(r)>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0); });
-    if (rc != VBX_OK) return rc;
-    b->is_set[rec] = 1;
-    b->recs_dirty = true;
-    b->mpart_valid = false;
-    return VBX_OK;
-}
-
-// recording `rec` of batch `b` on a COPY of the x-vectors (rho, Phi, sum G) of recording `src` of batch `from` -- another
-// sub-batch of the same stream group, i.e. another device arena: a sweep over one recording that runs on several streams
-// keeps one rho per stream (288 GB of HBM: a copy of 100 MB buys a stream of its own), shared by the points of that stream
-static int leaf_set_recording_cloned(vbx_batch* b, int rec, vbx_batch* from, int src, const double* pi0, const void* gamma0,
-                                     int g_dtype, const double* alpha0, const double* invL0, double loopProb, double Fa, double Fb) {
-    if (!b || !from) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = b->ctx;
-    if (rec < 0 || rec >= b->n_rec || src < 0 || src >= from->n_rec)
-        FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_shared: recording %d / source %d out of range", rec, src);
-    if (!pi0 || !gamma0) FAIL(ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_shared: NULL input");
-    if (g_dtype != VBX_F32 && g_dtype != VBX_F64) FAIL(ctx, VBX_ERR_INVALID, "bad element type");
-    if (!from->is_set[src]) FAIL(ctx, VBX_ERR_STATE, "the source of the x-vectors has not been set");
-    if (from->recs[src].T != b->recs[rec].T)
-        FAIL(ctx, VBX_ERR_INVALID, "recording %d has %d frames, its source has %d", rec, b->recs[rec].T, from->recs[src].T);
-    if (from->precision != b->precision || from->Dp != b->Dp || from->rsize != b->rsize) FAIL(ctx, VBX_ERR_STATE, "sub-batches of one group differ in layout");
-    if ((alpha0 == nullptr) != (invL0 == nullptr)) { alpha0 = nullptr; invL0 = nullptr; }
-    if (!(loopProb >= 0.0 && loopProb <= 1.0)) FAIL(ctx, VBX_ERR_INVALID, "loopProb=%g outside [0,1]", loopProb);
-    if (!(Fa > 0.0) || !(Fb > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Fa and Fb must be positive");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // the source lives on another stream: its rows (and its sum G) must be complete before they are copied from
-    if (int rc = sync_uploads(from); rc != VBX_OK) {
-        ctx->err = from->ctx->err;
-        return rc;
-    }
-    const RecDesc& sd = from->recs[from->share_src[src]];     // the rows `src` reads
-    RecDesc& rd = b->recs[rec];
-    rd.lp = loopProb;
-    rd.Fa = Fa;
-    rd.Fb = Fb;
-    own_rho(b, rec);
-    HIPCHK(ctx, hipMemcpyAsync((char*)b->d_rho + (size_t)rd.row0 * b->Dp * b->rsize, (const char*)from->d_rho + (size_t)sd.row0 * b->Dp * b->rsize,
-                               (size_t)rd.T * b->Dp * b->rsize, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->d_phi + (size_t)rec * b->Dp, from->d_phi + (size_t)src * b->Dp, sizeof(double) * b->Dp, hipMemcpyDeviceToDevice, ctx->stream));
-    rd.gsum = from->recs[src].gsum;
-    int rc = with_precision(b->precision, [&](auto r) { return set_recording_impl<decltype(r)>(b, rec, nullptr, VBX_F64, nullptr, pi0, gamma0, g_dtype, alpha0, invL0); });
-    if (rc != VBX_OK) return rc;
-    b->is_set[rec] = 1;
-    b->recs_dirty = true;
-    b->mpart_valid = false;
-    return VBX_OK;
 }
 
 // VBX_OPT_GEMM = split: the f16 copies of rho (vbx_split.hpp) of every recording whose x-vectors have changed since they

@@ -168,8 +168,8 @@ static int group_build(vbx_batch* b, int K) {
 
 // `rec` is about to get other x-vectors than it has (new ones of its own: `own`; or another recording's): whoever runs on
 // a copy of its old rows in ANOTHER sub-batch must be set again (inside its own sub-batch own_rho does the same), and the
-// bookkeeping of who shares whose rows follows.  One helper for the three setters (round 6, the advisor's finding: the
-// resident setter used to skip this and left clones running on stale x-vectors).
+// bookkeeping of who shares whose rows follows.  One helper for every setter (vbx_host_set.hpp: set_own_rows,
+// group_route_source; a setter that skips this leaves clones running on stale x-vectors).
 static void group_new_rows(vbx_batch* b, int rec, bool own) {
     const int k = b->kid_of[rec];
     if (b->root_of[rec] == rec)
@@ -246,59 +246,6 @@ int vbx_batch_set_option(vbx_batch* b, int option, int64_t value) {
     return VBX_OK;
 }
 
-int vbx_batch_set_recording(vbx_batch* b, int rec, const void* X, int x_dtype, const double* Phi, const double* pi0,
-                            const void* gamma0, int g_dtype, const double* alpha0, const double* invL0,
-                            double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    if (b->kids.empty())
-        return leaf_set_recording(b, rec, X, x_dtype, Phi, pi0, gamma0, g_dtype, alpha0, invL0, loopProb, Fa, Fb);
-    if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
-    const int k = b->kid_of[rec];
-    {
-        // (recordings of DIFFERENT sub-batches may be set from different host threads -- each has its own stream and arena, and
-        //  a batch call uploads three times as fast that way, vbx_amd/batch.py -- so the bookkeeping they share is guarded)
-        std::lock_guard<std::mutex> lock(b->group_mutex);
-        b->any_set = true;
-        group_new_rows(b, rec, true);
-    }
-    return kid_fail(b, k, leaf_set_recording(b->kids[k], b->local_of[rec], X, x_dtype, Phi, pi0, gamma0, g_dtype, alpha0,
-                                             invL0, loopProb, Fa, Fb));
-}
-
-int vbx_batch_set_recording_shared(vbx_batch* b, int rec, int src_rec, const double* pi0, const void* gamma0, int g_dtype,
-                                   const double* alpha0, const double* invL0, double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    if (b->kids.empty())
-        return leaf_set_recording_shared(b, rec, src_rec, pi0, gamma0, g_dtype, alpha0, invL0, loopProb, Fa, Fb);
-    if (rec < 0 || rec >= b->n_rec || src_rec < 0 || src_rec >= b->n_rec)
-        FAIL(b->ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_shared: recording index out of range");
-    if (rec == src_rec) FAIL(b->ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_shared: a recording cannot share with itself");
-    // A stream group deals its recordings to sub-batches with a device arena each.  Sharing proper works inside one of them;
-    // across two, the first recording of a sub-batch that asks for these x-vectors gets a COPY of the rows (device to
-    // device) and owns it, the later ones of that sub-batch share with it: one rho per stream, not one per sweep point.
-    const int k = b->kid_of[rec], ks = b->kid_of[src_rec];
-    const int root = b->root_of[src_rec];
-    if (root == rec) FAIL(b->ctx, VBX_ERR_STATE, "recording %d runs on the x-vectors of recording %d: it cannot be that recording's source", src_rec, rec);
-    group_new_rows(b, rec, false);                            // (`rec` had x-vectors of its own: its dependants in other sub-batches)
-    b->any_set = true;
-    int rc;
-    if (ks == k) {
-        rc = leaf_set_recording_shared(b->kids[k], b->local_of[rec], b->local_of[src_rec], pi0, gamma0, g_dtype, alpha0, invL0, loopProb, Fa, Fb);
-    } else {
-        int local_src = -1;                                   // a recording of sub-batch k that already holds these x-vectors
-        for (int i = 0; i < b->n_rec && local_src < 0; ++i)
-            if (i != rec && b->kid_of[i] == k && b->root_of[i] == root && b->kids[k]->is_set[b->local_of[i]] &&
-                b->kids[k]->share_src[b->local_of[i]] != b->local_of[rec])        // (not one that reads `rec`'s own copy: `rec` is
-                local_src = b->local_of[i];                                       //  the clone owner being set again -> a fresh clone)
-        rc = local_src >= 0
-                 ? leaf_set_recording_shared(b->kids[k], b->local_of[rec], local_src, pi0, gamma0, g_dtype, alpha0, invL0, loopProb, Fa, Fb)
-                 : leaf_set_recording_cloned(b->kids[k], b->local_of[rec], b->kids[ks], b->local_of[src_rec], pi0, gamma0, g_dtype,
-                                             alpha0, invL0, loopProb, Fa, Fb);
-    }
-    if (rc == VBX_OK) b->root_of[rec] = root;
-    return kid_fail(b, k, rc);
-}
-
 int vbx_batch_run(vbx_batch* b, int max_iters, double epsilon) {
     if (!b) return VBX_ERR_INVALID;
     if (b->kids.empty()) return leaf_run(b, max_iters, epsilon);
@@ -309,7 +256,7 @@ int vbx_batch_run(vbx_batch* b, int max_iters, double epsilon) {
     // (the cache policy of the rho loads is a property of what iterates TOGETHER: every sub-batch gets the group's total, the
     //  x-vectors a sweep shares across sub-batches counted once -- VBX_OPT_STREAM_LOADS.  This is a rule, not a count of
     //  physical bytes: every sub-batch that runs points of a sweep holds a device clone of the shared rows
-    //  (leaf_set_recording_cloned), and the clones are deliberately NOT counted -- the nine-point sweep over T = 200 000 on three
+    //  (rho_clone, vbx_host_set.hpp), and the clones are deliberately NOT counted -- the nine-point sweep over T = 200 000 on three
     //  streams reads 3 x 102 MB of distinct rho lines, more than the 256 MiB, and is classed as 102 MB.  That case keeps the
     //  default policy because its rate is unchanged by construction; streaming loads were never measured on it)
     long long rho_bytes = 0;
@@ -456,18 +403,6 @@ int vbx_host_free(void* p) {
     hp.spare.emplace_back(p, bytes);
     hp.spare_bytes += bytes;
     return VBX_OK;
-}
-
-int vbx_batch_set_recording_resident(vbx_batch* b, int rec, const vbx_xvectors* xv, int64_t row0, const int32_t* labels,
-                                     double init_smoothing, const double* Phi, double loopProb, double Fa, double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    if (b->kids.empty()) return leaf_set_recording_resident(b, rec, xv, row0, labels, init_smoothing, Phi, loopProb, Fa, Fb);
-    if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "recording index %d out of range", rec);
-    b->any_set = true;
-    const int k = b->kid_of[rec];
-    group_new_rows(b, rec, true);
-    return kid_fail(b, k, leaf_set_recording_resident(b->kids[k], b->local_of[rec], xv, row0, labels, init_smoothing, Phi,
-                                                      loopProb, Fa, Fb));
 }
 
 int vbx_batch_get_labels(vbx_batch* b, int rec, int32_t* first, int32_t* second) {

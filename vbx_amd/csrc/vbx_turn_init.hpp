@@ -153,57 +153,6 @@ int padded_states(int S) {                                     // (leaf_create: 
     return sp;
 }
 
-// recording `rec` from speaker turns: rho, Phi and sum G from the resident rows as set_recording_resident_impl builds them, the
-// responsibilities by turn_init_kernel where qinit_kernel writes them.  Ends with a synchronize, like the resident setter.
-template <typename R>
-int set_recording_turns_impl(vbx_batch* b, int rec, const double* d_fea, const int64_t* seg_a, const int64_t* seg_b, int64_t N,
-                             const int64_t* turn_u, const int64_t* turn_v, const int32_t* turn_spk, double init_smoothing,
-                             const double* Phi) {
-    vbx_ctx* ctx = b->ctx;
-    RecDesc& rd = b->recs[rec];
-    const int D = b->D, Dp = b->Dp, Sp = b->Sp, S = rd.S;
-    std::vector<double> phi(Dp, 0.0), sphi(Dp, 0.0), gt(rd.ntiles), pip(Sp, 0.0);
-    for (int d = 0; d < D; ++d) {
-        if (!(Phi[d] > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Phi[%d] must be positive", d);
-        phi[d] = Phi[d];
-        sphi[d] = std::sqrt(Phi[d]);
-    }
-    for (int s = 0; s < S; ++s) pip[s] = 1.0 / S;
-    RecState st;
-    std::memset(&st, 0, sizeof st);
-    {
-        DeviceCall call(ctx);                                  // (declared after the host vectors its copies read and write)
-        call.enqueued(hipMemcpyAsync(b->d_phi + (size_t)rec * Dp, phi.data(), sizeof(double) * Dp, hipMemcpyHostToDevice, call.st));
-        call.enqueued(hipMemcpyAsync(b->d_sqrt_phi, sphi.data(), sizeof(double) * Dp, hipMemcpyHostToDevice, call.st));
-        if (call.ok()) {
-            LaunchScope ls(b, VBX_K_PREP);
-            hipLaunchKernelGGL((prep_kernel<R, double>), dim3(rd.ntiles), dim3(256), 0, call.st, d_fea, (const double*)b->d_sqrt_phi,
-                               (R*)b->d_rho + rd.row0 * Dp, b->d_gtile + rd.tile0, rd.T, D, Dp);
-        }
-        call.launched();
-        call.download(gt.data(), (const double*)(b->d_gtile + rd.tile0), (size_t)rd.ntiles);
-        launch_turn_init<R>(call, rd.T, seg_a, seg_b, N, turn_u, turn_v, turn_spk, S, Sp, init_smoothing, nullptr, nullptr,
-                            (R*)b->d_gamma + rd.row0 * Sp, Sp);
-        call.copy_in(b->d_pi + (size_t)rec * Sp, (const double*)pip.data(), (size_t)Sp);
-        call.copy_in(b->d_state + rec, (const RecState*)&st, 1);
-        call.copy_in(b->d_state + b->n_rec + rec, (const RecState*)&st, 1);
-        if (call.ok()) call.enqueued(hipMemsetAsync(b->d_tile_done + rd.tile0, 0, sizeof(int) * rd.ntiles, call.st));
-        call.sync();
-        if (int rc = call.finish("vbx_batch_set_recording_turns failed"); rc != VBX_OK) return rc;
-    }
-    rd.has_model = 0;
-    double gsum = 0.0;
-    for (double g : gt) gsum += g;
-    rd.gsum = gsum;
-    if (!b->gsum_pending.empty()) b->gsum_pending[rec] = 0;
-    if (b->h_args) {                                          // (nothing of an earlier upload of this recording may follow)
-        const size_t per = (size_t)2 * Dp + Sp + 2;
-        b->h_args[(size_t)rec * per + per - 2] = b->h_args[(size_t)rec * per + per - 1] = 0.0;
-    }
-    b->mirrors_valid = false;
-    return VBX_OK;
-}
-
 }  // namespace
 }  // extern "C++"
 
@@ -230,51 +179,6 @@ int vbx_turn_weights(vbx_ctx* ctx, int64_t T, const int64_t* seg_a, const int64_
     if (q_host) call.download(q_host, (const double*)d_q, (size_t)T * S);
     call.sync();
     return call.finish("vbx_turn_weights failed");
-}
-
-static int leaf_set_recording_turns(vbx_batch* b, int rec, const vbx_xvectors* xv, int64_t row0, const int64_t* seg_a,
-                                    const int64_t* seg_b, int64_t N, const int64_t* turn_u, const int64_t* turn_v,
-                                    const int32_t* turn_spk, double init_smoothing, const double* Phi, double loopProb, double Fa,
-                                    double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    vbx_ctx* ctx = b->ctx;
-    const char* fn = "vbx_batch_set_recording_turns";
-    if (rec < 0 || rec >= b->n_rec) FAIL(ctx, VBX_ERR_INVALID, "%s: recording index %d out of range", fn, rec);
-    if (!xv || !Phi) FAIL(ctx, VBX_ERR_INVALID, "%s: NULL input", fn);
-    if (!(loopProb >= 0.0 && loopProb <= 1.0)) FAIL(ctx, VBX_ERR_INVALID, "loopProb=%g outside [0,1]", loopProb);
-    if (!(Fa > 0.0) || !(Fb > 0.0)) FAIL(ctx, VBX_ERR_INVALID, "Fa and Fb must be positive");
-    RecDesc& rd = b->recs[rec];
-    if (!turn_input_ok(ctx->err, fn, rd.T, seg_a, seg_b, N, turn_u, turn_v, turn_spk, rd.S)) return VBX_ERR_INVALID;
-    const double* d_fea = xvectors_fea_rows(xv, row0, rd.T, b->D, ctx->device);
-    if (!d_fea) FAIL(ctx, VBX_ERR_INVALID, "rows [%lld, +%d) x %d dims are not in the resident x-vectors", (long long)row0, rd.T, b->D);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    rd.lp = loopProb;
-    rd.Fa = Fa;
-    rd.Fb = Fb;
-    own_rho(b, rec);
-    int rc = with_precision(b->precision, [&](auto r) {
-        return set_recording_turns_impl<decltype(r)>(b, rec, d_fea, seg_a, seg_b, N, turn_u, turn_v, turn_spk, init_smoothing, Phi);
-    });
-    if (rc != VBX_OK) return rc;
-    b->is_set[rec] = 1;
-    b->recs_dirty = true;
-    b->mpart_valid = false;
-    return VBX_OK;
-}
-
-int vbx_batch_set_recording_turns(vbx_batch* b, int rec, const vbx_xvectors* xv, int64_t row0, const int64_t* seg_a,
-                                  const int64_t* seg_b, int64_t N, const int64_t* turn_u, const int64_t* turn_v,
-                                  const int32_t* turn_spk, double init_smoothing, const double* Phi, double loopProb, double Fa,
-                                  double Fb) {
-    if (!b) return VBX_ERR_INVALID;
-    if (b->kids.empty())
-        return leaf_set_recording_turns(b, rec, xv, row0, seg_a, seg_b, N, turn_u, turn_v, turn_spk, init_smoothing, Phi, loopProb, Fa, Fb);
-    if (rec < 0 || rec >= b->n_rec) FAIL(b->ctx, VBX_ERR_INVALID, "vbx_batch_set_recording_turns: recording index %d out of range", rec);
-    b->any_set = true;
-    const int k = b->kid_of[rec];
-    group_new_rows(b, rec, true);
-    return kid_fail(b, k, leaf_set_recording_turns(b->kids[k], b->local_of[rec], xv, row0, seg_a, seg_b, N, turn_u, turn_v, turn_spk,
-                                                   init_smoothing, Phi, loopProb, Fa, Fb));
 }
 
 }  // extern "C"
