@@ -235,7 +235,7 @@ def test_restarts_and_seed_without_random_n_are_refused_by_the_library_call():
     recordings, segs = _archive(['recA'])
     args = argparse.Namespace(init='AHC+VB', random_restarts=2, seed=None, threshold=0.0, lda_dim=4, Fa=0.3, Fb=17.0, loopP=0.9,
                               init_smoothing=5.0, output_2nd=False, out_rttm_dir=None)
-    with pytest.raises(ValueError, match='random_N'):
+    with pytest.raises(ValueError, match='--random-restarts needs --init random_<N>'):
         vbhmm.diarize_recordings(recordings, segs, dict(plda_psi=np.ones(4)), args, _Stages(), log=lambda *a: None)
 
 

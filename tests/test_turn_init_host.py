@@ -293,7 +293,7 @@ def test_the_library_call_refuses_the_directory_with_another_init(tmp_path):
     recordings, segs, first = _archive(tmp_path, ('recA',))
     args = argparse.Namespace(init='AHC+VB', init_rttm_dir=first, threshold=0.0, lda_dim=4, Fa=0.3, Fb=17.0, loopP=0.9,
                               init_smoothing=5.0, output_2nd=False, out_rttm_dir=None)
-    with pytest.raises(ValueError, match='init_rttm_dir'):
+    with pytest.raises(ValueError, match='--init-rttm-dir needs --init RTTM or RTTM\\+VB'):
         vbhmm.diarize_recordings(recordings, segs, dict(plda_psi=np.ones(4)), args, _Stages(), log=lambda *a: None)
 
 

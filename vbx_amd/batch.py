@@ -115,7 +115,7 @@ def _shape_of(rec, defaults):
     return int(T), int(S), (kw.get('alphaQInit', 1.0) if kw.get('gamma') is None else None)
 
 
-def _padded_states(n_states):
+def padded_states(n_states):
     """The padded state count a vbx_batch of this many speakers runs with (vbx_host_batch.hpp: powers of two from 16)."""
     sp = 16
     while sp < n_states:
@@ -194,7 +194,7 @@ def run_shard_hip(items, maxIters, epsilon, precision=None, device=None):
     results = [None] * len(items)
     by_dim = {}
     for k, it in enumerate(items):
-        by_dim.setdefault((it['X'].shape[1], _padded_states(len(it['pi']))), []).append(k)
+        by_dim.setdefault((it['X'].shape[1], padded_states(len(it['pi']))), []).append(k)
     for (D, _sp), idx in by_dim.items():
         prec = {_pick_precision(precision, items[k]['X']) for k in idx}
         prec = 'fp64' if 'fp64' in prec else prec.pop()

@@ -49,6 +49,7 @@ import time
 import numpy as np
 
 from . import score
+from .start import ahc_options_ignored, from_args
 from .kaldi_formats import read_xvector_timing_dict
 
 __all__ = ['main', 'tune', 'tune_recordings', 'grid_points', 'best_point', 'format_table', 'build_parser']
@@ -98,27 +99,9 @@ def check_one_rank(world=None):
 
 def check_init(args):
     """(N or None, restarts, seed) of ``args.init`` (default ``'AHC+VB'``), ``args.random_restarts`` and ``args.seed``, or
-    ValueError: the grid is one of VB-HMM parameters, so ``AHC`` alone and ``RTTM`` alone are refused; restarts and seed need
-    ``random_<N>``; ``args.init_rttm_dir`` and ``RTTM+VB`` need each other."""
-    from .vbhmm import random_init_states, turn_init
-    init = getattr(args, 'init', 'AHC+VB')
-    n_random = random_init_states(init)
-    restarts, seed = getattr(args, 'random_restarts', None), getattr(args, 'seed', None)
-    if init == 'AHC':
-        raise ValueError('--init AHC runs no VB-HMM: Fa, Fb and loopP change nothing; use AHC+VB or random_<N>')
-    if init == 'RTTM':
-        raise ValueError('--init RTTM runs no VB-HMM: Fa, Fb and loopP change nothing; use RTTM+VB')
-    rttm_dir = getattr(args, 'init_rttm_dir', None)
-    if turn_init(init) and rttm_dir is None:
-        raise ValueError(f'--init {init} needs --init-rttm-dir: the diarization to start from')
-    if not turn_init(init) and rttm_dir is not None:
-        raise ValueError(f'--init-rttm-dir needs --init RTTM+VB: --init {init} reads no diarization')
-    if n_random is None and (restarts is not None or seed is not None):
-        raise ValueError(f'--random-restarts and --seed need --init random_<N>: --init {init} draws nothing')
-    restarts, seed = (1 if restarts is None else int(restarts)), (0 if seed is None else int(seed))
-    if restarts < 1 or not 0 <= seed < 1 << 64:
-        raise ValueError(f'--random-restarts {restarts} must be >= 1 and --seed {seed} in 0 .. 2^64 - 1')
-    return n_random, restarts, seed
+    ValueError (``start.check_options``): the grid is one of VB-HMM parameters, so ``AHC`` alone and ``RTTM`` alone are refused."""
+    start = from_args(args, need_vb=True)
+    return start.n_random, start.restarts, start.seed
 
 
 def read_reference(ref_rttm_dir, names):
@@ -152,7 +135,7 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
     ``step``."""
     from concurrent.futures import ThreadPoolExecutor
     from ._capi import MAX_SPEAKERS
-    from .vbhmm import DeviceStages, _ahc_kw, tune_host_process, turn_init
+    from .vbhmm import DeviceStages, _ahc_kw, driver_threads, tune_host_process
     criterion, step = check_criterion(getattr(args, 'criterion', 'der'), getattr(args, 'step', None))
     extended = criterion != 'der' or step is not None
     grid = [tuple(float(v) for v in g) for g in grid]
@@ -165,16 +148,15 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
     if missing:
         raise ValueError('no reference turns for: ' + ', '.join(missing))
     ahc_kw = _ahc_kw(args, ahc_scores)
-    n_random, restarts, seed = check_init(args)
-    given = None                                                     # --init RTTM+VB: [((a, b), (u, v, spk, S))] in ticks
-    if turn_init(getattr(args, 'init', 'AHC+VB')):
-        from .turn_init import read_init_turns, window_ticks
-        given = []
-        for name in names:
-            u, v, spk, speakers = read_init_turns(args.init_rttm_dir, name)
-            if len(speakers) > MAX_SPEAKERS:
-                raise ValueError(f'{name}: --init {args.init}: {len(speakers)} speakers, the device path takes at most {MAX_SPEAKERS}')
-            given.append((window_ticks(segs_dict[name][1]), (u, v, spk, len(speakers))))
+    start = from_args(args, need_vb=True)                            # the one place that knows which kind of start this is
+    def refuse_too_many(labels):
+        for name, lab in zip(names, labels):
+            if start.states(name, lab) > MAX_SPEAKERS:
+                raise ValueError(start.too_many(start.states(name, lab), tune_name=name))
+    start.read(names, segs_dict)
+    ahc = [None] * len(recordings)
+    if not start.runs_ahc:                                           # (no AHC: known before anything runs)
+        refuse_too_many(ahc)
     if t_read is None:
         t_read = time.perf_counter()
     if t_start is None:
@@ -189,42 +171,27 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
         for name in names:
             log(name)
         # the AHC initialisation does not depend on the grid: once per recording, a few recordings side by side as in the driver
-        n_workers = max(1, min(int(os.environ.get('VBX_AMD_DRIVER_THREADS', '6')), (os.cpu_count() or 2) - 1))
-        if given is not None:                                        # --init RTTM+VB: no AHC at all, one start for every point
-            ahc = [None] * len(recordings)
-        elif n_random is None:
-            with tune_host_process(), ThreadPoolExecutor(max_workers=n_workers) as pool:
-                ahc = list(pool.map(lambda k: stages.ahc(k, args.threshold, **ahc_kw)[0], range(len(recordings))))
+        if start.runs_ahc:
+            with tune_host_process(), ThreadPoolExecutor(max_workers=driver_threads()) as pool:
+                ahc = list(pool.map(lambda k: start.stage1(stages, k, names[k], args.threshold, ahc_kw)[0], range(len(recordings))))
             if hasattr(stages, 'close_thread_contexts'):
                 stages.close_thread_contexts()
-        else:                                                        # --init random_N: no AHC at all
-            ahc = [None] * len(recordings)
-            if n_random > MAX_SPEAKERS:
-                raise ValueError(f'--init {args.init}: the device path takes at most {MAX_SPEAKERS} states')
-        for (name, seg_names, _x), lab in zip(recordings, ahc):
+            refuse_too_many(ahc)
+        for name, seg_names, _x in recordings:
             assert np.all(segs_dict[name][0] == seg_names)                                # vbhmm.py:166
-            if lab is not None and int(np.max(lab)) + 1 > MAX_SPEAKERS:
-                raise ValueError(f'{name}: AHC left {int(np.max(lab)) + 1} clusters, the device path takes at most {MAX_SPEAKERS}')
         t_ahc = time.perf_counter()
         ks = list(range(len(recordings)))
         labels = []
         for Fa, Fb, loopP in grid:                                   # the call diarize_recordings makes at this point
             common = dict(init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6, precision=getattr(args, 'precision', 'fp64'),
                           loopProb=loopP, Fa=Fa, Fb=Fb)
-            if not ks:
-                res = []
-            elif given is not None:
-                res = stages.vb_turns(ks, [given[k][1] for k in ks], [given[k][0] for k in ks], **common)
-            elif n_random is None:
-                res = stages.vb(ks, [ahc[k] for k in ks], **common)
-            else:                                                    # R restarts per point and recording, the winner's labels
-                res = stages.vb_random(ks, n_random, restarts, seed, [names[k] for k in ks], **common)
+            res = start.run(stages, ks, names, ahc, common) if ks else []
             labels.append([np.asarray(r[0]) for r in res])
         t_vb = time.perf_counter()
         items = []
         for k, name in enumerate(names):
-            start, end = segs_dict[name][1].T
-            items.append((ref_turns[name], start, end, [labels[g][k] for g in range(len(grid))]))
+            begin, end = segs_dict[name][1].T
+            items.append((ref_turns[name], begin, end, [labels[g][k] for g in range(len(grid))]))
         split = {}
         collar, ignore_overlaps = getattr(args, 'collar', 0.25), getattr(args, 'ignore_overlaps', False)
         if extended:
@@ -383,10 +350,9 @@ def main(argv=None):
         if not args.collar >= 0.0:
             raise ValueError('--collar must be >= 0')
         check_criterion(args.criterion, args.step)
-        from .vbhmm import runs_ahc
         check_init(args)
-        if not runs_ahc(args.init):
-            print(f'warning: --init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored', file=sys.stderr)
+        if ahc_options_ignored(args.init) is not None:
+            print(f'warning: {ahc_options_ignored(args.init)}', file=sys.stderr)
     except ValueError as exc:
         parser.error(str(exc))
     try:

@@ -39,8 +39,10 @@ import time
 
 import numpy as np
 
+from .batch import padded_states
 from .kaldi_formats import (read_plda, read_vec_flt_ark_grouped, read_xvec_transform, read_xvector_timing_dict,
                             write_rttm)
+from .start import ahc_options_ignored, check_options, from_args, parse
 
 __all__ = ['main', 'diarize', 'diarize_recordings', 'DeviceStages', 'tune_host_process', 'load_models', 'cluster', 'cut_linkage', 'merge_adjacent_labels', 'l2_norm',
            'random_init_states', 'name_hash', 'best_restart', 'add_init_arguments', 'check_init_arguments', 'turn_init', 'runs_vb',
@@ -73,29 +75,23 @@ def merge_adjacent_labels(starts, ends, labels):
 
 def random_init_states(init):
     """N for ``--init random_N`` (N a decimal integer >= 1), None for ``AHC``, ``AHC+VB``, ``RTTM`` and ``RTTM+VB``; ValueError
-    for anything else."""
-    if init in ('AHC', 'AHC+VB') or turn_init(init):
-        return None
-    head, sep, digits = str(init).partition('_')
-    if head != 'random' or not sep or not digits.isascii() or not digits.isdigit() or int(digits) < 1:
-        raise ValueError(f"invalid choice: {init!r} (choose from 'AHC', 'AHC+VB', 'RTTM', 'RTTM+VB', 'random_<N>' with N a decimal "
-                         'integer >= 1)')
-    return int(digits)
+    for anything else (as from the three below: ``start.parse`` is the one place that reads the value)."""
+    return parse(init).n_random
 
 
 def turn_init(init):
     """Does this ``--init`` start from the speaker turns of ``--init-rttm-dir``?  RTTM and RTTM+VB do."""
-    return init in ('RTTM', 'RTTM+VB')
+    return parse(init).from_turns
 
 
 def runs_ahc(init):
     """Does this ``--init`` run the AHC stage (and hold its T x T score matrix)?"""
-    return init in ('AHC', 'AHC+VB')
+    return parse(init).runs_ahc
 
 
 def runs_vb(init):
     """Does this ``--init`` run the VB-HMM?  AHC+VB, RTTM+VB and random_N do (README.md:24: 'and run VBx')."""
-    return init.endswith('VB') or random_init_states(init) is not None
+    return parse(init).runs_vb
 
 
 def name_hash(name):
@@ -150,7 +146,8 @@ def cluster(cond, thr, threshold):
 
 
 class DeviceStages:
-    """The device side of the driver (no host fallback: without the HIP library every method raises).
+    """The device side of the driver (no host fallback: without the HIP library every method raises).  Which of ``vb``,
+    ``vb_random`` and ``vb_turns`` a run calls, and what stage 1 is, is decided once, by the ``Start`` of ``vbx_amd/start.py``.
 
     project   every x-vector of this rank goes up ONCE; the projections of vbhmm.py:125-129 and the PLDA projection of
               vbhmm.py:153 run on the device for all recordings together and stay resident (vbx_xvectors)
@@ -254,39 +251,38 @@ class DeviceStages:
             sc.close()
         return cut_linkage(lin_mat, thr, threshold), float(thr)
 
-    @staticmethod
-    def padded_states(n_states):
-        """The padded state count a batch of this many speakers runs with (vbx_host_batch.hpp: powers of two from 16)."""
-        sp = 16
-        while sp < n_states:
-            sp *= 2
-        return sp
+    padded_states = staticmethod(padded_states)       # the padded state count a batch of this many speakers runs with
 
-    def vb(self, ks, labels, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
-        """-> [(labels1st, labels2nd or None, iterations)] for the recordings ``ks`` with AHC labels ``labels``.
-
-        One ``vbx_batch`` per padded state count: every recording of a batch runs with the widest one's padding, and one
-        recording with more than 64 AHC clusters would push a whole archive from the fused kernels (responsibilities and
-        lattices on the chip) onto the wide scan -- about 5x slower per iteration."""
-        S = [int(np.max(lab)) + 1 for lab in labels]
+    def _run_batches(self, ks, S, slots, set_slots, maxIters, epsilon, precision, collect=None):
+        """The batch work of every start -> one result per recording of ``ks``, in their order.  ``S[j]`` states and ``slots`` batch
+        slots for ``ks[j]``; ``set_slots(batch, b, j)`` sets the slots b .. b + slots - 1 of ``ks[j]``; after the run ``collect(batch)``
+        is called once and what it returns once per recording, with its first slot (default: the slot's labels and iterations).
+        One ``vbx_batch`` per padded state count, the narrowest first: every recording of a batch runs with the widest one's
+        padding, and one recording with more than 64 states would push a whole archive from the fused kernels (responsibilities
+        and lattices on the chip) onto the wide scan -- about 5x slower per iteration."""
         buckets = {}
         for j, s in enumerate(S):
             buckets.setdefault(self.padded_states(s), []).append(j)
         out = [None] * len(ks)
         for _sp, members in sorted(buckets.items()):
-            batch = self._capi.Batch(self.ctx, [self.T[ks[j]] for j in members], [S[j] for j in members], self.lda_dim,
-                                     precision=precision, max_iters=maxIters)
+            batch = self._capi.Batch(self.ctx, [self.T[ks[j]] for j in members for _r in range(slots)],
+                                     [S[j] for j in members for _r in range(slots)], self.lda_dim, precision=precision, max_iters=maxIters)
             try:
                 for b, j in enumerate(members):
-                    batch.set_recording_resident(b, self.xv, self.row0[ks[j]], labels[j], init_smoothing, self.Phi,
-                                                 loopProb, Fa, Fb)
+                    set_slots(batch, b * slots, j)
                 batch.run(maxIters, epsilon)
+                result_of = collect(batch) if collect else lambda b: (*batch.labels(b), batch.n_iters(b))
                 for b, j in enumerate(members):
-                    first, second = batch.labels(b)
-                    out[j] = (first, second, batch.n_iters(b))
+                    out[j] = result_of(b * slots)
             finally:
                 batch.close()
         return out
+
+    def vb(self, ks, labels, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
+        """-> [(labels1st, labels2nd or None, iterations)] for the recordings ``ks`` with AHC labels ``labels``."""
+        def set_slots(batch, b, j):
+            batch.set_recording_resident(b, self.xv, self.row0[ks[j]], labels[j], init_smoothing, self.Phi, loopProb, Fa, Fb)
+        return self._run_batches(ks, [int(np.max(lab)) + 1 for lab in labels], 1, set_slots, maxIters, epsilon, precision)
 
     def vb_random(self, ks, N, restarts, seed, names, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
         """-> [(labels1st, labels2nd or None, iterations, winning restart, [final ELBO of every restart])] for the recordings
@@ -298,27 +294,21 @@ class DeviceStages:
         R = int(restarts)
         if R < 1 or int(N) < 1:
             raise ValueError(f'vb_random: restarts={restarts}, N={N}: both must be >= 1')
-        if not ks:
-            return []
-        batch = self._capi.Batch(self.ctx, [self.T[k] for k in ks for _r in range(R)], [int(N)] * (len(ks) * R), self.lda_dim,
-                                 precision=precision, max_iters=maxIters)
-        try:
-            for j, k in enumerate(ks):
-                h = name_hash(names[j])
-                for r in range(R):
-                    batch.set_recording_random(j * R + r, self.xv, self.row0[k], -1 if r == 0 else j * R, seed, h, r,
-                                               init_smoothing, self.Phi, loopProb, Fa, Fb)
-            batch.run(maxIters, epsilon)
+
+        def set_slots(batch, b, j):
+            h = name_hash(names[j])
+            for r in range(R):
+                batch.set_recording_random(b + r, self.xv, self.row0[ks[j]], -1 if r == 0 else b, seed, h, r, init_smoothing,
+                                           self.Phi, loopProb, Fa, Fb)
+
+        def winners(batch):
             elbos = batch.final_elbos()
-            out = []
-            for j in range(len(ks)):
-                mine = elbos[j * R:(j + 1) * R]
-                win = best_restart(mine)
-                first, second = batch.labels(j * R + win)
-                out.append((first, second, batch.n_iters(j * R + win), win, mine))
-        finally:
-            batch.close()
-        return out
+
+            def winner(b):
+                win = best_restart(elbos[b:b + R])
+                return (*batch.labels(b + win), batch.n_iters(b + win), win, elbos[b:b + R])
+            return winner
+        return self._run_batches(ks, [int(N)] * len(ks), R, set_slots, maxIters, epsilon, precision, collect=winners)
 
     def turn_labels(self, k, turns, segments):
         """-> the labels of ``--init RTTM`` for recording k: per window ``segments`` = (a, b) the speaker of ``turns`` =
@@ -331,29 +321,12 @@ class DeviceStages:
 
     def vb_turns(self, ks, turns, segments, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
         """-> [(labels1st, labels2nd or None, iterations)] for the recordings ``ks`` started from given speaker turns, ``--init
-        RTTM+VB``: ``turns[j]`` = (u, v, spk, S) and ``segments[j]`` = (a, b) of ``ks[j]``, all in ticks (``turn_init``).
-
-        One ``vbx_batch`` per padded state count, as in ``vb``; the responsibilities are built on the device from the ticks
-        (``Batch.set_recording_turns``)."""
-        buckets = {}
-        for j, t in enumerate(turns):
-            buckets.setdefault(self.padded_states(int(t[3])), []).append(j)
-        out = [None] * len(ks)
-        for _sp, members in sorted(buckets.items()):
-            batch = self._capi.Batch(self.ctx, [self.T[ks[j]] for j in members], [int(turns[j][3]) for j in members], self.lda_dim,
-                                     precision=precision, max_iters=maxIters)
-            try:
-                for b, j in enumerate(members):
-                    (a, e), (u, v, spk, _S) = segments[j], turns[j]
-                    batch.set_recording_turns(b, self.xv, self.row0[ks[j]], a, e, u, v, spk, init_smoothing, self.Phi, loopProb,
-                                              Fa, Fb)
-                batch.run(maxIters, epsilon)
-                for b, j in enumerate(members):
-                    first, second = batch.labels(b)
-                    out[j] = (first, second, batch.n_iters(b))
-            finally:
-                batch.close()
-        return out
+        RTTM+VB``: ``turns[j]`` = (u, v, spk, S) and ``segments[j]`` = (a, b) of ``ks[j]``, all in ticks (``turn_init``).  The
+        responsibilities are built on the device from the ticks (``Batch.set_recording_turns``)."""
+        def set_slots(batch, b, j):
+            (a, e), (u, v, spk, _S) = segments[j], turns[j]
+            batch.set_recording_turns(b, self.xv, self.row0[ks[j]], a, e, u, v, spk, init_smoothing, self.Phi, loopProb, Fa, Fb)
+        return self._run_batches(ks, [int(t[3]) for t in turns], 1, set_slots, maxIters, epsilon, precision)
 
     def close_thread_contexts(self):
         """The per-thread contexts (a HIP stream each) of the AHC stage: closed before the VB batch creates its stream
@@ -410,6 +383,12 @@ def tune_host_process():
     except (OSError, AttributeError):
         pass
     return _small_blas_pool()
+
+
+def driver_threads():
+    """Worker threads of stage 1 (``VBX_AMD_DRIVER_THREADS``, default 6; one core stays free): the Python glue between the native calls
+    limits the useful threads for short recordings; each holds a T x T score matrix on the device while it works (T = 20 000: 3.2 GB)."""
+    return max(1, min(int(os.environ.get('VBX_AMD_DRIVER_THREADS', '6')), (os.cpu_count() or 2) - 1))
 
 
 def _read_recordings(ark_path):
@@ -541,22 +520,9 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
         t_read = time.perf_counter()
     if t_start is None:
         t_start = t_read
-    n_random = random_init_states(args.init)                     # --init random_N: N states, no AHC stage at all
-    restarts, seed = int(getattr(args, 'random_restarts', None) or 1), int(getattr(args, 'seed', None) or 0)
-    if n_random is None and (getattr(args, 'random_restarts', None) is not None or getattr(args, 'seed', None) is not None):
-        raise ValueError('random_restarts and seed need init = random_N')
-    if restarts < 1 or seed < 0 or seed >= 1 << 64:
-        raise ValueError(f'random_restarts={restarts} must be >= 1, seed={seed} in [0, 2^64)')
-    want_vb = runs_vb(args.init)
-    given = None                                                 # --init RTTM / RTTM+VB: {name: ((a, b), (u, v, spk, S))} in ticks
-    if turn_init(args.init):
-        from .turn_init import read_init_turns, window_ticks
-        given = {}
-        for name, _seg_names, _x in recordings:                  # (only the files of the recordings of this rank)
-            u, v, spk, speakers = read_init_turns(getattr(args, 'init_rttm_dir', None), name)
-            given[name] = (window_ticks(segs_dict[name][1]), (u, v, spk, len(speakers)))
-    elif getattr(args, 'init_rttm_dir', None) is not None:
-        raise ValueError('init_rttm_dir needs init = RTTM or RTTM+VB')
+    start = from_args(args)                                      # the one place that knows which kind of start this is
+    names = [r[0] for r in recordings]
+    start.read(names, segs_dict)                                 # (only the files of the recordings of this rank)
     own_stages = stages is None
     if own_stages:
         stages = DeviceStages()
@@ -576,31 +542,16 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
 
         def prepare(k):
             file_name, seg_names, _ = recordings[k]
-            if n_random is not None:                                  # (no score matrix, no calibration: thr is nan)
-                return file_name, dict(labels1st=None, labels2nd=None, thr=float('nan'), n_iters=0, seg_names=seg_names)
-            if given is not None:
-                st = dict(labels1st=None, labels2nd=None, thr=float('nan'), n_iters=0, seg_names=seg_names)
-                segments, turns = given[file_name]
-                if turns[3] > MAX_SPEAKERS:                           # (reported with the others after the run)
-                    return file_name, st
-                if not want_vb:                                       # RTTM only: the given turns on the windows are final
-                    st['labels1st'] = stages.turn_labels(k, turns, segments)
-                    _write_rttm_files(args, file_name, st, segs_dict)
-                return file_name, st
-            labels1st, thr = stages.ahc(k, args.threshold, **ahc_kw)
+            labels1st, thr = start.stage1(stages, k, file_name, args.threshold, ahc_kw)
             st = dict(labels1st=labels1st, labels2nd=None, thr=thr, n_iters=0, seg_names=seg_names)
-            if not want_vb:
-                _write_rttm_files(args, file_name, st, segs_dict)        # AHC only: the result is final
+            if not start.runs_vb and labels1st is not None:
+                _write_rttm_files(args, file_name, st, segs_dict)        # AHC only, RTTM only: the result is final
             return file_name, st
 
-        # the Python glue between the native calls limits the useful threads for short recordings; every thread holds a
-        # T x T score matrix on the device while it works (T = 20 000: 3.2 GB)
-        n_workers = int(os.environ.get('VBX_AMD_DRIVER_THREADS', '6'))
-        n_workers = max(1, min(n_workers, (os.cpu_count() or 2) - 1))
         state = {}
         for rec in recordings:
             log(rec[0])                                               # vbhmm.py:121
-        with tune_host_process(), ThreadPoolExecutor(max_workers=n_workers) as pool:
+        with tune_host_process(), ThreadPoolExecutor(max_workers=driver_threads()) as pool:
             for file_name, st in pool.map(prepare, range(len(recordings))):      # results in archive order
                 state[file_name] = st
         if hasattr(stages, 'close_thread_contexts'):
@@ -608,44 +559,21 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
         t_ahc = time.perf_counter()
 
         # ---- stage 2: every recording of this rank in one batch ------------------------------------------------------
-        if want_vb and recordings:
-            hyper = dict(loopProb=args.loopP, Fa=args.Fa, Fb=args.Fb)
-            common = dict(init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6,
-                          precision=getattr(args, 'precision', 'fp64'), **hyper)
-            names = [r[0] for r in recordings]
-            ks = []
-            for k, name in enumerate(names):
-                if n_random is not None:
-                    if n_random > MAX_SPEAKERS:
-                        failed[name] = f'--init {args.init}: the device path takes at most {MAX_SPEAKERS} states'
-                    else:
-                        ks.append(k)
-                    continue
-                if given is not None:
-                    if given[name][1][3] > MAX_SPEAKERS:
-                        failed[name] = f'--init {args.init}: {given[name][1][3]} speakers, the device path takes at most {MAX_SPEAKERS}'
-                    else:
-                        ks.append(k)
-                    continue
-                n_clusters = int(np.max(state[name]['labels1st'])) + 1
-                if n_clusters > MAX_SPEAKERS:
-                    failed[name] = f'AHC left {n_clusters} clusters, the device path takes at most {MAX_SPEAKERS}'
-                else:
-                    ks.append(k)
+        n_states = {name: start.states(name, state[name]['labels1st']) for name in names}
+        failed.update((name, start.too_many(n)) for name, n in n_states.items() if n > MAX_SPEAKERS)
+        ks = [k for k, name in enumerate(names) if name not in failed]
+        if start.runs_vb and recordings:
+            common = dict(init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6, precision=getattr(args, 'precision', 'fp64'),
+                          loopProb=args.loopP, Fa=args.Fa, Fb=args.Fb)
 
             def finish(k, result):
                 st = state[names[k]]
                 st['labels1st'], st['labels2nd'], st['n_iters'] = result[:3]
-                if n_random is not None:                              # the winning restart and every restart's final ELBO
-                    st['restart'], st['elbos'] = result[3], result[4]
+                st.update(zip(start.result_keys, result[3:]))
                 _write_rttm_files(args, names[k], st, segs_dict)
 
             def run_vb(some):
-                if n_random is not None:
-                    return stages.vb_random(some, n_random, restarts, seed, [names[k] for k in some], **common)
-                if given is not None:
-                    return stages.vb_turns(some, [given[names[k]][1] for k in some], [given[names[k]][0] for k in some], **common)
-                return stages.vb(some, [state[names[k]]['labels1st'] for k in some], **common)
+                return start.run(stages, some, names, {k: state[names[k]]['labels1st'] for k in some}, common)
 
             try:
                 for k, result in zip(ks, run_vb(ks)):
@@ -657,10 +585,6 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
                         finish(k, run_vb([k])[0])
                     except VbxError as exc_k:
                         failed[names[k]] = str(exc_k)
-        elif given is not None:                                       # RTTM only: too many speakers is reported as above
-            for name, (_segments, turns) in given.items():
-                if turns[3] > MAX_SPEAKERS:
-                    failed[name] = f'--init {args.init}: {turns[3]} speakers, the device path takes at most {MAX_SPEAKERS}'
         t_vb = time.perf_counter()
     finally:
         if own_stages:
@@ -738,38 +662,17 @@ def add_init_arguments(p, default=None):
 
 
 def check_init_arguments(args, error, warn=None):
-    """After parsing: ``--random-restarts`` and ``--seed`` are refused (``error(message)``) unless ``--init`` is random_N and get
-    their defaults 1 and 0; ``--init-rttm-dir`` is refused unless ``--init`` is RTTM or RTTM+VB, which in turn need it.  With
-    anything but AHC and AHC+VB one line goes to ``warn`` (default: stderr) about the AHC options that are ignored."""
-    rttm_dir = getattr(args, 'init_rttm_dir', None)
-    if turn_init(args.init) and rttm_dir is None:
-        error(f'--init {args.init} needs --init-rttm-dir: the diarization to start from')
-    if not turn_init(args.init) and rttm_dir is not None:
-        error(f'--init-rttm-dir needs --init RTTM or RTTM+VB: --init {args.init} reads no diarization')
-    if random_init_states(args.init) is None:
-        for flag, value in (('--random-restarts', args.random_restarts), ('--seed', args.seed)):
-            if value is not None:
-                error(f'{flag} needs --init random_<N>: --init {args.init} draws nothing')
-        if turn_init(args.init):
-            message = f'--init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored'
-            if warn is None:
-                print(f'warning: {message}', file=sys.stderr)
-            else:
-                warn(message)
-        return
-    if args.random_restarts is None:
-        args.random_restarts = 1
-    if args.seed is None:
-        args.seed = 0
-    if args.random_restarts < 1:
-        error(f'--random-restarts {args.random_restarts}: must be >= 1')
-    if not 0 <= args.seed < 1 << 64:
-        error(f'--seed {args.seed}: must be in 0 .. 2^64 - 1')
-    message = f'--init {args.init} runs no AHC: --threshold, --ahc-scores and --target-energy are ignored'
-    if warn is None:
-        print(f'warning: {message}', file=sys.stderr)
-    else:
-        warn(message)
+    """After parsing: what ``start.check_options`` refuses goes to ``error(message)``; with random_N ``--random-restarts`` and ``--seed``
+    get their defaults 1 and 0; with anything but AHC and AHC+VB one line about the ignored AHC options goes to ``warn`` (default: stderr)."""
+    try:
+        restarts, seed = check_options(args.init, getattr(args, 'init_rttm_dir', None), args.random_restarts, args.seed)
+    except ValueError as exc:
+        return error(str(exc))
+    if parse(args.init).n_random is not None:
+        args.random_restarts, args.seed = restarts, seed
+    message = ahc_options_ignored(args.init)
+    if message is not None:
+        (warn or (lambda text: print(f'warning: {text}', file=sys.stderr)))(message)
 
 
 def add_score_arguments(p):
