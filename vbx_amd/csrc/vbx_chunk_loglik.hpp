@@ -107,31 +107,38 @@ __global__ __launch_bounds__(256, (LAT ? (SP * (int)sizeof(R) <= 128 ? 4 : 2)
                     a[buf][m][1] = load_policy<STREAM>(ra + ((long long)m * KK + kk) * 128 + 64);
                 }
             };
-            load_a(0, 0);
-            if constexpr (LAT) {
-#pragma unroll
-                for (int kk = 1; kk < 4; ++kk)
-                    if (kk < KK) load_a(kk, kk);
-            }
             // (three terms of alpha per K-block: two K-blocks per staging round keep the slice inside the region b will take)
             constexpr int KS = 2;
-            // one staging round: the alpha terms of K-blocks [kk0, kk0 + KS) into LDS, then their products.  `kslot` = the A
-            // buffer of K-block kk0 (a compile-time constant in the LAT instance, whose rounds are unrolled: a register array
-            // indexed at run time would live in scratch memory)
-            auto round = [&](int kk0, auto slot0) {
-                constexpr int kSlot0 = decltype(slot0)::value;
-                const int nk = min(KS, KK - kk0);
-                if (kk0 > 0) __syncthreads();
+            constexpr int NAF = (KS * 192 + 255) / 256;   // 16-byte vectors of a round per thread and N-tile
+            // The alpha terms of K-blocks [kk0, kk0 + KS) on their way to LDS, in two halves: fetch_alpha issues every load of the
+            // round back to back, store_alpha writes them to LDS.  Nothing is predicated: a slot past the end of the round takes
+            // the round's LAST vector -- inside the array -- and stores it where its owner stores it (the same 16 bytes to the
+            // same address).  Written as one loop `afl[q] = af[q]` over the slots, each load sat behind a full wait for the one
+            // before it (tools/loads_in_flight.py), and a predicated store lets the compiler sink its load behind the rho slab.
+            auto fetch_alpha = [&](h8 (&aft)[NT][NAF], int kk0, int nkk) {
+                const int cnt = min(KS, nkk - kk0) * 192;   // >= 192
 #pragma unroll
                 for (int n = 0; n < NT; ++n)
-                    for (int q = tid; q < nk * 192; q += 256) afl[n * (KS * 192) + q] = af[((long long)n * KK + kk0) * 192 + q];
-                __syncthreads();
+#pragma unroll
+                    for (int u = 0; u < NAF; ++u) aft[n][u] = af[((long long)n * KK + kk0) * 192 + min(u * 256 + tid, cnt - 1)];
+            };
+            auto store_alpha = [&](const h8 (&aft)[NT][NAF], int kk0, int nkk) {
+                const int cnt = min(KS, nkk - kk0) * 192;
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+#pragma unroll
+                    for (int u = 0; u < NAF; ++u) afl[n * (KS * 192) + min(u * 256 + tid, cnt - 1)] = aft[n][u];
+            };
+            // the products of the K-blocks of one staging round.  `slot0` = the A buffer of K-block kk0 (a compile-time constant in
+            // the LAT instance, whose rounds are unrolled: a register array indexed at run time would live in scratch memory)
+            auto products = [&](int kk0, int nkk, auto slot0) {
+                constexpr int kBufBase = LAT ? decltype(slot0)::value : 0;
+                const int nk = min(KS, nkk - kk0);
 #pragma unroll
                 for (int kl = 0; kl < KS; ++kl) {
                     if (kl < nk) {
                         const int kk = kk0 + kl;
-                        if (!LAT && kk + 1 < KK) load_a((kl + 1) & 1, kk + 1);      // (kk0 is even: buffer = kl & 1)
-                        constexpr int kBufBase = LAT ? kSlot0 : 0;
+                        if (!LAT && kk + 1 < nkk) load_a((kl + 1) & 1, kk + 1);      // (kk0 is even: buffer = kl & 1)
 #pragma unroll
                         for (int n = 0; n < NT; ++n) {
                             const h8* bf = afl + (n * KS + kl) * 192 + lane;
@@ -143,12 +150,45 @@ __global__ __launch_bounds__(256, (LAT ? (SP * (int)sizeof(R) <= 128 ? 4 : 2)
                     }
                 }
             };
+            // (the barriers of the staging rounds order LDS traffic only: the rho fragments in flight are not waited for)
             if constexpr (LAT) {
-                round(0, std::integral_constant<int, 0>{});
-                if (KK > KS) round(KS, std::integral_constant<int, KS>{});
+                // ALL of alpha (KK <= 4: two rounds) is requested BEFORE the rho slab -- a few KB the previous launch has just
+                // written against a 64 KB slab from HBM: it lands first, round 0 is in LDS while the slab is still arriving and
+                // round 1 waits in registers, so that the first products wait for K-block 0 of the slab and nothing else, and no
+                // round trip sits between the two barriers in the middle of the pass.  kFull (KK == 4, i.e. Dp = 128): requests,
+                // stores and products are straight-line code, so every wait counts exactly the loads behind the one it needs;
+                // with a run-time number of K-blocks the waits are sized for the shortest slab.
+                auto whole_slab = [&](auto full_tag) {
+                    const int nkk = decltype(full_tag)::value ? 4 : KK;
+                    h8 aft0[NT][NAF], aft1[NT][NAF];
+                    fetch_alpha(aft0, 0, nkk);
+                    if (nkk > KS) fetch_alpha(aft1, KS, nkk);
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk)
+                        if (kk < nkk) load_a(kk, kk);
+                    store_alpha(aft0, 0, nkk);
+                    lds_barrier();
+                    products(0, nkk, std::integral_constant<int, 0>{});
+                    if (nkk > KS) {
+                        lds_barrier();                     // every wave is done with round 0's terms
+                        store_alpha(aft1, KS, nkk);
+                        lds_barrier();
+                        products(KS, nkk, std::integral_constant<int, KS>{});
+                    }
+                };
+                if (KK == 4) whole_slab(std::true_type{});
+                else whole_slab(std::false_type{});
             } else {
+                load_a(0, 0);
 #pragma unroll 1
-                for (int kk0 = 0; kk0 < KK; kk0 += KS) round(kk0, std::integral_constant<int, 0>{});
+                for (int kk0 = 0; kk0 < KK; kk0 += KS) {
+                    h8 aft[NT][NAF];
+                    fetch_alpha(aft, kk0, KK);
+                    if (kk0 > 0) lds_barrier();            // every wave is done with the previous round's terms
+                    store_alpha(aft, kk0, KK);
+                    lds_barrier();
+                    products(kk0, KK, std::integral_constant<int, 0>{});
+                }
             }
         } else {
         // rows past the end of the recording are clamped (their results are never stored)

@@ -134,7 +134,21 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
         R* const bl = region[0];                       // b, then a (rows >= m) / x (rows < m), then gamma
         R* const r1 = region[1];                       // a_f below the crossing of its half, x_f from it on
         VBX_STAMP();
-        // everything a re-run wave needs from HBM is requested before the b tile, so that it is there when the tile is:
+        // Everything the workgroup needs before the re-run is requested in ONE go, the b tile first: its NST loads per thread
+        // stand in straight-line code in front of the branches that pick a wave's other requests -- behind them the compiler
+        // put a full wait in front of the tile's loads (it cannot tell which of the branches' loads are pending), i.e. the tile
+        // was requested one round trip after the boundary vectors and the operators.  Its stores to LDS follow those requests.
+        static_assert(NST * 256 == LAT / 4, "a full tile fills every slot of the staging round");
+        // (kTight: the folded split instance at SP = 16 lives on 96 registers and spills eight of them.  With the tile requested
+        //  up here, or behind the other requests in straight-line code, it spills sixteen to twenty-four -- 1 MB more scratch
+        //  traffic per launch of one recording (PMC) -- so it keeps its two loads in the one-pass loop they always stood in,
+        //  behind the other requests, now unconditional and back to back)
+        constexpr bool kTight = FOLD && SPLIT && SP == 16;
+        R4 btmp[NST];
+        if constexpr (!kTight) {
+            if (len == kTileFrames) stage_fetch<NST, true>(btmp, reinterpret_cast<const R4*>(bt.bmat + trow * SP), LAT / 4, tid, 256);
+            else stage_fetch<NST>(btmp, reinterpret_cast<const R4*>(bt.bmat + trow * SP), len * SP / 4, tid, 256);
+        }
         // the boundary vector and, for the waves that start at the cut, their quarter of the operator (the four 16-lane
         // rows of a wave split the sum of the product)
         constexpr int QS = SP / 4;                         // columns (forward) / rows (backward) per 16-lane row
@@ -195,7 +209,17 @@ __global__ __launch_bounds__(256, (ChunkPostCfg<R, SP>::kPerCU)) void chunk_post
 #pragma unroll
             for (int r = 0; r < NREG; ++r) ope[r] = bt.ophexp[o * SP + so + r];
         }
-        stage_to_lds<NST>(reinterpret_cast<R4*>(bl), reinterpret_cast<const R4*>(bt.bmat + trow * SP), len * SP / 4, tid, 256);
+        if constexpr (kTight) {
+            const int cnt = len * SP / 4;
+            for (int base = 0; base < cnt; base += NST * 256) {
+                stage_fetch<NST>(btmp, reinterpret_cast<const R4*>(bt.bmat + trow * SP) + base, cnt - base, tid, 256);
+                stage_store<NST>(reinterpret_cast<R4*>(bl) + base, btmp, cnt - base, tid, 256);
+            }
+        } else {
+            // (a full tile -- all but the last one of a recording -- fills every slot of the staging round: nothing predicated)
+            if (len == kTileFrames) stage_store<NST, true>(reinterpret_cast<R4*>(bl), btmp, LAT / 4, tid, 256);
+            else stage_store<NST>(reinterpret_cast<R4*>(bl), btmp, len * SP / 4, tid, 256);
+        }
         if (tid < SP) {
             const double pj = (REPLAY ? bt.pi_prev : bt.pi)[(long long)rec * SP + tid];
             c_l[tid] = (tid < n_spk) ? (R)((1.0 - lp_d) * pj + 1e-8) : (R)0;

@@ -228,25 +228,43 @@ __device__ __forceinline__ float exp_r(float x) { return __expf(x); }
 __device__ __forceinline__ double exp_r(double x) { return exp(x); }
 template <typename R> __device__ __forceinline__ R neg_inf() { return -(R)INFINITY; }
 
-// Copy `count` vectors from global memory to LDS with N independent loads in flight per thread.
+// Copy `count` vectors from global memory to LDS with N independent loads in flight per thread.  ONE pass:
+// 1 <= count <= N * nthreads.  Every caller sizes N for its whole tile and says so in a static_assert beside the call (a
+// larger count would lose its tail); count >= 1 because a tile has at least one frame (count = 0 would clamp to src[-1]).
 // A plain `dst[q] = src[q]` loop waits for every load before issuing the next one: at ~0.6 us per
 // round trip (data written by the previous kernel usually sits behind another XCD's L2) that
 // serialisation was the largest single cost of the first scan kernels.
-template <int N, typename V>
-__device__ __forceinline__ void stage_to_lds(V* dst, const V* __restrict__ src, int count, int tid, int nthreads) {
-    for (int base = 0; base < count; base += N * nthreads) {
-        V tmp[N];
+// The loads are UNCONDITIONAL and in straight-line code: a slot past the end re-reads the last vector (index clamped to
+// count - 1, inside the array by construction) and only the store is predicated.  Written as
+// `if (idx < count) tmp[u] = src[idx]` inside a loop over passes, each load sat in an exec-masked block of its own with
+// s_waitcnt vmcnt(0) in front of it -- N dependent round trips, which is what this helper exists to avoid -- and the loop
+// header put another full wait in front of the first one, behind whatever the caller had requested before
+// (tools/loads_in_flight.py lists the sequence of a built kernel; tests/test_staging_isa.py holds it).
+// FULL: the caller knows that count == N * nthreads (a whole tile): nothing is clamped or predicated.  (Where the store
+// is predicated the compiler may still sink a load into its store's block, behind the other loads: in flight with them,
+// but the first store then waits for all of them.)
+// The two halves are callable on their own, so that a kernel can put further requests between them (chunk_post).
+template <int N, bool FULL = false, typename V>
+__device__ __forceinline__ void stage_fetch(V (&tmp)[N], const V* __restrict__ src, int count, int tid, int nthreads) {
 #pragma unroll
-        for (int u = 0; u < N; ++u) {
-            const int idx = base + u * nthreads + tid;
-            if (idx < count) tmp[u] = src[idx];
-        }
-#pragma unroll
-        for (int u = 0; u < N; ++u) {
-            const int idx = base + u * nthreads + tid;
-            if (idx < count) dst[idx] = tmp[u];
-        }
+    for (int u = 0; u < N; ++u) {
+        const int idx = u * nthreads + tid;
+        tmp[u] = src[FULL || idx < count ? idx : count - 1];
     }
+}
+template <int N, bool FULL = false, typename V>
+__device__ __forceinline__ void stage_store(V* dst, const V (&tmp)[N], int count, int tid, int nthreads) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const int idx = u * nthreads + tid;
+        if (FULL || idx < count) dst[idx] = tmp[u];
+    }
+}
+template <int N, bool FULL = false, typename V>
+__device__ __forceinline__ void stage_to_lds(V* dst, const V* __restrict__ src, int count, int tid, int nthreads) {
+    V tmp[N];
+    stage_fetch<N, FULL>(tmp, src, count, tid, nthreads);
+    stage_store<N, FULL>(dst, tmp, count, tid, nthreads);
 }
 
 // Non-temporal loads (global_load_dwordx4 ... nt) for data a launch reads exactly once and that is larger than the caches:

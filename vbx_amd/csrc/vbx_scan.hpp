@@ -65,7 +65,9 @@ __global__ __launch_bounds__(SP * SP / 4) void scan1_kernel(BatchView<R> bt) {
     const int t0 = bt.tile_t0[tile];
     const int len = min(kTileFrames, rd.T - t0);
     const int tid = threadIdx.x;
-    stage_to_lds<(kTileFrames * SP / 4 + NTHR - 1) / NTHR>(
+    constexpr int NSTG = (kTileFrames * SP / 4 + NTHR - 1) / NTHR;
+    static_assert(NSTG * NTHR >= kTileFrames * SP / 4, "stage_to_lds makes one pass: N covers a whole tile");
+    stage_to_lds<NSTG>(
         reinterpret_cast<R4*>(btile), reinterpret_cast<const R4*>(bt.bmat + (rd.row0 + t0) * SP), len * SP / 4, tid, NTHR);
     __syncthreads();
     const int col = tid / PH, j0 = (tid % PH) * NR;
@@ -514,7 +516,9 @@ __global__ __launch_bounds__(64) void scan3_kernel(BatchView<R> bt) {
     } else if (bt.state[recA].done) {
         return;
     }
-    stage_to_lds<(2 * kTileFrames * SP / 4 + 63) / 64>(
+    constexpr int NSTG = (2 * kTileFrames * SP / 4 + 63) / 64;
+    static_assert(NSTG * 64 >= 2 * kTileFrames * SP / 4, "stage_to_lds makes one pass: N covers both tiles");
+    stage_to_lds<NSTG>(
         reinterpret_cast<R4*>(btile), reinterpret_cast<const R4*>(bt.bmat + (rdA.row0 + t0A) * SP),
         (lenA + lenB) * SP / 4, lane, 64);
     const R* bl = btile + (cs == 1 ? lenA * SP : 0);        // this task's rows in LDS

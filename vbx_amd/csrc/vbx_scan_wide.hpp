@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void scan1_wide_kernel(BatchView<R> bt) {
     using R4 = typename Vec<R>::v4;
     constexpr int PH = Cfg::PH, NR = Cfg::NR, CB = Cfg::CB, PIECE = Cfg::kPiece;
     constexpr int NV = (PIECE * SP / 4 + 255) / 256;
+    static_assert(NV * 256 >= PIECE * SP / 4, "stage_to_lds makes one pass: N covers a whole piece");
     __shared__ __attribute__((aligned(16))) R bp[PIECE * SP];
     const int tile = blockIdx.x;
     const int rec = bt.tile_rec[tile];
@@ -115,6 +116,7 @@ __global__ __launch_bounds__(1024) void scan1_wide_lds_kernel(BatchView<R> bt) {
     using R4 = typename Vec<R>::v4;
     constexpr int PH = 16, NR = SP / PH;
     constexpr int NV = (kTileFrames * SP / 4 + 1023) / 1024;
+    static_assert(NV * 1024 >= kTileFrames * SP / 4, "stage_to_lds makes one pass: N covers a whole tile");
     __shared__ __attribute__((aligned(16))) R btile[kTileFrames * SP];
     __shared__ __attribute__((aligned(16))) R cl[SP];
     const int tile = blockIdx.x;
