@@ -414,6 +414,30 @@ int vbx_batch_set_recording_turns(vbx_batch* batch, int b, const vbx_xvectors* x
  * equal responsibilities keep their index order (numpy leaves the order of ties unspecified).  Either may be NULL. */
 int vbx_batch_get_labels(vbx_batch* batch, int b, int32_t* first, int32_t* second);
 
+/* ---- Viterbi decoding: the jointly most probable state sequence ------------------------------------
+ * The model is vbx_forward_backward's: tr = I*loopProb + (1-loopProb)*pi, eps = 1e-8 added to tr and to ip before the
+ * logarithm (VBx.py:158-164); ip NULL: ip = pi.  lls [T][S], pi [S], ip [S] are host arrays.
+ *   path [T]  the state sequence q that maximises log(ip[q_0] + eps) + sum_t lls[t][q_t] + sum_{t>=1} log(tr[q_{t-1}][q_t] + eps)
+ *   logp      that maximum
+ * Among equal scores the lowest state index wins at the last frame and where a path enters a state; where staying in a
+ * state and entering it score the same, the path stays.  Either output may be NULL.  The call takes no guard-band argument:
+ * exactly T labels are written (the tests over-allocate and pass an interior pointer to see that nothing else is).
+ * Refused before the device is touched: NULL lls or pi, T < 1, S < 1, loopProb outside [0, 1] (VBX_ERR_INVALID); S > 1024
+ * (VBX_ERR_UNSUPPORTED, the message names S): one wavefront walks a recording with up to 16 states per lane. */
+int vbx_viterbi(vbx_ctx* ctx, int64_t T, int32_t S, const double* lls, const double* pi, const double* ip, double loopProb,
+                int32_t* path, double* logp);
+/* The same for recording b of a batch after a run, under the model of the LAST forward-backward pass -- the one the
+ * responsibilities vbx_batch_get_result returns come from: that iteration's likelihoods (the batch's b = exp(l - m_t), taken
+ * as log b: a per-frame shift does not change the path), the priors that entered it, ip = pi, the recording's loopProb.
+ *   first  [T]  the path
+ *   second [T]  the speaker of the largest gamma[t][s] among s != first[t], the lowest index among equals; -1 when S == 1
+ * Either may be NULL.  VBX_ERR_INVALID for a recording index out of range, VBX_ERR_STATE for a batch that has not run or a
+ * recording that has run no iteration (no E-step to decode), VBX_ERR_UNSUPPORTED for S[b] > 1024. */
+int vbx_batch_get_path(vbx_batch* batch, int b, int32_t* first, int32_t* second);
+/* Device time in milliseconds of the kernels of the calling thread's last successful vbx_viterbi / vbx_batch_get_path, between
+ * two events on the stream: the copies either side are not in it (tools/bench_viterbi.py). */
+double vbx_viterbi_last_ms(void);
+
 /* ---- score stage of the AHC initialisation (next row upstream of VBx(): vbhmm.py:135-138) -------------
  * cos_similarity(x)            /root/reference/VBx/diarization_lib.py:190-213
  * twoGMMcalib_lin(s, niters)   /root/reference/VBx/diarization_lib.py:13-31

@@ -16,12 +16,16 @@ against the labels is accumulated on the device inside the one run (vbx_batch_se
 cross-entropy]`` are built from that history; only the Hungarian assignment runs on the host.  ``plot=True``, more than
 64 labels or ``VBX_AMD_REF_SCORING=host`` take the responsibilities to the host after every iteration instead.
 
-Two extra keyword-only arguments (the reference call sites never pass them):
+Keyword-only arguments beyond the reference's (its call sites never pass them):
   precision  'fp64' | 'fp32' | None.  None -> $VBX_AMD_PRECISION or "auto": float32 ``X``
              selects the fp32 device path, anything else the fp64 path (the reference always
              computes in float64, VBx.py:87).  The fp64 path reproduces the reference's
              iteration count under ``epsilon``; fp32 matches gamma/pi/Li to ~1e-5 relative.
   device     HIP device index (default $VBX_AMD_DEVICE / $LOCAL_RANK / 0).
+  return_path  append ``path`` (int64 [T]) to the returned tuple: the jointly most probable speaker sequence under the
+             model of the last forward-backward pass, where ``argmax(gamma, 1)`` is the frame-wise one.
+
+``viterbi(lls, loopProb, pi, ip=None)`` is that decode for log-likelihoods of the caller's, next to ``forward_backward``.
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ['VBx', 'forward_backward', 'DER', 'speaker_confusion', 'der_from_confusion']
+__all__ = ['VBx', 'forward_backward', 'viterbi', 'DER', 'speaker_confusion', 'der_from_confusion']
 
 _EPS_TR = 1e-8          # VBx.py:158
 
@@ -46,10 +50,10 @@ def _pick_precision(precision, X):
 
 def VBx(X, Phi, loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, maxIters=10,
         epsilon=1e-4, alphaQInit=1.0, ref=None, plot=False,
-        return_model=False, alpha=None, invL=None, *, precision=None, device=None):
+        return_model=False, alpha=None, invL=None, *, precision=None, device=None, return_path=False):
     """Variational-Bayes HMM over an x-vector sequence; see the reference docstring
     (VBx.py:30-67) for the meaning of every argument.  Returns ``(gamma[T,S], pi[S], Li)``
-    plus ``(alpha[S,D], invL[S,D])`` when ``return_model`` is set."""
+    plus ``(alpha[S,D], invL[S,D])`` when ``return_model`` is set, plus ``path[T]`` last when ``return_path`` is."""
     X = np.asarray(X)
     Phi = np.asarray(Phi)
     if type(pi) is int:                                   # VBx.py:76-77: Python int only
@@ -63,6 +67,8 @@ def VBx(X, Phi, loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, maxIters=10,
     T, D = X.shape
     S = len(pi)
     if maxIters <= 0:                                     # range(0): inputs come back untouched
+        if return_path:
+            raise ValueError('VBx: return_path needs an E-step to decode; maxIters = 0 runs none')
         return (gamma, pi, []) + ((alpha, invL) if return_model else ())
 
     ctx = _capi.default_context(device)
@@ -98,11 +104,14 @@ def VBx(X, Phi, loopProb=0.9, Fa=1.0, Fb=1.0, pi=10, gamma=None, maxIters=10,
                     break
         if res['warned']:
             print('WARNING: Value of auxiliary function has decreased!')   # VBx.py:123-124
+        path = batch.path(0)[0] if return_path else None
     finally:
         batch.close()
     out = (res['gamma'], res['pi'], Li)
     if return_model:
         out = out + (res['alpha'], res['invL'])
+    if return_path:
+        out = out + (path,)
     return out
 
 
@@ -179,6 +188,19 @@ def DER(q, ref, expected=True, xentropy=False):
     if xentropy:
         return best / float(n_frames)
     return (n_frames + best) / float(n_frames)
+
+
+def viterbi(lls, loopProb, pi, ip=None, *, device=None):
+    """The jointly most probable state sequence of the HMM forward_backward() sums over, for the transition structure VBx()
+    builds (``tr = I*loopProb + (1-loopProb)*pi``, VBx.py:98; 1e-8 added to ``tr`` and ``ip`` before the logarithm as
+    VBx.py:158-164 add it): ``(path int32 [T], logp)``.  ``ip=None``: ``ip = pi`` (VBx.py:99).  Up to 1024 states, on the device
+    (vbx_viterbi.hpp); among equal scores the lowest state index wins, and a path that may stay or enter at equal score stays."""
+    lls = np.asarray(lls, dtype=np.float64)
+    pi = np.asarray(pi, dtype=np.float64)
+    if lls.ndim != 2 or pi.shape != (lls.shape[1],) or (ip is not None and np.shape(ip) != pi.shape):
+        raise ValueError('viterbi: lls [T][S], pi [S] and ip [S] (or None) expected')
+    path, logp = _capi.default_context(device).viterbi(lls, pi, loopProb, ip=ip)
+    return path, np.float64(logp)
 
 
 def _split_transition(tr):

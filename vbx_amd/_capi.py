@@ -29,6 +29,7 @@ PLAN_FLAGS = PLAN_FIELDS[:8] + ['use_chunked']
 K_NAMES = ['prep', 'mstep_acc', 'mstep_fin', 'loglik', 'fb', 'fb_aux', 'post', 'iter_fin', 'chunk_loglik',
            'chunk_post']
 MAX_SPEAKERS = 16384
+MAX_DECODE_STATES = 1024      # kVitMaxStates: one wavefront walks a recording's Viterbi decode, 16 states per lane (vbx_viterbi.hpp)
 PLDA_COV_CHUNK = 512         # rows of one partial of the PLDA covariance (vbx_plda_score.hpp: kCovChunk)
 PLDA_MAX_DIM = 256           # dimensions the PLDA projection kernel keeps (vbx_plda_score.hpp: 16 * kPldaMaxTiles)
 MAX_REF_LABELS = 64          # labels a recording can be scored against on the device (vbx_batch_set_reference)
@@ -77,6 +78,7 @@ ABI_SYMBOLS = [
     'vbx_turn_weights', 'vbx_batch_set_recording_turns',
     'vbx_backend_class_sums', 'vbx_backend_second_moments', 'vbx_backend_create', 'vbx_backend_stage1', 'vbx_backend_stage2',
     'vbx_backend_destroy',
+    'vbx_viterbi', 'vbx_batch_get_path', 'vbx_viterbi_last_ms',
 ]
 
 
@@ -157,6 +159,9 @@ def load():
     lib.vbx_cos_similarity_resident.argtypes = [vp, vp, i64, i64, C.POINTER(vp)]
     lib.vbx_batch_set_recording_resident.argtypes = [vp, C.c_int, vp, i64, vp, dbl, vp, dbl, dbl, dbl]
     lib.vbx_batch_get_labels.argtypes = [vp, C.c_int, vp, vp]
+    lib.vbx_batch_get_path.argtypes = [vp, C.c_int, vp, vp]
+    lib.vbx_viterbi.argtypes = [vp, i64, i32, vp, vp, vp, dbl, vp, C.POINTER(dbl)]
+    lib.vbx_viterbi_last_ms.argtypes = []
     lib.vbx_batch_sync_uploads.argtypes = [vp]
     lib.vbx_batch_stream_of.argtypes = [vp, C.c_int]
     lib.vbx_batch_get_results.argtypes = [vp, C.c_int, vp]
@@ -221,6 +226,8 @@ def load():
         fn = getattr(lib, name)          # AttributeError here = the .so does not export the ABI
         if name in ('vbx_scores_count', 'vbx_ark_index'):
             fn.restype = C.c_int64
+        elif name == 'vbx_viterbi_last_ms':
+            fn.restype = C.c_double
         elif name not in ('vbx_last_error', 'vbx_abi_version'):
             fn.restype = C.c_int
     _lib = lib
@@ -379,6 +386,16 @@ class Context:
                                         precision_code(precision), _ptr(out)), 'vbx_loglik')
         return out
 
+    def viterbi(self, lls, pi, loopProb, ip=None):
+        """(path int32 [T], logp): the most probable state sequence under forward_backward's model (vbx_viterbi)."""
+        lls, pi, ip = _f64(lls), _f64(pi), _f64(ip)
+        T, S = lls.shape
+        assert pi.shape == (S,) and (ip is None or ip.shape == (S,))
+        path = np.empty(T, dtype=np.int32)
+        logp = C.c_double()
+        self.check(self._lib.vbx_viterbi(self._h, T, S, _ptr(lls), _ptr(pi), _ptr(ip), float(loopProb), _ptr(path),
+                                         C.byref(logp)), 'vbx_viterbi')
+        return path, logp.value
 
     def score_posteriors(self, gamma, ref, n_ref=None, precision='fp64'):
         """Confusion block C[2][n_ref][S] of responsibilities ``gamma[T,S]`` against labels ``ref[T]`` (vbx_score_posteriors):
@@ -1094,6 +1111,15 @@ class Batch:
         first = np.empty(self.T[b], dtype=np.int32)
         second = np.empty(self.T[b], dtype=np.int32)
         self.ctx.check(self._lib.vbx_batch_get_labels(self._h, int(b), _ptr(first), _ptr(second)), 'vbx_batch_get_labels')
+        return first.astype(np.int64), (second.astype(np.int64) if self.S[b] > 1 else None)
+
+    def path(self, b):
+        """(first, second) of recording b after a run: first is the most probable state sequence under the model of the
+        last forward-backward pass, second the best other speaker of every frame by responsibility (None for a single
+        speaker) -- vbx_batch_get_path."""
+        first = np.empty(self.T[b], dtype=np.int32)
+        second = np.empty(self.T[b], dtype=np.int32)
+        self.ctx.check(self._lib.vbx_batch_get_path(self._h, int(b), _ptr(first), _ptr(second)), 'vbx_batch_get_path')
         return first.astype(np.int64), (second.astype(np.int64) if self.S[b] > 1 else None)
 
     def set_reference(self, b, ref, n_ref=None):

@@ -134,7 +134,7 @@ def _pipeline_halves(n_rec, n_bytes):
     return os.environ.get('VBX_AMD_BATCH_PIPELINE') == '1' and n_rec >= 2
 
 
-def _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results, gates=None):
+def _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results, gates=None, want_path=False):
     """One vbx_batch for the recordings ``idx`` of ``items`` on ``ctx``: enqueue the uploads (one host thread per stream),
     iterate, fetch.  ``gates`` = (upload, run, fetch) locks shared with the other half of a pipelined call: the host link
     carries one half's arrays at a time in each direction, and at most one half iterates."""
@@ -176,12 +176,14 @@ def _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results, gates=N
             for j, (k, res) in enumerate(zip(idx, batch.results())):
                 if items[k].get('ref') is not None:       # the confusion block of every iteration (_as_tuple: DER, cross-entropy)
                     res['conf'] = batch.scores(j)
+                if want_path:                             # (_as_tuple: the most probable speaker sequence, last in the tuple)
+                    res['path'] = batch.path(j)[0]
                 results[k] = res
     finally:
         batch.close()
 
 
-def run_shard_hip(items, maxIters, epsilon, precision=None, device=None):
+def run_shard_hip(items, maxIters, epsilon, precision=None, device=None, want_path=False):
     """Run normalised recordings on the local GPU, one vbx_batch per (feature dimension, padded state count): every
     recording of a batch runs with the widest one's padding, and one recording with more than 64 speakers would push the
     others from the fused kernels onto the wide scan.  ``precision=None`` is VBx()'s rule (VBX_AMD_PRECISION, else fp32
@@ -210,7 +212,7 @@ def run_shard_hip(items, maxIters, epsilon, precision=None, device=None):
 
             def work(slot, part):
                 try:
-                    _run_one_batch(_capi.default_context(ctx.device, slot), items, part, D, prec, maxIters, epsilon, results, gates)
+                    _run_one_batch(_capi.default_context(ctx.device, slot), items, part, D, prec, maxIters, epsilon, results, gates, want_path)
                 except BaseException as exc:           # (re-raised on the calling thread)
                     errors.append(exc)
             threads = [threading.Thread(target=work, args=(slot, part)) for slot, part in enumerate(halves)]
@@ -221,12 +223,12 @@ def run_shard_hip(items, maxIters, epsilon, precision=None, device=None):
             if errors:
                 raise errors[0]
         else:
-            _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results)
+            _run_one_batch(ctx, items, idx, D, prec, maxIters, epsilon, results, want_path=want_path)
     return results
 
 
-def VBx_batch(recordings, maxIters=10, epsilon=1e-4, precision=None, device=None, return_model=False,
-              **defaults):
+def VBx_batch(recordings, maxIters=10, epsilon=1e-4, precision=None, device=None, return_model=False, *,
+              return_path=False, **defaults):
     """``[VBx(**rec, maxIters=..., epsilon=...) for rec in recordings]`` on one GPU, in one batch.
 
     Each recording is a dict with ``X`` and ``Phi`` plus the per-recording keyword arguments of VBx(): ``loopProb``,
@@ -239,13 +241,20 @@ def VBx_batch(recordings, maxIters=10, epsilon=1e-4, precision=None, device=None
     not T non-negative integers below 64.  ``precision`` follows VBx(): fp64 kernels
     unless every X is float32 (or VBX_AMD_PRECISION / the argument says otherwise) -- NB before round 2 the default was
     fp32 whatever the input type -- so the numerics and iteration counts are those of one VBx() call per recording.  Returns a list of ``(gamma, pi, Li[,
-    alpha, invL])`` tuples in input order (same types as the reference returns, VBx.py:126)."""
+    alpha, invL])`` tuples in input order (same types as the reference returns, VBx.py:126); ``return_path=True`` appends
+    every recording's most probable speaker sequence (VBx(return_path=True)) last, and is a ValueError with ``maxIters = 0``."""
     items = [_normalise(r, defaults) for r in recordings]
     if maxIters <= 0:
+        _no_path_without_estep(return_path, 'VBx_batch')
         return [(it['gamma'], it['pi'], []) + ((it['alpha'], it['invL']) if return_model else ())
                 for it in items]
-    raw = run_shard_hip(items, int(maxIters), epsilon, precision=precision, device=device)
-    return [_as_tuple(r, return_model) for r in raw]
+    raw = run_shard_hip(items, int(maxIters), epsilon, precision=precision, device=device, want_path=return_path)
+    return [_as_tuple(r, return_model, return_path=return_path) for r in raw]
+
+
+def _no_path_without_estep(return_path, who):
+    if return_path:
+        raise ValueError(f'{who}: return_path needs an E-step to decode; maxIters = 0 runs none')
 
 
 def sweep_streams(n_points, T):
@@ -262,7 +271,7 @@ def sweep_streams(n_points, T):
     return 3 if (n_points >= 6 and tiles >= 4608) else 2 if (n_points >= 4 and tiles >= 3072) else 1
 
 
-def run_sweep_hip(X, Phi, items, maxIters, epsilon, precision=None, device=None):
+def run_sweep_hip(X, Phi, items, maxIters, epsilon, precision=None, device=None, want_path=False):
     """Normalised sweep points over ONE recording on the local GPU: one vbx_batch, the first point owns rho, the others
     share it (vbx_batch_set_recording_shared) -- one rho per stream sub-batch (sweep_streams)."""
     from . import _capi
@@ -286,13 +295,15 @@ def run_sweep_hip(X, Phi, items, maxIters, epsilon, precision=None, device=None)
         for j, it in enumerate(items):
             if it.get('ref') is not None:
                 out[j]['conf'] = batch.scores(j)
+            if want_path:
+                out[j]['path'] = batch.path(j)[0]
         return out
     finally:
         batch.close()
 
 
-def VBx_sweep(X, Phi, points, maxIters=10, epsilon=1e-4, precision=None, device=None, return_model=False, ref=None,
-              **defaults):
+def VBx_sweep(X, Phi, points, maxIters=10, epsilon=1e-4, precision=None, device=None, return_model=False, ref=None, *,
+              return_path=False, **defaults):
     """``[VBx(X, Phi, **defaults, **p, maxIters=..., epsilon=...) for p in points]`` -- a hyper-parameter sweep over ONE
     recording, the grids of the reference's recipes (DIHARD2_run.sh:42-47, AMI_run.sh:44-49, CALLHOME_run.sh:42-47:
     Fa x Fb x loopP around one x-vector sequence) -- as one batch on one GPU with ONE rho = X * sqrt(Phi) (VBx.py:89) in
@@ -301,20 +312,23 @@ def VBx_sweep(X, Phi, points, maxIters=10, epsilon=1e-4, precision=None, device=
     VBx() (``Fa``, ``Fb``, ``loopProb``, ``pi``, ``gamma``, ``alphaQInit``, ``alpha``, ``invL``).  ``gamma=None`` draws the
     initialisation from the global RNG per point, in list order, exactly as successive VBx() calls would.  ``ref``: reference
     labels of the recording, one array for all points -- every point's ``Li`` rows are then ``[ELBO, DER, cross-entropy]``
-    (what a grid is scored by), accumulated on the device.  Returns the list of ``(gamma, pi, Li[, alpha, invL])`` tuples."""
+    (what a grid is scored by), accumulated on the device.  Returns the list of ``(gamma, pi, Li[, alpha, invL])`` tuples, with
+    every point's most probable speaker sequence last when ``return_path`` is set (ValueError with ``maxIters = 0``)."""
     X = np.asarray(X)
     if ref is not None:
         defaults = dict(defaults, ref=ref)
     items = [_normalise(dict(p, X=X, Phi=Phi), defaults) for p in points]
     if maxIters <= 0:
+        _no_path_without_estep(return_path, 'VBx_sweep')
         return [(it['gamma'], it['pi'], []) + ((it['alpha'], it['invL']) if return_model else ()) for it in items]
     if not items:
         return []
-    raw = run_sweep_hip(X, np.asarray(Phi), items, int(maxIters), epsilon, precision=precision, device=device)
-    return [_as_tuple(r, return_model) for r in raw]
+    raw = run_sweep_hip(X, np.asarray(Phi), items, int(maxIters), epsilon, precision=precision, device=device,
+                        want_path=return_path)
+    return [_as_tuple(r, return_model, return_path=return_path) for r in raw]
 
 
-def _as_tuple(res, return_model, warn=True):
+def _as_tuple(res, return_model, warn=True, return_path=False):
     if res['warned'] and warn:
         print('WARNING: Value of auxiliary function has decreased!')       # VBx.py:123-124
     if res.get('conf') is not None:                       # a recording with reference labels: [ELBO, DER, cross-entropy] rows
@@ -325,6 +339,8 @@ def _as_tuple(res, return_model, warn=True):
     out = (res['gamma'], res['pi'], Li)
     if return_model:
         out = out + (res['alpha'], res['invL'])
+    if return_path:
+        out = out + (res['path'],)
     return out
 
 

@@ -32,7 +32,7 @@ def _find_objdump() -> str | None:
 
 OBJDUMP = _find_objdump()
 SOURCES = ['vbx_capi.hip']
-HEADERS = ['vbx_host_state.hpp', 'vbx_host_launch.hpp', 'vbx_host_call.hpp', 'vbx_host_batch.hpp', 'vbx_host_group.hpp', 'vbx_host_set.hpp', 'vbx_host_steps.hpp', 'vbx_host_ahc.hpp', 'vbx_device.hpp', 'vbx_kernels.hpp', 'vbx_scan.hpp', 'vbx_scan_wide.hpp', 'vbx_fb_dense.hpp', 'vbx_operator.hpp', 'vbx_split.hpp', 'vbx_chunk_loglik.hpp', 'vbx_chunk_post.hpp', 'vbx_big.hpp', 'vbx_score.hpp', 'vbx_linkage.hpp', 'vbx_ahc.hpp', 'vbx_plda_score.hpp', 'vbx_rttm_score.hpp', 'vbx_labels_score.hpp', 'vbx_vad.hpp', 'vbx_frame_score.hpp', 'vbx_labels_frame.hpp', 'vbx_resample.hpp', 'vbx_turn_init.hpp', 'vbx_backend.hpp', 'vbx_frontend.hpp', 'vbx_fbank.hpp', 'vbx_host_fbank.hpp', 'vbx_resnet.hpp', 'vbx_resnet_split.hpp', 'vbx_host_resnet.hpp', os.path.join('..', '..', 'include', 'vbx_hip.h')]
+HEADERS = ['vbx_host_state.hpp', 'vbx_host_launch.hpp', 'vbx_host_call.hpp', 'vbx_host_batch.hpp', 'vbx_host_group.hpp', 'vbx_host_set.hpp', 'vbx_host_steps.hpp', 'vbx_host_ahc.hpp', 'vbx_device.hpp', 'vbx_kernels.hpp', 'vbx_scan.hpp', 'vbx_scan_wide.hpp', 'vbx_fb_dense.hpp', 'vbx_operator.hpp', 'vbx_split.hpp', 'vbx_chunk_loglik.hpp', 'vbx_chunk_post.hpp', 'vbx_big.hpp', 'vbx_score.hpp', 'vbx_linkage.hpp', 'vbx_ahc.hpp', 'vbx_plda_score.hpp', 'vbx_rttm_score.hpp', 'vbx_labels_score.hpp', 'vbx_vad.hpp', 'vbx_frame_score.hpp', 'vbx_labels_frame.hpp', 'vbx_resample.hpp', 'vbx_turn_init.hpp', 'vbx_backend.hpp', 'vbx_viterbi.hpp', 'vbx_frontend.hpp', 'vbx_fbank.hpp', 'vbx_host_fbank.hpp', 'vbx_resnet.hpp', 'vbx_resnet_split.hpp', 'vbx_host_resnet.hpp', os.path.join('..', '..', 'include', 'vbx_hip.h')]
 # -slp-vectorize-hor=false: the compiler's vectorised sums end in "v_pk_add_f32 d, p, p op_sel:[0,1]" (x + y of a register
 # pair), one of the packed-f32 forms that misread src1 on gfx950 under matrix-instruction load (audit_isa() below,
 # DESIGN section 6); with horizontal reductions left scalar none of them is generated, and audit_isa() makes sure

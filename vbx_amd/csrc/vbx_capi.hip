@@ -55,6 +55,7 @@ using namespace vbx;
 #include "vbx_turn_init.hpp"     // --init RTTM+VB: speaker turns resampled onto the x-vector windows
 #include "vbx_host_set.hpp"      // the six ways a batch slot is set: one path (needs the resident x-vectors and the two kernels above)
 #include "vbx_backend.hpp"       // training the backend: class sums and segmented second moments of labelled x-vectors
+#include "vbx_viterbi.hpp"       // the most probable state sequence: one wavefront per recording, vbx_viterbi, vbx_batch_get_path
 
 #ifdef VBX_PHASE_CLOCKS
 // instrumentation builds only: the per-tile phase stamps of chunk_post_mid_kernel (tile, {wave 0, wave 2}, 8)

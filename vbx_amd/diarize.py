@@ -97,6 +97,7 @@ def build_parser():
     p.add_argument('--precision', default='fp64', choices=['fp64', 'fp32', 'fp32-split'],
                    help='arithmetic of the VB-HMM kernels (fp64 = the reference\'s dtype and iteration counts)')
     p.add_argument('--timing', action='store_true', help='print a JSON line with the stage timings')
+    vbhmm.add_decode_argument(p)
     vbhmm.add_score_arguments(p)
     return p
 
@@ -137,6 +138,7 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     _check(args, p.error)
     vbhmm.check_init_arguments(args, p.error)
+    vbhmm.check_decode_argument(args, p.error)
     return args
 
 
@@ -304,7 +306,7 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
                   ahc_scores='cos', init_smoothing=5.0, output_2nd=False, precision='fp64', gemm='exact', embed_dim=256,
                   seg_len=144, seg_jump=24, batch_size=128, no_dither=False, dither='host', out_ark_fn=None, out_seg_fn=None,
                   log=None, ref_rttm_dir=None, collar=0.25, ignore_overlaps=False, resample_to=None, random_restarts=None,
-                  seed=None, init_rttm_dir=None):
+                  seed=None, init_rttm_dir=None, decode='posterior'):
     """Diarize ``wav_dir/<name>.wav`` with the VAD labels ``lab_dir/<name>.lab`` for every name of ``file_names``.
 
     -> ``({recording: dict(labels1st, labels2nd, n_iters, thr, starts, ends)}, timing)``: per x-vector of the recording its
@@ -327,7 +329,13 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
 
     ``init='RTTM+VB'`` with ``init_rttm_dir``: no AHC; the VB-HMM starts from the diarization ``<init_rttm_dir>/<name>.rttm``,
     resampled on the device onto the windows the extraction left (``vbhmm.DeviceStages.vb_turns``); ``init='RTTM'`` returns and
-    writes that resampling alone.  ``thr`` is nan."""
+    writes that resampling alone.  ``thr`` is nan.
+
+    ``decode='viterbi'`` (with an ``init`` that runs the VB-HMM): ``labels1st`` is the jointly most probable speaker sequence
+    of the HMM under the model of the last iteration instead of the frame-wise largest responsibility, ``labels2nd`` the best
+    other speaker of every frame (``vbhmm.DeviceStages``, ``_capi.Batch.path``); at most 1024 speakers per recording."""
+    if decode not in vbhmm.DECODES:
+        raise ValueError(f'decode must be one of {vbhmm.DECODES}, not {decode!r}')
     args = argparse.Namespace(
         gpus=str(device), checkpoint=checkpoint, gemm=gemm, model=None, weights=None, model_file=None, backend='pytorch',
         ndim=fbank.N_MEL, embed_dim=embed_dim, seg_len=seg_len, seg_jump=seg_jump, in_file_list=None, in_lab_dir=lab_dir,
@@ -335,7 +343,7 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
         dither=dither, init=init, out_rttm_dir=out_rttm_dir, xvec_transform=xvec_transform, plda_file=plda_file,
         threshold=threshold, lda_dim=lda_dim, Fa=Fa, Fb=Fb, loopP=loopP, target_energy=target_energy, ahc_scores=ahc_scores,
         init_smoothing=init_smoothing, output_2nd=output_2nd, precision=precision, timing=False, resample_to=resample_to,
-        random_restarts=random_restarts, seed=seed, init_rttm_dir=init_rttm_dir)
+        random_restarts=random_restarts, seed=seed, init_rttm_dir=init_rttm_dir, decode=decode)
     if ref_rttm_dir is not None:
         args.ref_rttm_dir, args.collar, args.ignore_overlaps = ref_rttm_dir, collar, ignore_overlaps
     try:
@@ -347,6 +355,7 @@ def diarize_files(file_names, wav_dir, lab_dir, checkpoint, xvec_transform, plda
         raise ValueError(msg)
     _check(args, error)
     vbhmm.check_init_arguments(args, error, warn=lambda _message: None)       # (a library call has said what it wants)
+    vbhmm.check_decode_argument(args, error)
     if vbhmm.turn_init(init):                                                 # (a missing directory fails before the extraction)
         from .turn_init import check_init_rttm_dir
         check_init_rttm_dir(init_rttm_dir)

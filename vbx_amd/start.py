@@ -29,9 +29,10 @@ class Start:
         """Stage 1 of recording k -> (labels or None, calibrated threshold or nan)."""
         return None, float('nan')
 
-    def too_many(self, n, tune_name=None):
-        """Why a recording of ``n`` > MAX_SPEAKERS states is left out; ``tune_name``: as tune words it, which ends there."""
-        return self.TOO_MANY.format(who='' if tune_name is None else f'{tune_name}: ', init=self.init, n=n, most=MAX_SPEAKERS)
+    def too_many(self, n, tune_name=None, most=MAX_SPEAKERS):
+        """Why a recording of ``n`` > ``most`` states is left out (MAX_SPEAKERS; ``--decode viterbi``: the decode's limit);
+        ``tune_name``: as tune words it, which ends there."""
+        return self.TOO_MANY.format(who='' if tune_name is None else f'{tune_name}: ', init=self.init, n=n, most=most)
 
 
 class AhcStart(Start):

@@ -121,7 +121,7 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
                     t_start=None, t_read=None):
     """The grid search for recordings in memory: ``recordings`` = ``[(name, seg_names, x)]``, ``segs_dict``, ``models`` and
     ``args`` (threshold, lda_dim, init_smoothing and, optionally, precision, ahc_scores, target_energy, collar,
-    ignore_overlaps, criterion, step) as ``vbhmm.diarize_recordings`` takes them, ``grid`` = ``[(Fa, Fb, loopP)]``, ``ref_turns`` =
+    ignore_overlaps, criterion, step, decode) as ``vbhmm.diarize_recordings`` takes them, ``grid`` = ``[(Fa, Fb, loopP)]``, ``ref_turns`` =
     ``{name: [(start, end, speaker)]}``.  ``stages`` defaults to ``DeviceStages()``; with injected host stages (an object
     without a device context) the scoring runs in numpy.
 
@@ -134,8 +134,12 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
     columns and their integers), ``pooled`` the OVERALL rows of ``metrics._overall``, and the dict also holds ``criterion`` and
     ``step``."""
     from concurrent.futures import ThreadPoolExecutor
-    from ._capi import MAX_SPEAKERS
-    from .vbhmm import DeviceStages, _ahc_kw, driver_threads, tune_host_process
+    from ._capi import MAX_DECODE_STATES, MAX_SPEAKERS
+    from .vbhmm import DECODES, DeviceStages, _ahc_kw, driver_threads, tune_host_process
+    decode = getattr(args, 'decode', 'posterior')
+    if decode not in DECODES:
+        raise ValueError(f'decode must be one of {DECODES}, not {decode!r}')
+    most = MAX_DECODE_STATES if decode == 'viterbi' else MAX_SPEAKERS
     criterion, step = check_criterion(getattr(args, 'criterion', 'der'), getattr(args, 'step', None))
     extended = criterion != 'der' or step is not None
     grid = [tuple(float(v) for v in g) for g in grid]
@@ -151,8 +155,8 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
     start = from_args(args, need_vb=True)                            # the one place that knows which kind of start this is
     def refuse_too_many(labels):
         for name, lab in zip(names, labels):
-            if start.states(name, lab) > MAX_SPEAKERS:
-                raise ValueError(start.too_many(start.states(name, lab), tune_name=name))
+            if start.states(name, lab) > most:
+                raise ValueError(start.too_many(start.states(name, lab), tune_name=name, most=most))
     start.read(names, segs_dict)
     ahc = [None] * len(recordings)
     if not start.runs_ahc:                                           # (no AHC: known before anything runs)
@@ -185,6 +189,8 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
         for Fa, Fb, loopP in grid:                                   # the call diarize_recordings makes at this point
             common = dict(init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6, precision=getattr(args, 'precision', 'fp64'),
                           loopProb=loopP, Fa=Fa, Fb=Fb)
+            if decode != 'posterior':                                # (every point is read out the same way)
+                common['decode'] = decode
             res = start.run(stages, ks, names, ahc, common) if ks else []
             labels.append([np.asarray(r[0]) for r in res])
         t_vb = time.perf_counter()
@@ -211,6 +217,8 @@ def tune_recordings(recordings, segs_dict, models, args, grid, ref_turns, stages
                   score_mapping=split.get('mapping', 0.0), score=t_score - t_vb, total=time.perf_counter() - t_start,
                   recordings=len(names), points=len(grid), xvectors=int(sum(len(r[1]) for r in recordings)))
     result = dict(grid=grid, names=names, labels=labels, records=records, pooled=pooled, best=best_point(pooled, criterion), timing=timing)
+    if decode != 'posterior':
+        result['decode'] = decode
     if extended:
         result.update(criterion=criterion, step=step)
     return result
@@ -249,6 +257,8 @@ def format_table(result):
         best = f'DER={_percent(result["pooled"][result["best"]])[0]}'
     width = [max(len(r[c]) for r in rows) for c in range(len(rows[0]))]
     lines = ['  '.join(r[c].rjust(width[c]) for c in range(len(rows[0]))) for r in rows]
+    if 'decode' in result:                                           # (--decode other than the default: said above the header row)
+        lines.insert(0, f'decode: {result["decode"]}')
     Fa, Fb, loopP = result['grid'][result['best']]
     lines.append(f'best: Fa={Fa:g} Fb={Fb:g} loopP={loopP:g} {best}')
     return '\n'.join(lines)
@@ -272,6 +282,8 @@ def to_json(result, args=None):
                          pooled=figures(result['pooled'][b])), timing=result['timing'])
     if 'criterion' in result:
         out.update(criterion=result['criterion'], step=result['step'])
+    if 'decode' in result:
+        out.update(decode=result['decode'])
     return out
 
 
@@ -305,7 +317,7 @@ def tune(args, stages=None, log=print):
 
 
 def build_parser():
-    from .vbhmm import add_init_arguments
+    from .vbhmm import add_decode_argument, add_init_arguments
     p = argparse.ArgumentParser(prog='python -m vbx_amd.tune', description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--xvec-ark-file', required=True, type=str,
                    help='Kaldi ark file with x-vectors from one or more input recordings (all x-vectors of one recording consecutive)')
@@ -323,6 +335,7 @@ def build_parser():
     p.add_argument('--init-smoothing', required=False, type=float, default=5.0,
                    help='smoothing of the hard AHC labels into the initial soft assignments')
     p.add_argument('--precision', default='fp64', choices=['fp64', 'fp32', 'fp32-split'], help='arithmetic of the VB-HMM kernels')
+    add_decode_argument(p)
     p.add_argument('--ref-rttm-dir', required=True, type=str, help='reference turns: <dir>/<recording>.rttm for every recording of the archive')
     p.add_argument('--collar', required=False, type=float, default=0.25,
                    help='no-score zone round every reference turn boundary, seconds (default: %(default)s)')

@@ -253,7 +253,15 @@ class DeviceStages:
 
     padded_states = staticmethod(padded_states)       # the padded state count a batch of this many speakers runs with
 
-    def _run_batches(self, ks, S, slots, set_slots, maxIters, epsilon, precision, collect=None):
+    @staticmethod
+    def _read_out(batch, decode):
+        """first / second speaker of a slot: the frame-wise argmax of the responsibilities (vbhmm.py:160-162) or, ``--decode
+        viterbi``, the most probable speaker sequence and the best other speaker of every frame (``Batch.path``)."""
+        if decode not in DECODES:
+            raise ValueError(f'decode must be one of {DECODES}, not {decode!r}')
+        return batch.path if decode == 'viterbi' else batch.labels
+
+    def _run_batches(self, ks, S, slots, set_slots, maxIters, epsilon, precision, collect=None, decode='posterior'):
         """The batch work of every start -> one result per recording of ``ks``, in their order.  ``S[j]`` states and ``slots`` batch
         slots for ``ks[j]``; ``set_slots(batch, b, j)`` sets the slots b .. b + slots - 1 of ``ks[j]``; after the run ``collect(batch)``
         is called once and what it returns once per recording, with its first slot (default: the slot's labels and iterations).
@@ -271,26 +279,30 @@ class DeviceStages:
                 for b, j in enumerate(members):
                     set_slots(batch, b * slots, j)
                 batch.run(maxIters, epsilon)
-                result_of = collect(batch) if collect else lambda b: (*batch.labels(b), batch.n_iters(b))
+                read_out = self._read_out(batch, decode)
+                result_of = collect(batch) if collect else lambda b: (*read_out(b), batch.n_iters(b))
                 for b, j in enumerate(members):
                     out[j] = result_of(b * slots)
             finally:
                 batch.close()
         return out
 
-    def vb(self, ks, labels, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
+    def vb(self, ks, labels, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb, decode='posterior'):
         """-> [(labels1st, labels2nd or None, iterations)] for the recordings ``ks`` with AHC labels ``labels``."""
         def set_slots(batch, b, j):
             batch.set_recording_resident(b, self.xv, self.row0[ks[j]], labels[j], init_smoothing, self.Phi, loopProb, Fa, Fb)
-        return self._run_batches(ks, [int(np.max(lab)) + 1 for lab in labels], 1, set_slots, maxIters, epsilon, precision)
+        return self._run_batches(ks, [int(np.max(lab)) + 1 for lab in labels], 1, set_slots, maxIters, epsilon, precision,
+                                 decode=decode)
 
-    def vb_random(self, ks, N, restarts, seed, names, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
+    def vb_random(self, ks, N, restarts, seed, names, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb,
+                  decode='posterior'):
         """-> [(labels1st, labels2nd or None, iterations, winning restart, [final ELBO of every restart])] for the recordings
         ``ks`` (``names[j]`` names ``ks[j]``) started from random labels over N states, ``--init random_N``.
 
         ONE ``vbx_batch`` of len(ks) x restarts slots, since every slot has N states: restart 0 of a recording owns its rho,
         the others share it.  The labels are drawn on the device from (seed, name, restart); after the run only the ELBOs come
-        back, the winner is picked here (``best_restart``) and only the winners' labels follow."""
+        back, the winner is picked here (``best_restart``) and only the winners' labels follow (``decode='viterbi'``: only the
+        winner is decoded)."""
         R = int(restarts)
         if R < 1 or int(N) < 1:
             raise ValueError(f'vb_random: restarts={restarts}, N={N}: both must be >= 1')
@@ -303,10 +315,11 @@ class DeviceStages:
 
         def winners(batch):
             elbos = batch.final_elbos()
+            read_out = self._read_out(batch, decode)
 
             def winner(b):
                 win = best_restart(elbos[b:b + R])
-                return (*batch.labels(b + win), batch.n_iters(b + win), win, elbos[b:b + R])
+                return (*read_out(b + win), batch.n_iters(b + win), win, elbos[b:b + R])
             return winner
         return self._run_batches(ks, [int(N)] * len(ks), R, set_slots, maxIters, epsilon, precision, collect=winners)
 
@@ -319,14 +332,14 @@ class DeviceStages:
             raise ValueError(f'recording {k}: {len(a)} windows in the segments file, {self.T[k]} x-vectors')
         return self._capi.turn_weights(self._thread_ctx(), a, b, u, v, spk, S, 0.0, want=('labels',))[0].astype(np.int64)
 
-    def vb_turns(self, ks, turns, segments, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb):
+    def vb_turns(self, ks, turns, segments, init_smoothing, maxIters, epsilon, precision, loopProb, Fa, Fb, decode='posterior'):
         """-> [(labels1st, labels2nd or None, iterations)] for the recordings ``ks`` started from given speaker turns, ``--init
         RTTM+VB``: ``turns[j]`` = (u, v, spk, S) and ``segments[j]`` = (a, b) of ``ks[j]``, all in ticks (``turn_init``).  The
         responsibilities are built on the device from the ticks (``Batch.set_recording_turns``)."""
         def set_slots(batch, b, j):
             (a, e), (u, v, spk, _S) = segments[j], turns[j]
             batch.set_recording_turns(b, self.xv, self.row0[ks[j]], a, e, u, v, spk, init_smoothing, self.Phi, loopProb, Fa, Fb)
-        return self._run_batches(ks, [int(t[3]) for t in turns], 1, set_slots, maxIters, epsilon, precision)
+        return self._run_batches(ks, [int(t[3]) for t in turns], 1, set_slots, maxIters, epsilon, precision, decode=decode)
 
     def close_thread_contexts(self):
         """The per-thread contexts (a HIP stream each) of the AHC stage: closed before the VB batch creates its stream
@@ -506,16 +519,19 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
     """The stages of ``diarize`` for recordings already in memory: ``[(name, seg_names, x_or_None)]``, ``segs_dict`` as
     ``read_xvector_timing_dict`` gives it, ``models`` from ``load_models``, ``args`` with the hyper-parameters
     (init, threshold, lda_dim, Fa, Fb, loopP, init_smoothing, output_2nd, out_rttm_dir and, optionally, precision,
-    ahc_scores, target_energy; init_rttm_dir with init = RTTM or RTTM+VB: ``<init_rttm_dir>/<name>.rttm`` is read for every
+    ahc_scores, target_energy, decode; init_rttm_dir with init = RTTM or RTTM+VB: ``<init_rttm_dir>/<name>.rttm`` is read for every
     recording given, and for no other).  Returns what ``diarize`` returns.
 
     ``xvectors``: the x-vectors of all recordings, in order, projected on the device already (``XVectors.from_device``,
     ``fea_dim`` = ``args.lda_dim``); the third entry of a recording is not read then and nothing is uploaded
     (``stages.project_device``).  ``stages`` adopts them: they are released with it (or by the caller of injected stages).
     ``t_start`` / ``t_read``: when the caller began and finished reading, for the timing (default: now)."""
-    from ._capi import MAX_SPEAKERS, VbxError
+    from ._capi import MAX_DECODE_STATES, MAX_SPEAKERS, VbxError
     assert 0 <= args.loopP <= 1, f'Expecting loopP between 0 and 1, got {args.loopP} instead.'
     ahc_kw = _ahc_kw(args, ahc_scores)
+    decode = getattr(args, 'decode', 'posterior')
+    if decode not in DECODES:
+        raise ValueError(f'decode must be one of {DECODES}, not {decode!r}')
     if t_read is None:
         t_read = time.perf_counter()
     if t_start is None:
@@ -560,11 +576,14 @@ def diarize_recordings(recordings, segs_dict, models, args, stages=None, log=pri
 
         # ---- stage 2: every recording of this rank in one batch ------------------------------------------------------
         n_states = {name: start.states(name, state[name]['labels1st']) for name in names}
-        failed.update((name, start.too_many(n)) for name, n in n_states.items() if n > MAX_SPEAKERS)
+        most = MAX_DECODE_STATES if decode == 'viterbi' and start.runs_vb else MAX_SPEAKERS
+        failed.update((name, start.too_many(n, most=most)) for name, n in n_states.items() if n > most)
         ks = [k for k, name in enumerate(names) if name not in failed]
         if start.runs_vb and recordings:
             common = dict(init_smoothing=args.init_smoothing, maxIters=40, epsilon=1e-6, precision=getattr(args, 'precision', 'fp64'),
                           loopProb=args.loopP, Fa=args.Fa, Fb=args.Fb)
+            if decode != 'posterior':                                 # (the default: the stage calls as they have always been)
+                common['decode'] = decode
 
             def finish(k, result):
                 st = state[names[k]]
@@ -631,8 +650,27 @@ def build_parser():
     p.add_argument('--precision', default='fp64', choices=['fp64', 'fp32', 'fp32-split'],
                    help='arithmetic of the VB-HMM kernels (fp64 = the reference\'s dtype and iteration counts)')
     p.add_argument('--timing', action='store_true', help='print a JSON line with the stage timings of this rank')
+    add_decode_argument(p)
     add_score_arguments(p)
     return p
+
+
+DECODES = ('posterior', 'viterbi')
+
+
+def add_decode_argument(p):
+    """``--decode`` of vbhmm, diarize and tune."""
+    p.add_argument('--decode', required=False, type=str, default='posterior', choices=list(DECODES),
+                   help='how the VB-HMM is read out.  posterior: every x-vector gets the speaker of its largest responsibility, '
+                        'frame by frame (what the reference driver writes; the default).  viterbi: the jointly most probable '
+                        'speaker sequence of the HMM under the model of the last iteration, decoded on the device (at most 1024 '
+                        'speakers per recording); with --output-2nd the second file holds the best other speaker of every frame')
+
+
+def check_decode_argument(args, error):
+    """After parsing: ``--decode viterbi`` decodes a VB-HMM, so an ``--init`` that runs none is refused."""
+    if getattr(args, 'decode', 'posterior') == 'viterbi' and not runs_vb(args.init):
+        return error(f'--decode viterbi needs the VB-HMM: --init {args.init} runs none (use {parse(args.init).use_instead})')
 
 
 def _init_argument(value):
@@ -690,6 +728,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_init_arguments(args, parser.error)
+    check_decode_argument(args, parser.error)
     if args.ref_rttm_dir is not None:
         try:
             check_ref_rttm_dir(args, int(os.environ.get('WORLD_SIZE', 1)))
